@@ -10,8 +10,10 @@ Prints ONE JSON line on rank 0 (see the contract in the task description):
   value     = whole-job A-images/s (N images of A per GPU per step; weak scaling, inputs resident in HBM)
   roofline  = algorithmic HBM bytes of one step (4.841 MB per A-image, fp32, chfak 1)
               / average duration of one step's HIP-graph launch, timed with HIP events on the launch stream
-  cpu_baseline = the CPU oracle (a port of the reference step, oracle/hourglass_ref.py) timed on this box's
+  cpu_baseline = (--full) the CPU oracle (a port of the reference step, oracle/hourglass_ref.py) timed on this box's
               host cores on a bounded sample of the same workload (rank 0, --gpus 1 only).
+  side      = (--full) the other BASELINE configurations, measured by a child process after the headline.
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs DIR if given and prints the line.
 """
 import argparse
 import json
@@ -103,10 +105,16 @@ def parse():
     ap.add_argument("--config", type=int, default=0,
                     help="5 = BASELINE config 5, a SIDE measurement: the build-defined 128x128 Hourglass (no reference counterpart) on the bf16 "
                          "kernels, batch 256: --mode train = the phase-2 training step, --mode infer = the eval-mode forward")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="headline line only: no CPU baseline and no side block (the quick form tools / tests use)")
+    ap.add_argument("--full", action="store_true",
+                    help="headline run: also measure the CPU baseline and the side block (BASELINE configs 4 and 5 and the paper's model size); "
+                         "a plain run times the headline step alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed seeded sample of anything larger)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no side block")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the side block (BASELINE configs 4 and 5 and the paper's model size, measured by ONE child process after the "
-                         "headline's timed region and reported under the extra key \"side\" of the same JSON line)")
+                    help="with --full: skip the side block (BASELINE configs 4 and 5 and the paper's model size, measured by ONE child process "
+                         "after the headline's timed region and reported under the extra key \"side\" of the same JSON line)")
     ap.add_argument("--side-timeout", type=float, default=240.0, help="seconds the parent waits for the side-block child")
     ap.add_argument("--side-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
@@ -117,7 +125,12 @@ def parse():
     ap.add_argument("--prime-s", type=float, default=0.4,
                     help="untimed graph replays for this many seconds right after capture (before the --warmup steps): lets the chip's "
                          "clocks settle from idle so that a short --steps/--warmup run measures the steady state; never inside the timed region")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode == "cli-train":
+        ap.error("--dump-outputs: --mode cli-train times a whole training loop, not a step whose outputs could be written")
+    return args
 
 
 def dp_graph_arg(args):
@@ -194,6 +207,34 @@ def g1_weights():
     pc = {k.split("/", 1)[1]: torch.from_numpy(v) for k, v in raw.items() if k.startswith("critic/")}
     pm = {k.split("/", 1)[1]: torch.from_numpy(v) for k, v in raw.items() if k.startswith("masker/")}
     return pc, pm
+
+
+DUMP_LIMIT_BYTES = 64_000_000      # --dump-outputs: all .npy payloads together (64 MB)
+
+
+def step_outputs(ret, state=None):
+    """The arrays a caller of the timed path holds after its last step.  A training step (`state` = the engine that owns flat / m / v):
+    the losses it returned and the parameters and Adam moments it updated in place.  An inference: the (pred, Z) it returned."""
+    if state is not None:
+        return {"losses": ret[:6], "params": state.flat, "adam_m": state.m, "adam_v": state.v}
+    pred, Z = ret
+    return {"pred": pred} if Z is None else {"pred": pred, "Z": Z}
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy, float64 kept, every other dtype as float32.  Above DUMP_LIMIT_BYTES in all, every
+    array is cut to the same fraction of its elements, drawn by a fixed seed, so that two builds write the same sample."""
+    import numpy as np
+    host = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = a.size * DUMP_LIMIT_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).permutation(a.size)[:keep])]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] outputs of the last timed step: {', '.join(sorted(host))} -> {out_dir}"
+          + (f" (a seeded sample: {total / 1e6:.0f} MB in all)" if total > DUMP_LIMIT_BYTES else ""), file=sys.stderr, flush=True)
 
 
 def host_cores():
@@ -373,7 +414,7 @@ def generic_mode(args, dev, rank):
 
         def run():
             c = gen.critic_forward(fc, lc, A, cf)
-            return gen.masker_forward(fm, lm, A, [c[f"e{i}"] for i in range(5)], cf)["Z"]
+            return c["pred"], gen.masker_forward(fm, lm, A, [c[f"e{i}"] for i in range(5)], cf)["Z"]
         flops = fcf + fmf
         what = f"eval-mode critic(collect) + masker forward, chfak {cf}: shape-generic MFMA kernels"
     prime_fixed(run, args.prime_s, 5.5 if args.mode == "train" else 1.2)
@@ -382,9 +423,11 @@ def generic_mode(args, dev, rank):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        last = run()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, step_outputs(last, eng if args.mode == "train" else None))
     ach = flops * n / dt / 1e12
     emit({"metric": f"Hourglass+critic {args.mode} images/sec, 64x64x3 batch={n}, chfak={cf} (generic kernels)", "value": n / dt,
                       "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt * 1e3,
@@ -425,9 +468,11 @@ def config5_mode(args, dev, pg=None, world=1, rank=0):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        last = run()
     barrier()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(last, net if train else None))
     if pg is not None:                           # max over ranks
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -494,9 +539,11 @@ def side_mode(args, dev, world, rank):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        last = run()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, step_outputs(last, eng if args.mode == "phase1" else None))
     ach = bytes_per_img * n / dt / 1e9
     emit({"metric": f"Hourglass {args.mode} images/sec, 64x64x3 batch={n}", "value": n / dt, "unit": "images/s",
                       "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True,
@@ -632,9 +679,9 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # the side block's child is started HERE, before this process creates its HIP context; it idles on a pipe until the headline is done
     headline = args.gpus == 1 and world == 1 and args.mode == "train" and args.chfak == 1 and args.config == 0 and not args.force_pg
-    # (--no-cpu-baseline = the quick form tools and tests use: headline line only, no side block either)
+    # (--full only: a plain run times the headline and nothing else; --full --no-cpu-baseline drops the side block too)
     # (no torch.cuda call before the fork: /dev/kfd says whether a GPU node exists; the child reports a missing GPU itself)
-    side_proc = start_side_child() if (headline and not args.no_side and not args.no_cpu_baseline and os.path.exists("/dev/kfd")) else None
+    side_proc = start_side_child() if (headline and args.full and not args.no_side and not args.no_cpu_baseline and os.path.exists("/dev/kfd")) else None
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the HIP path has no CPU fallback")
     if args.backend == "gloo":         # rehearsal: ranks share the visible GPU(s)
@@ -717,7 +764,7 @@ def main():
         t0 = time.perf_counter()
         ev0.record(stream)
         for _ in range(args.steps):
-            eng.phase2_step()
+            last = eng.phase2_step()
         ev1.record(stream)
         barrier()
         wall = time.perf_counter() - t0
@@ -733,7 +780,7 @@ def main():
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.SUM)
             per_rank_ms = [float(x) * 1e3 / args.steps for x in t.tolist()]
             wall = float(t.max().item())                      # MAX over ranks
-        return {"wall": wall, "dev_ms": dev_ms, "losses": losses, "per_rank_ms": per_rank_ms, "primed": primed}
+        return {"wall": wall, "dev_ms": dev_ms, "losses": losses, "per_rank_ms": per_rank_ms, "primed": primed, "last": last}
 
     dp_report = None
     if pg is None:
@@ -782,6 +829,8 @@ def main():
             eng.set_dp_launch_form(chosen == "graph")
     wall, dev_ms, losses, per_rank_ms, primed = res["wall"], res["dev_ms"], res["losses"], res["per_rank_ms"], res["primed"]
     if rank == 0:
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, step_outputs(res["last"], eng))
         ms_step = wall * 1e3 / args.steps
         launch_ms = dev_ms / args.steps
         achieved = ALGO_BYTES_PER_IMAGE * n / (launch_ms * 1e-3) / 1e9
@@ -828,7 +877,7 @@ def main():
             torch.cuda.synchronize()
             out["side"] = finish_side_child(side_proc, args.side_timeout)
             side_proc = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(n, args.cpu_steps, args.dropout)
         print(json.dumps(out), flush=True)
     if side_proc is not None:           # (not reached on rank 0 of a headline run; any other path that started one closes it)

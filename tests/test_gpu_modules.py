@@ -609,12 +609,12 @@ def test_rccl_path_one_rank_rehearsal():
     assert extra_ms < 0.10, "the data-parallel launch form must cost at most tens of microseconds over the single-GPU step"
 
 
-def test_bench_default_line_carries_the_side_block():
-    """The driver's command (`python bench.py --gpus 1 --steps K --warmup W`) prints ONE JSON line whose extra key "side" holds the other
+def test_bench_full_line_carries_the_side_block():
+    """`python bench.py --gpus 1 --steps K --warmup W --full` prints ONE JSON line whose extra key "side" holds the other
     BASELINE configurations, each measured by the child process after the headline's timed region: config 4 (fp16 inference, batch 2048),
     config 5 (128x128 bf16: training step and inference, batch 256), the paper's model size (chfak 5 training step)."""
     plain = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-steps", "1"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-steps", "1", "--full"],
                        capture_output=True, text=True, env=plain, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -630,6 +630,35 @@ def test_bench_default_line_carries_the_side_block():
         print(f"side {key}: {line['value'] / 1e3:.0f} k images/s, {line['ms_per_step']:.3f} ms, frac {line['roofline']['frac']:.3f} ({line['roofline']['bound']})")
     assert side["config4_fp16_infer_batch2048"]["config"]["batch"] == 2048 and side["config4_fp16_infer_batch2048"]["dtype"].startswith("f16")
     assert side["config5_train_batch256"]["config"]["batch"] == 256 and side["config5_train_batch256"]["dtype"].startswith("bf16")
+
+
+def test_bench_plain_run_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """The plain command (`python bench.py --gpus 1 --steps K --warmup W`) runs no side block and no CPU baseline, times exactly K steps, and
+    with --dump-outputs writes the last timed step's losses, parameters and Adam moments as float32 .npy files; two runs with the same
+    arguments start from the same inputs and write the same arrays."""
+    plain = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines, dumps = [], []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, env=plain, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        got = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(got) == 1, "exactly one JSON line on stdout"
+        lines.append(json.loads(got[0]))
+        dumps.append({f.stem: np.load(f) for f in sorted(out.glob("*.npy"))})
+    for d in lines:
+        assert "side" not in d and "cpu_baseline" not in d
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["unit"] == "images/s" and d["higher_is_better"] is True
+        assert d["ms_per_step"] > 0 and abs(d["value"] - 512 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    a, b = dumps
+    assert set(a) == {"losses", "params", "adam_m", "adam_v"}
+    assert a["losses"].shape == (6,) and all(a[k].shape == (25661,) for k in ("params", "adam_m", "adam_v"))
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64_000_000
+    np.testing.assert_allclose(a["losses"], [lines[0]["final_losses"][k] for k in ("critic", "replace", "inject", "l1", "l2", "total")], rtol=1e-6)
+    for k in a:
+        np.testing.assert_allclose(b[k], a[k], rtol=1e-5, atol=1e-6 * float(np.abs(a[k]).max()), err_msg=k)
 
 
 def test_bench_gpus_flag_starts_ranks_or_refuses():

@@ -306,3 +306,27 @@ def test_bench_side_child_exits_when_the_parent_goes_away():
     """The side-block child idles on its stdin pipe; EOF (the parent died before the go line) makes it exit without touching a GPU."""
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--side-child"], input="", capture_output=True, text=True, timeout=300)
     assert r.returncode == 3 and r.stdout.strip() == ""
+
+
+def test_bench_dump_outputs_are_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 stays float64, every other dtype becomes float32, shapes are kept under the byte budget; above it every
+    array is cut to the same fraction of its elements by a fixed seed (the same sample on every run) and the files fit the budget."""
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))   # bench sets it at import
+    import bench
+    arrays = {"h": torch.arange(12, dtype=torch.float16).reshape(3, 4), "d": torch.linspace(0, 1, 5, dtype=torch.float64),
+              "b": torch.ones(7, dtype=torch.bfloat16), "f": torch.randn(2, 2)}
+    bench.write_outputs(str(tmp_path / "all"), arrays)
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in arrays}
+    assert {k: v.dtype for k, v in got.items()} == {"h": np.float32, "d": np.float64, "b": np.float32, "f": np.float32}
+    for k, v in arrays.items():
+        np.testing.assert_array_equal(got[k], v.double().numpy())
+    big = {"x": torch.arange(10000, dtype=torch.float32), "y": torch.arange(3000, dtype=torch.float64)}
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8000)
+    for run in ("s1", "s2"):
+        bench.write_outputs(str(tmp_path / run), big)
+    s1 = {k: np.load(tmp_path / "s1" / f"{k}.npy") for k in big}
+    s2 = {k: np.load(tmp_path / "s2" / f"{k}.npy") for k in big}
+    assert sum(v.nbytes for v in s1.values()) <= 8000 and s1["x"].size > 0 and s1["y"].size > 0
+    for k in big:
+        np.testing.assert_array_equal(s1[k], s2[k])
+        assert len(np.unique(s1[k])) == s1[k].size and np.isin(s1[k], big[k].numpy()).all()

@@ -30,9 +30,9 @@ tools/sq_quick.sh final/sq_c5 --chfak 5 --mode train > $out/sq_c5.log 2>&1 && py
 tools/sq_quick.sh final/sq_c4 --mode infer --fp16 --batch 2048 > $out/sq_c4.log 2>&1 && python tools/sq_any.py gpurun_out/final/sq_c4 > $out/sq_config4.txt 2>&1
 fi
 if [ "$part" != "a" ]; then
-# the default line (200 steps) and the driver's command, both with the side block and the CPU baseline
-python bench.py > $out/bench.json 2> $out/bench.err || exit 1
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_cmd.json 2>/dev/null || exit 1
+# the default line (200 steps) and the driver's command, both --full: with the side block and the CPU baseline
+python bench.py --full > $out/bench.json 2> $out/bench.err || exit 1
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_driver_cmd.json 2>/dev/null || exit 1
 python bench.py --force-pg --no-cpu-baseline > $out/bench_force_pg.json 2>/dev/null || exit 1
 python bench.py --force-pg --dp-eager-allreduce --no-cpu-baseline > $out/bench_force_pg_eager.json 2>/dev/null || exit 1
 python bench.py --chfak 5 --mode infer --steps 20 --warmup 3 > $out/bench_chfak5_infer.json 2>/dev/null || exit 1
