@@ -47,6 +47,10 @@ class Pack16Job(C.Structure):        # = cgs_gen16_pack_job (include/cgs_hip.h)
     _fields_ = [("w", C.c_void_p), ("out", C.c_void_p), ("ca", i32), ("cb", i32), ("co", i32), ("transposed", i32)]
 
 
+class CrfParams(C.Structure):     # = cgs_crf_params (include/cgs_hip.h)
+    _fields_ = [("w_bilateral", f32), ("alpha", f32), ("beta", f32), ("w_gaussian", f32), ("gamma", f32), ("iterations", i32)]
+
+
 class ReduceJob(C.Structure):
     _fields_ = [("slab", C.c_void_p), ("dst", C.c_void_p), ("nslab", i32), ("stride", i32), ("count", i32),
                 ("accumulate", i32)]
@@ -186,6 +190,7 @@ SIGNATURES = {
     "cgs_gather_f32": (i32, [vp, vp, i32, vp, vp]),
     "cgs_gather_contrastive": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "cgs_dropout_mask": (i32, [Dropout, i64, vp, vp]),
+    "cgs_dense_crf2": (i32, [vp, vp, i32, i32, i32, C.POINTER(CrfParams), vp, vp, vp]),
     "cgs_build_arch": (C.c_char_p, []),
     "cgs_abi_version": (i32, []),
 }

@@ -2,9 +2,10 @@
 (main.py:66-156, 158-236, 238-312, 314-575, 584-591, 1103-1223) with its inner loops replaced by the fused
 HIP engine.  Same method names, same checkpoint / dataset file naming, same output file names.
 
-Out of scope here: CRF, videos / PNG debug grids.  ``collect_data`` reads an existing gz-pickle or, when the
+Out of scope here: videos / PNG debug grids.  ``collect_data`` reads an existing gz-pickle or, when the
 ``minerl`` package is importable, builds it from MineRL episodes exactly as the reference labels them (the MineRL download / decoder
-itself is the package's; it is absent from this image).  ``-eval`` (section 8 f2) is carried over without CRF / videos.
+itself is the package's; it is absent from this image).  ``-eval`` (section 8 f2) is carried over without videos; ``-crf`` runs the
+dense CRF of crf.py (exact mean field on the GPU) in both ``-process`` and ``-eval``.
 """
 import gzip
 import math
@@ -15,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, dataformat, parallel
+from .crf import dense_crf
 from .engine import HourglassEngine
 from .generic_engine import GenericEngine
 from .nets import NewCritic, UnetDecoder
@@ -398,8 +400,6 @@ class Handler:
         print("STARTING SEGMENTATION...")
         args = self.args
         os.makedirs(self.path, exist_ok=True)
-        if args.crf:
-            raise NotImplementedError("-crf is outside this build's scope")
         if args.noevalmode and args.salience:
             raise NotImplementedError("-noevalmode together with -salience (Dropout inside the saliency backward) is not implemented")
         if args.process_salience and not args.salience:
@@ -420,8 +420,13 @@ class Handler:
         cols = [M]
         if args.binarymaskthreshold:
             cols.append(M >= args.binarymaskthreshold)
+        if args.crf:                    # main.py:1169-1172 (with --binarymaskthreshold 0 this column lands in position 2)
+            cols.append(self.crf(frames, M, None))
         if args.process_salience:       # main.py:1176-1197
-            cols += list(self._saliency_post(sal, preds, args.salience_thresh, args.salglobal))
+            sal_maps, sal_hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
+            cols += [sal_maps, sal_hard]
+            if args.crf:                # main.py:1200-1203
+                cols.append(self.crf(frames, sal_maps, None))
         kinds = ("raw-mask", "thresholded-mask", "crf-mask", "saliency-map", "thresholded-saliency", "crf-saliency")
         out_dir = args.mask_output_imgs
         os.makedirs(out_dir, exist_ok=True)
@@ -473,6 +478,38 @@ class Handler:
         out = np.minimum(salM / (scale + tiny) * preds.reshape(-1, 1, 1, 1), 1.0)
         return out, (out > thresh).astype(np.uint8)
 
+    # ------------------------------------------------------------------ -crf: dense-CRF refinement of mask stacks
+    def crf(self, imgs, mask, Y, skip=1):
+        """main.py:1226-1263: every `skip`-th frame's mask [n,1,h,w] (P of label 1) refined by the two-label dense CRF at the reference's
+        parameters (crf.REFERENCE_PARAMS), the whole stack in one GPU call; the other frames keep their mask.  Returns (mask >= 1) as
+        NCHW bool.  imgs: NHWC uint8, or float in [0,1] (then (255 * img).astype(uint8) as the reference, which gives back the uint8 frame).
+        Like the reference, every 50th refined frame leaves {path}crf/{i}_mask.png, {i}_img.png, {i}_crf.png (rank 0).  Y (the labels the
+        reference's parameter grid is scored with) is not used: the grid has one point."""
+        mask = np.array(mask, copy=True)
+        imgs = np.asarray(imgs)[::skip]
+        frames = imgs if imgs.dtype == np.uint8 else (255 * imgs).astype(np.uint8)
+        prob = np.ascontiguousarray(mask[::skip, 0], dtype=np.float32)
+        labels = dense_crf(torch.from_numpy(np.ascontiguousarray(frames)).to(self.device),
+                           torch.from_numpy(prob).to(self.device)).cpu().numpy()
+        if self.rank == 0:
+            self._crf_debug_pngs(imgs, prob, labels)
+        mask[::skip, 0] = labels
+        return mask >= 1
+
+    def _crf_debug_pngs(self, imgs, prob, labels):
+        try:
+            import matplotlib
+            matplotlib.use("Agg")
+            from matplotlib import pyplot as plt
+        except Exception:
+            return
+        out = self.path + "crf/"
+        os.makedirs(out, exist_ok=True)
+        for i in range(0, len(labels), 50):
+            plt.imsave(out + f"{i}_mask.png", prob[i])
+            plt.imsave(out + f"{i}_img.png", imgs[i])
+            plt.imsave(out + f"{i}_crf.png", labels[i])
+
     # ------------------------------------------------------------------ -eval: IoU on the labelled red-trees set
     @staticmethod
     def get_iou(A, B):
@@ -482,15 +519,16 @@ class Handler:
         return round(both / either, 3) if either else float("nan")
 
     def eval(self, folder="", vis=False):
-        """main.py:891-1020 without CRF / videos: masks of `red-trees/X.npy[100:5000:2]` (batch 128, eval mode), thresholded
+        """main.py:891-1020 without videos: masks of `red-trees/X.npy[100:5000:2]` (batch 128, eval mode), thresholded
         at --eval-thresh, IoU against `all(Y.npy, axis=-1)`; with -salience also the saliency baseline of main.py:941-953,
-        976-1003 (|d mean(pred)/dX| summed over channels, normalised, weighted by pred, thresholded) and its IoU.
-        Returns [iou] or [iou, saliou] like the reference."""
+        976-1003 (|d mean(pred)/dX| summed over channels, normalised, weighted by pred, thresholded) and its IoU; with -crf the IoU of
+        the CRF-refined mask (and saliency map) as well.  Returns [iou, crfiou, saliou, salcrfiou] without the entries whose flag is
+        off, in the reference's order (main.py:1005-1015)."""
         args = self.args
         if args.noevalmode and args.salience:
             raise NotImplementedError("-noevalmode together with -salience (Dropout inside the saliency backward) is not implemented")
-        if args.crf or args.resimages or folder or vis:
-            raise NotImplementedError("-crf / -resimages / folder / video evaluation are outside this build's scope")
+        if args.resimages or folder or vis:
+            raise NotImplementedError("-resimages / folder / video evaluation are outside this build's scope")
         pick = slice(100, 5000, 2)                                        # the reference's evaluation subset
         frames = np.load("red-trees/X.npy")[pick]                         # uint8 [n,64,64,3] (the reference divides by 255 here)
         truth = np.load("red-trees/Y.npy")[pick].all(axis=-1)             # [n,64,64] bool: all three label channels set
@@ -503,9 +541,13 @@ class Handler:
 
         preds, M, sal = self._sweep_masks(frames, to_device, "eval at", want_saliency=want_sal)
         ious = [self.get_iou(M[:, 0] > args.eval_thresh, truth)]
+        if args.crf:                                                      # main.py:969-972
+            ious.append(self.get_iou(self.crf(frames, M, truth)[:, 0], truth))
         if want_sal:
-            _maps, hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
+            maps, hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
             ious.append(self.get_iou(hard[:, 0], truth))
+            if args.crf:                                                  # main.py:1000-1003
+                ious.append(self.get_iou(self.crf(frames, maps, truth)[:, 0], truth))
         print("\nRESULTS", ious)
         return ious
 

@@ -735,6 +735,22 @@ int cgs_gather_f32(const float* src, const int64_t* idx, int32_t n, float* dst, 
 int cgs_gather_contrastive(const uint8_t* xpos, const uint8_t* xneg, const float* ypos, const float* yneg, const int64_t* idx, int32_t n,
                            int32_t h, int32_t shift_px, uint8_t* a, uint8_t* b, float* y, cgs_stream_t stream);
 
+/* ---- dense-CRF mask refinement (csrc/crf.hip; Handler.crf, main.py:1226-1263) -----------------------------------------------------
+ * Two labels, Potts compatibility, the EXACT fully-connected mean field of DenseCRF2D's addPairwiseGaussian(gamma, Potts(w_gaussian)) +
+ * addPairwiseBilateral(alpha, beta, frame, Potts(w_bilateral)) with symmetric normalisation and unary -ln P (no permutohedral lattice).
+ * frames [n,h,w,3] uint8 (the colours), p1 [n,h,w] fp32: P(label 1), P(label 0) = 1 - p1; p1 of exactly 0 or 1 pins the label.
+ * labels [n,h,w] uint8 in {0,1}: label 1 iff a_1 - a_0 > 0 after `iterations` mean-field steps (iterations = 0: iff p1 > 1 - p1).
+ * q1_or_null [n,h,w] fp32 (optional): Q(label 1) after the last step.  Frames are independent: a frame's result does not depend on the
+ * batch it is in, and the summation order is fixed (bitwise reproducible).  h * w <= 16384, else CGS_ERR_UNSUPPORTED; n >= 1, positive
+ * stds and iterations >= 0, else CGS_ERR_BADARG.  Unlike the other entry points this one takes no workspace argument: it allocates its
+ * scratch (10 floats per pixel of at most 2^22 pixels) stream-ordered (hipMallocAsync / hipFreeAsync) on `stream`.                      */
+typedef struct {
+    float w_bilateral, alpha, beta, w_gaussian, gamma;
+    int32_t iterations;
+} cgs_crf_params;
+int cgs_dense_crf2(const uint8_t* frames, const float* p1, int32_t n, int32_t h, int32_t w, const cgs_crf_params* prm, uint8_t* labels,
+                   float* q1_or_null, cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
