@@ -106,18 +106,54 @@ def _drop(h, p, training, mask):
     return h * mask.to(h.dtype) / (1.0 - p)
 
 
+class _PoolAt(torch.autograd.Function):
+    """2x2 / stride-2 pooling at given flat plane indices (max_pool2d's ``return_indices`` form).  The forward is a gather written
+    into a tensor of max_pool2d's own memory layout and the backward IS max_pool2d's, so with max_pool2d's own indices every value
+    and gradient (and the layout of everything downstream) is bitwise the unpinned oracle's."""
+
+    @staticmethod
+    def forward(ctx, h, idx):
+        N, C, H, W = h.shape
+        out = F.max_pool2d(h, 2)
+        out.copy_(h.reshape(N, C, H * W).gather(2, idx.reshape(N, C, -1)).reshape(out.shape))
+        ctx.save_for_backward(h, idx)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        h, idx = ctx.saved_tensors
+        return torch.ops.aten.max_pool2d_with_indices_backward(dy, h, [2, 2], [2, 2], [0, 0], [1, 1], False, idx), None
+
+
+def pool_at(h: torch.Tensor, pick: torch.Tensor) -> torch.Tensor:
+    """2x2 / stride-2 pooling that takes, per window, the element at a GIVEN position instead of the maximum.  ``pick``: int64
+    [N, C, H/2, W/2], the position in the window row-major (0 = (0,0), 1 = (0,1), 2 = (1,0), 3 = (1,1)).  Autograd routes dy of a
+    window to exactly that pixel."""
+    H, W = h.shape[-2:]
+    pick = pick.to(torch.int64)
+    r = 2 * torch.arange(H // 2).view(-1, 1) + pick // 2
+    c = 2 * torch.arange(W // 2) + pick % 2
+    return _PoolAt.apply(h, r * W + c)
+
+
 def critic_apply(P: Params, X: torch.Tensor, collect: bool = False, p: float = 0.0,
-                 training: bool = False, masks: Optional[Sequence[torch.Tensor]] = None):
+                 training: bool = False, masks: Optional[Sequence[torch.Tensor]] = None,
+                 picks: Optional[Sequence[Optional[torch.Tensor]]] = None):
     """Encoder + critic head.  X is NCHW fp32 in [0,1].  ``masks`` (optional) are the three
     dropout keep-masks, shaped like embed2, embed3 and the first Linear's output.
+    ``picks`` (optional) are four window positions [N, C, H/2, W/2], one per pooling stage (features.0 / .3 / .6 / .10; see
+    ``pool_at``; None for a stage keeps max_pool2d there): the pooled value is relu(conv) at that position.  A checker uses them to
+    follow the pixel an implementation picked where a window's two largest values are a near-tie (fp32 and float64 rounding can
+    order those differently); where every value of a window is <= 0 any position gives 0 and no gradient.
     Returns pred [N,1] (and the 5 embeds when ``collect``): embeds are the four post-pool
     tensors taken BEFORE dropout plus the post-ReLU bottleneck (nets.py:200-205)."""
     m = list(masks) if masks is not None else [None, None, None]
+    pk = list(picks) if picks is not None else [None, None, None, None]
     h = X
     embeds = []
     for i, key in enumerate(ENC_CONV_KEYS):
         h = F.conv2d(h, P[key + ".weight"], P[key + ".bias"], stride=1, padding=1)
-        h = F.max_pool2d(F.relu(h), 2)
+        h = F.max_pool2d(F.relu(h), 2) if pk[i] is None else pool_at(F.relu(h), pk[i])
         embeds.append(h)
         if i >= 2:
             h = _drop(h, p, training, m[i - 2])
@@ -178,9 +214,9 @@ def shift_batch(X: torch.Tensor, shift: int, generator: Optional[torch.Generator
 # losses
 # --------------------------------------------------------------------------------------
 def phase1_loss(Pc: Params, XP: torch.Tensor, Y: torch.Tensor, threshrew: float = 0.0, p: float = 0.0,
-                training: bool = True, masks=None):
-    """Critic regression (main.py:189-195): mse(critic(X).squeeze(), Y) or BCE under --threshrew."""
-    pred = critic_apply(Pc, XP, p=p, training=training, masks=masks).squeeze()
+                training: bool = True, masks=None, picks=None):
+    """Critic regression (main.py:189-195): mse(critic(X).squeeze(), Y) or BCE under --threshrew.  ``picks``: critic_apply's."""
+    pred = critic_apply(Pc, XP, p=p, training=training, masks=masks, picks=picks).squeeze()
     if threshrew:
         return F.binary_cross_entropy(pred, Y), pred
     return F.mse_loss(pred, Y), pred
@@ -189,15 +225,17 @@ def phase1_loss(Pc: Params, XP: torch.Tensor, Y: torch.Tensor, threshrew: float 
 def phase2_loss(Pc: Params, Pm: Params, A: torch.Tensor, B: torch.Tensor, Y: torch.Tensor,
                 lfak: float = 5, L1: float = 0.5, L2: float = 0.0, inject: bool = True, live: bool = True,
                 threshrew: float = 0.0, p: float = 0.0, training: bool = True, masks=None, Ps: Optional[Params] = None,
-                staticnorm: bool = True):
+                staticnorm: bool = True, picks=None):
     """Joint mask/critic objective of one phase-2 step (main.py:364-429, staticnorm => valuefak=1).
 
     ``masks`` (optional) = 4 lists of 3 dropout keep-masks for the passes [A, B, replaced, injected]
-    in the order the reference draws them (a 5th list: the second critic's pass over A).  ``Ps``: parameters of the second
+    in the order the reference draws them (a 5th list: the second critic's pass over A).  ``picks`` (optional): likewise one
+    list of critic_apply's four pool picks per pass, in the same order.  ``Ps``: parameters of the second
     critic of -separate (main.py:389-390): the masker then takes ITS embeds of A.  Returns (total, parts dict, Z, pred)."""
     mk = masks if masks is not None else [None, None, None, None, None]
-    pred, embeds = critic_apply(Pc, A, collect=True, p=p, training=training, masks=mk[0])
-    negpred = critic_apply(Pc, B, p=p, training=training, masks=mk[1])
+    pk = picks if picks is not None else [None, None, None, None, None]
+    pred, embeds = critic_apply(Pc, A, collect=True, p=p, training=training, masks=mk[0], picks=pk[0])
+    negpred = critic_apply(Pc, B, p=p, training=training, masks=mk[1], picks=pk[1])
     pred = pred.squeeze()
     negpred = negpred.squeeze().detach()
     total = 0
@@ -207,16 +245,17 @@ def phase2_loss(Pc: Params, Pm: Params, A: torch.Tensor, B: torch.Tensor, Y: tor
         total = total + lfak * cl
         parts["critic"] = cl
     if Ps is not None:
-        _, embeds = critic_apply(Ps, A, collect=True, p=p, training=training, masks=mk[4] if len(mk) > 4 else None)
+        _, embeds = critic_apply(Ps, A, collect=True, p=p, training=training, masks=mk[4] if len(mk) > 4 else None,
+                                 picks=pk[4] if len(pk) > 4 else None)
     Z = masker_apply(Pm, A, embeds)
     replaced = A * (1 - Z) + Z * B
-    rv = critic_apply(Pc, replaced, p=p, training=training, masks=mk[2]).squeeze()
+    rv = critic_apply(Pc, replaced, p=p, training=training, masks=mk[2], picks=pk[2]).squeeze()
     rl = F.mse_loss(rv, negpred.detach())
     total = total + rl
     parts["replace"] = rl
     if inject:
         injected = B * (1 - Z) + Z * A
-        iv = critic_apply(Pc, injected, p=p, training=training, masks=mk[3]).squeeze()
+        iv = critic_apply(Pc, injected, p=p, training=training, masks=mk[3], picks=pk[3]).squeeze()
         il = F.mse_loss(iv, pred.detach())
         total = total + il
         parts["inject"] = il
@@ -264,10 +303,23 @@ def leafify(P: Params) -> Params:
     return {k: v.detach().clone().requires_grad_(True) for k, v in P.items()}
 
 
-def train_phase2(Pc: Params, Pm: Params, batches, steps: int, live=True, Ps: Optional[Params] = None, **loss_kw):
+def _rows(obj, a: int, b: int):
+    """Images a:b of every tensor in a (nested) list of per-image tensors -- dropout masks, pool picks; None stays None."""
+    if obj is None:
+        return None
+    if isinstance(obj, torch.Tensor):
+        return obj[a:b]
+    return [_rows(o, a, b) for o in obj]
+
+
+def train_phase2(Pc: Params, Pm: Params, batches, steps: int, live=True, Ps: Optional[Params] = None, chunk: Optional[int] = None,
+                 **loss_kw):
     """Runs ``steps`` optimiser steps of phase 2 on (A,B,Y) batches; returns per-step records.
     Optimiser membership follows main.py:330-334 (critic+masker when live, masker only when frozen; + the second critic
-    of -separate in both cases)."""
+    of -separate in both cases).
+    ``chunk``: evaluate the step over slices of that many images (masks / picks sliced alike) and sum their gradients, each slice's
+    loss weighted by its share of the batch -- every loss term is a per-image mean, so this is the whole-batch step at a fraction of
+    the memory (float64 at the paper's model size and N = 512 needs ~11 GB in one piece)."""
     Pc, Pm = leafify(Pc), leafify(Pm)
     Ps = leafify(Ps) if Ps is not None else None
     keys = ([("c", k) for k in Pc] if live else []) + [("m", k) for k in Pm] + ([("s", k) for k in Ps] if Ps is not None else [])
@@ -278,9 +330,25 @@ def train_phase2(Pc: Params, Pm: Params, batches, steps: int, live=True, Ps: Opt
         A, B, Y = batches[s % len(batches)]
         for t in list(Pc.values()) + list(Pm.values()) + (list(Ps.values()) if Ps is not None else []):
             t.grad = None
-        total, parts, Z, pred = phase2_loss(Pc, Pm, A, B, Y, live=live, Ps=Ps, **loss_kw)
-        total.backward()
-        rec = dict(total=float(total.detach()), parts={k: float(v.detach()) for k, v in parts.items()},
+        n = len(A)
+        size = n if not chunk else int(chunk)
+        tot, psum, Zs, preds = 0.0, {}, [], []
+        for a in range(0, n, size):
+            b = min(n, a + size)
+            kw = dict(loss_kw)
+            for k in ("masks", "picks"):
+                kw[k] = _rows(kw.get(k), a, b)
+            total, parts, Z, pred = phase2_loss(Pc, Pm, A[a:b], B[a:b], Y[a:b], live=live, Ps=Ps, **kw)
+            w = (b - a) / n
+            (total * w if size < n else total).backward()
+            tot += float(total.detach()) * w
+            for k, v in parts.items():
+                psum[k] = psum.get(k, 0.0) + float(v.detach()) * w
+            Zs.append(Z.detach())
+            preds.append(pred.detach())
+        if len(Zs) > 1:
+            Z, pred = torch.cat(Zs), torch.cat([q.reshape(-1) for q in preds])
+        rec = dict(total=tot, parts=psum,
                    grads_c={k: (v.grad.clone() if v.grad is not None else None) for k, v in Pc.items()},
                    grads_m={k: (v.grad.clone() if v.grad is not None else None) for k, v in Pm.items()},
                    Z=Z.detach().clone(), pred=pred.detach().clone())
@@ -296,6 +364,7 @@ def train_phase2(Pc: Params, Pm: Params, batches, steps: int, live=True, Ps: Opt
 
 
 def train_phase1(Pc: Params, batches, steps: int, **loss_kw):
+    """Phase-1 steps on (X, Y) batches; ``loss_kw`` as phase1_loss (masks, picks, ...)."""
     Pc = leafify(Pc)
     tensors = list(Pc.values())
     opt = AdamRef(tensors)

@@ -9,6 +9,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import hourglass_ref as orc
+import pool_picks
 from test_gpu_kernels import rel_close
 
 
@@ -166,7 +167,8 @@ def _export_masks(e, n_imgs_total, step_value):
 
 @pytest.mark.parametrize("n", [12, 512])
 def test_phase2_with_dropout_vs_oracle_masks(g1, n):
-    """dropout 0.3, train mode: the oracle is fed the keep-masks the kernels drew (slot order B, A, rep, inj).
+    """dropout 0.3, train mode: the oracle is fed the keep-masks the kernels drew (slot order B, A, rep, inj) and follows their 2x2 max-pool
+    picks (tests/pool_picks.py; check_picks asserts each pick is float64's except on near-ties, so the bound holds for any seed).
     n = 512 is the benchmark configuration itself (BASELINE.json config 2): losses, all 28 gradients, updated parameters."""
     rs = np.random.RandomState(42)
     dev = torch.device("cuda:0")
@@ -182,15 +184,25 @@ def test_phase2_with_dropout_vs_oracle_masks(g1, n):
     sl = {"B": slice(0, n), "A": slice(n, 2 * n), "rep": slice(2 * n, 3 * n), "inj": slice(3 * n, 4 * n)}
     omasks = [[m[sl[k]] for m in masks] for k in ("A", "B", "rep", "inj")]  # oracle order: A, B, replaced, injected
     pc, pm = g1
+    # the argmax nibbles of all four stages and passes, and each stage's input as the kernels computed it: the mixes are formed in
+    # features.0's tile loaders from A, B and Z (elementwise.hip / conv_tile.h), features.10 reads e2 through its dropout mask
+    picks, dead = pool_picks.buffer_picks(e.cbuf, 4 * n)
+    a32, b32, z = e.ab[n:].float() / 255.0, e.ab[:n].float() / 255.0, e.mbuf["Z"].unsqueeze(-1)
+    x0 = torch.cat((b32, a32, a32 * (1.0 - z) + z * b32, b32 * (1.0 - z) + z * a32))
+    e2d = e.cbuf["e2"] * (masks[0].permute(0, 2, 3, 1).to(dev) / 0.7)
+    flips = pool_picks.check_picks(pc, [x0, e.cbuf["e0"], e.cbuf["e1"], e2d], picks, dead, what=f"chfak 1 n={n}")
+    nflip = pool_picks.report(flips, f"chfak 1 n={n}")
+    assert nflip <= max(4, n // 8), f"pool picks differ from float64 on {nflip} near-tied cells: {flips}"
+    opicks = pool_picks.oracle_order(picks, n)
     if n == 512:
         # At 2 M pixels per weight the CPU's own fp32 summation is off by 1-3e-3 of a tensor's maximum on the mask-head
         # gradients (measured against float64), more than the tolerance: the checker runs in float64 here.
         dd = lambda P: {k: v.double() for k, v in P.items()}
         rec = orc.train_phase2(dd(pc), dd(pm), [(orc.u8_to_nchw(A).double(), orc.u8_to_nchw(B).double(), torch.from_numpy(Y).double())],
-                               steps=1, p=0.3, training=True, masks=[[m.double() for m in mm] for mm in omasks])[0]
+                               steps=1, p=0.3, training=True, masks=[[m.double() for m in mm] for mm in omasks], picks=opicks, chunk=128)[0]
     else:
         rec = orc.train_phase2(pc, pm, [(orc.u8_to_nchw(A), orc.u8_to_nchw(B), torch.from_numpy(Y))], steps=1,
-                               p=0.3, training=True, masks=omasks)[0]
+                               p=0.3, training=True, masks=omasks, picks=opicks)[0]
     parts = rec["parts"]
     np.testing.assert_allclose(losses[:4], [parts["critic"], parts["replace"], parts["inject"], parts["norm"]], rtol=1e-3)
     gc, gm = e.lc.unflatten(e.gc), e.lm.unflatten(e.gm)

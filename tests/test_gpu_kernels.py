@@ -8,16 +8,16 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import hourglass_ref as orc
+import pool_picks
 
 
 REL_REPORT = {}       # what -> worst PURE relative error over the elements above 1 % of the tensor's maximum (summary test below)
 
 
-def rel_close(got, ref, what, rtol=1e-3, atol_scale=2e-5, report=True):
+def rel_close(got, ref, what, rtol=1e-3, atol_scale=2e-5):
     """|got - ref| <= rtol |ref| + atol_scale max|ref| elementwise.  The absolute term only covers values near zero; the worst
-    pure-relative error of the elements that carry the tensor (>= 1 % of its maximum) is recorded and shown on failure.
-    report = False: the comparison is not entered into the summary of test_zz_rel_summary.py (a tensor whose difference from the
-    checker is a counted discrete effect -- pool picks of near-tied cells at fp32 vs float64 -- not rounding)."""
+    pure-relative error of the elements that carry the tensor (>= 1 % of its maximum) is recorded (for the summary of
+    test_zz_rel_summary.py) and shown on failure."""
     got = np.asarray(got, dtype=np.float64)
     ref = np.asarray(ref, dtype=np.float64)
     assert got.shape == ref.shape, f"{what}: shape {got.shape} vs {ref.shape}"
@@ -26,8 +26,7 @@ def rel_close(got, ref, what, rtol=1e-3, atol_scale=2e-5, report=True):
     err = np.abs(got - ref)
     big = np.abs(ref) >= 1e-2 * mx
     worst_rel = float((err[big] / np.abs(ref[big])).max()) if big.any() else 0.0
-    if report:
-        REL_REPORT[what] = max(REL_REPORT.get(what, 0.0), worst_rel)
+    REL_REPORT[what] = max(REL_REPORT.get(what, 0.0), worst_rel)
     bad = err > (rtol * np.abs(ref) + atol)
     assert not bad.any(), (f"{what}: {bad.sum()}/{bad.size} outside tol; max err {err.max():.3e} "
                            f"(ref max {np.abs(ref).max():.3e}) at {np.unravel_index(err.argmax(), err.shape)}; "
@@ -172,35 +171,11 @@ def test_pool_argmax_first_index_on_ties(ctx):
     assert ties_total > 5000, f"the tie set exercised only {ties_total} positive ties"
 
 
-def drop_near_tie_images(pc, x_u8, rel=3e-6):
-    """Two fp32 implementations that sum a convolution in different orders can disagree on WHICH element of a 2x2 window is
-    the maximum when its two largest values differ by a few ulps (not an exact tie); the pooling gradient then takes another
-    route and every upstream gradient moves by one window's worth.  Images containing such a window (float64 oracle, any of the
-    four pooling stages) are left out of the gradient comparisons; exact ties stay in (they must resolve identically)."""
-    F = torch.nn.functional
-    keep = np.ones(len(x_u8), bool)
-    with torch.no_grad():
-        h = orc.u8_to_nchw(x_u8).double()
-        for key in ("features.0", "features.3", "features.6", "features.10"):
-            pre = torch.relu(F.conv2d(h, pc[key + ".weight"].double(), pc[key + ".bias"].double(), padding=1))
-            n, c, hw = pre.shape[0], pre.shape[1], pre.shape[-1]
-            top2 = pre.unfold(2, 2, 2).unfold(3, 2, 2).reshape(n, c, hw // 2, hw // 2, 4).topk(2, dim=-1).values
-            gap = top2[..., 0] - top2[..., 1]
-            near = (gap > 0) & (gap < rel * top2[..., 0].abs()) & (top2[..., 0] > 0)
-            keep &= ~near.flatten(1).any(1).numpy()
-            h = F.max_pool2d(pre, 2)
-    dropped = int((~keep).sum())
-    print(f"drop_near_tie_images: {dropped} of {len(x_u8)} images hold a near-tie pooling window and are left out")
-    # a loader / indexing bug that only hits some images must not be able to hide behind this filter
-    assert dropped <= max(1, len(x_u8) // 10), f"{dropped} of {len(x_u8)} images dropped as near ties: more than 10 %"
-    return x_u8[keep]
-
-
-def _oracle_grads(ctx, x_u8, cot_pred, cot_embeds, cot_Z, f32_input=False):
+def _oracle_grads(ctx, x_u8, cot_pred, cot_embeds, cot_Z, f32_input=False, picks=None):
     pc = orc.leafify(ctx["pc"])
     pm = orc.leafify(ctx["pm"])
     X = orc.u8_to_nchw(x_u8).requires_grad_(f32_input)
-    pred, embeds = orc.critic_apply(pc, X, collect=True)
+    pred, embeds = orc.critic_apply(pc, X, collect=True, picks=picks)
     Z, inter = orc.masker_apply(pm, X.detach(), embeds, return_all=True)
     loss = (pred[:, 0] * cot_pred).sum() + (Z[:, 0] * cot_Z).sum()
     for e, c in zip(embeds, cot_embeds):
@@ -211,24 +186,27 @@ def _oracle_grads(ctx, x_u8, cot_pred, cot_embeds, cot_Z, f32_input=False):
 
 @pytest.mark.parametrize("n,kind", [(8, "noise"), (21, "noise"), (13, "ties")])
 def test_backward_matches_oracle_autograd(ctx, n, kind):
-    """critic + masker backward with random cotangents on every output, vs torch autograd on the oracle.
-    kind = ties: flat-patch frames, where the pooling gradient must follow max_pool2d's first-index rule."""
+    """critic + masker backward with random cotangents on every output, vs torch autograd on the oracle, every image.
+    kind = ties: flat-patch frames, where the pooling gradient must follow max_pool2d's first-index rule.
+    The oracle follows the kernels' 2x2 max-pool picks (the argmax nibbles critic_forward writes for all four stages): where a window's
+    two largest values are a near-tie fp32 and float64 may pick different pixels; check_picks asserts that this is the only way the
+    picks differ (an exact tie must take max_pool2d's first index) and the count stays small."""
     hg, dev, lc, lm = ctx["hg"], ctx["dev"], ctx["lc"], ctx["lm"]
     rs = np.random.RandomState(n)
     x_u8 = rs.randint(0, 256, (n, 64, 64, 3)).astype(np.uint8) if kind == "noise" else tie_frames(n, 7)
-    if kind == "noise":
-        x_u8 = drop_near_tie_images(ctx["pc"], x_u8)
-    assert len(x_u8) >= n // 2
-    n = len(x_u8)
     cot_pred = torch.from_numpy(rs.randn(n).astype(np.float32))
     cot_Z = torch.from_numpy(rs.randn(n, 64, 64).astype(np.float32) * 0.1)
     shapes = [(n, 8, 32, 32), (n, 8, 16, 16), (n, 8, 8, 8), (n, 16, 4, 4), (n, 32, 1, 1)]
     cot_e = [torch.from_numpy(rs.randn(*s).astype(np.float32) * 0.05) for s in shapes]
-    pc, pm, X, Z = _oracle_grads(ctx, x_u8, cot_pred, cot_e, cot_Z, f32_input=True)
 
     xd = torch.from_numpy(x_u8).to(dev)
     xf = (xd.float() / 255.0).contiguous()   # fp32 image path so that the image gradient can be checked too
     c = hg.critic_forward(ctx["fc"], lc, xf, n)
+    picks, dead = pool_picks.buffer_picks(c, n)
+    flips = pool_picks.check_picks(ctx["pc"], [xf, c["e0"], c["e1"], c["e2"]], picks, dead, what=f"{kind} n={n}")
+    nflip = pool_picks.report(flips, f"critic_forward {kind} n={n}")
+    assert nflip <= max(1, n // 10), f"pool picks differ from float64 on {nflip} near-tied cells: {flips}"
+    pc, pm, X, Z = _oracle_grads(ctx, x_u8, cot_pred, cot_e, cot_Z, f32_input=True, picks=picks)
     embeds = [c[f"e{i}"] for i in range(5)]
     m = hg.masker_forward(ctx["fm"], lm, xf, embeds, n)
     Zd = m["Z"]

@@ -105,7 +105,7 @@ def test_g9_main_train_reproduces_the_reference_run(tmp_path, monkeypatch):
     # steps from the reference's own pre-step state, tight bounds).  A fresh critic's TRAJECTORY is chaotic: Adam's normalised step turns an
     # fp32 summation-order difference on a near-zero gradient element into a full-size update and the runs drift apart by ~1.3x per step
     # (reproduced on the CPU alone: test_g9_phase1_trajectory_is_sensitive_to_gradient_rounding).  Measured on MI355X: 1.2e-7 / 7.6e-5 /
-    # 8.4e-3, parameters 1.7e-2; the loose end bounds only catch a run that went somewhere else entirely.
+    # 8.4e-3, parameters 1.7e-2; the wide end bounds only catch a run that went somewhere else entirely.
     assert e1[:8].max() <= 1e-5 and e1[:24].max() <= 1e-3 and e1.max() <= 5e-2
     assert ec <= 6e-2
     assert sorted(os.listdir("m/saves")) == json.loads(str(g["listing_json"]))["saves"]                  # both checkpoint names
@@ -231,7 +231,7 @@ def test_g11_collect_data_under_a_stub_minerl_writes_the_reference_pickle(tmp_pa
 
 
 def test_g12_phase1_single_steps_from_the_reference_states():
-    """Phase 1 pinned STEP BY STEP (replaces the loose end-of-trajectory bound of run A as the parity statement for
+    """Phase 1 pinned STEP BY STEP (replaces the wide end-of-trajectory bound of run A as the parity statement for
     row a9 at the loop level): for EACH of the 48 batches of the reference's `main.py -train` run (G9) the engine is put into the
     reference's recorded state before that batch -- critic parameters, Adam moments, step count (G12) -- runs ONE phase1_step on the recorded
     frames (DataLoader indices + shift draws of G9) and is compared with what the reference computed: the loss, all 14 gradients, and the

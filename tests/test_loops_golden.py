@@ -215,7 +215,7 @@ def test_g12_oracle_single_steps_from_the_reference_states():
 
 
 def test_g9_phase1_trajectory_is_sensitive_to_gradient_rounding():
-    """Why tests/test_gpu_loops.py bounds the END of the GPU's phase-1 trajectory loosely (loss 5e-2, parameters 6e-2) while its first steps
+    """Why tests/test_gpu_loops.py bounds the END of the GPU's phase-1 trajectory with wide bounds (loss 5e-2, parameters 6e-2) while its first steps
     agree to 1e-7: the oracle itself, replaying the reference's 48 recorded batches twice -- once as is, once with every gradient tensor
     perturbed by Gaussian noise of 3e-7 of its largest element (the size of an fp32 summation-order difference) -- ends 1e-3..1e-2 apart in
     the loss and in the parameters, because Adam's normalised step m / sqrt(v) turns a relative error on a near-zero gradient element into a
