@@ -51,6 +51,15 @@ class CrfParams(C.Structure):     # = cgs_crf_params (include/cgs_hip.h)
     _fields_ = [("w_bilateral", f32), ("alpha", f32), ("beta", f32), ("w_gaussian", f32), ("gamma", f32), ("iterations", i32)]
 
 
+class VideoCell(C.Structure):    # = cgs_video_cell (include/cgs_hip.h)
+    _fields_ = [("src", C.c_void_p), ("y", C.c_void_p), ("value", C.c_double), ("kind", i32), ("mode", i32)]
+
+
+VIDEO_RGB8, VIDEO_MASK8, VIDEO_F32, VIDEO_F64 = 0, 1, 2, 3
+VIDEO_GREY, VIDEO_CODE, VIDEO_CONST = 0, 1, 2
+VIDEO_MAX_CELLS, VIDEO_NONTEMPORAL = 16, 1
+
+
 class ReduceJob(C.Structure):
     _fields_ = [("slab", C.c_void_p), ("dst", C.c_void_p), ("nslab", i32), ("stride", i32), ("count", i32),
                 ("accumulate", i32)]
@@ -191,6 +200,7 @@ SIGNATURES = {
     "cgs_gather_contrastive": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "cgs_dropout_mask": (i32, [Dropout, i64, vp, vp]),
     "cgs_dense_crf2": (i32, [vp, vp, i32, i32, i32, C.POINTER(CrfParams), vp, vp, vp]),
+    "cgs_video_compose": (i32, [C.POINTER(VideoCell), i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp]),
     "cgs_build_arch": (C.c_char_p, []),
     "cgs_abi_version": (i32, []),
 }

@@ -2,6 +2,7 @@
 
     python main.py -train --model DIR
     python main.py -process [-concatenated] [--binarymaskthreshold t] --model DIR --source-imgs S --mask-output-imgs R
+    python main.py -test --model DIR --output-video V       (evaluation sweep + the evaluation video V/iou=....mp4)
 
 Every flag of the reference parses (same names, defaults and the ``type=bool`` quirk: ``-cload False`` is
 still True, as in the reference); flags whose code path is outside this build raise NotImplementedError

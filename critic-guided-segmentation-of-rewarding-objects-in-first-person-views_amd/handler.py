@@ -2,10 +2,11 @@
 (main.py:66-156, 158-236, 238-312, 314-575, 584-591, 1103-1223) with its inner loops replaced by the fused
 HIP engine.  Same method names, same checkpoint / dataset file naming, same output file names.
 
-Out of scope here: videos / PNG debug grids.  ``collect_data`` reads an existing gz-pickle or, when the
-``minerl`` package is importable, builds it from MineRL episodes exactly as the reference labels them (the MineRL download / decoder
-itself is the package's; it is absent from this image).  ``-eval`` (section 8 f2) is carried over without videos; ``-crf`` runs the
-dense CRF of crf.py (exact mean field on the GPU) in both ``-process`` and ``-eval``.
+Out of scope here: the -viscritic / -vismasker videos and the PNG debug grids.  ``collect_data`` reads an
+existing gz-pickle or, when the ``minerl`` package is importable, builds it from MineRL episodes exactly as the reference labels them
+(the MineRL download / decoder itself is the package's; it is absent from this image).  ``-eval`` (section 8 f2) is carried over, with
+the evaluation video of ``-test`` / ``--output-video`` (video.py: frames composed on the GPU); ``-crf`` runs the dense CRF of crf.py
+(exact mean field on the GPU) in both ``-process`` and ``-eval``.
 """
 import gzip
 import math
@@ -15,7 +16,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, dataformat, parallel
+from . import _lib, dataformat, parallel, video
 from .crf import dense_crf
 from .engine import HourglassEngine
 from .generic_engine import GenericEngine
@@ -519,16 +520,18 @@ class Handler:
         return round(both / either, 3) if either else float("nan")
 
     def eval(self, folder="", vis=False):
-        """main.py:891-1020 without videos: masks of `red-trees/X.npy[100:5000:2]` (batch 128, eval mode), thresholded
+        """main.py:891-1087: masks of `red-trees/X.npy[100:5000:2]` (batch 128, eval mode), thresholded
         at --eval-thresh, IoU against `all(Y.npy, axis=-1)`; with -salience also the saliency baseline of main.py:941-953,
         976-1003 (|d mean(pred)/dX| summed over channels, normalised, weighted by pred, thresholded) and its IoU; with -crf the IoU of
         the CRF-refined mask (and saliency map) as well.  Returns [iou, crfiou, saliou, salcrfiou] without the entries whose flag is
-        off, in the reference's order (main.py:1005-1015)."""
+        off, in the reference's order (main.py:1005-1015).  With -test, or --output-video, rank 0 then writes the evaluation video of
+        main.py:1027-1087 (video.py) when the IoU is above 0; its layout and ffmpeg are checked before the sweep."""
         args = self.args
         if args.noevalmode and args.salience:
             raise NotImplementedError("-noevalmode together with -salience (Dropout inside the saliency backward) is not implemented")
         if args.resimages or folder or vis:
-            raise NotImplementedError("-resimages / folder / video evaluation are outside this build's scope")
+            raise NotImplementedError("-resimages / folder evaluation are outside this build's scope")
+        vid = (video.plan(bool(args.crf), bool(args.salience)), video.find_ffmpeg()) if video.wanted(args) else None
         pick = slice(100, 5000, 2)                                        # the reference's evaluation subset
         frames = np.load("red-trees/X.npy")[pick]                         # uint8 [n,64,64,3] (the reference divides by 255 here)
         truth = np.load("red-trees/Y.npy")[pick].all(axis=-1)             # [n,64,64] bool: all three label channels set
@@ -540,15 +543,26 @@ class Handler:
             return (t.double() / 255.0).float() if (t.dtype != torch.uint8 or want_sal) else t
 
         preds, M, sal = self._sweep_masks(frames, to_device, "eval at", want_saliency=want_sal)
-        ious = [self.get_iou(M[:, 0] > args.eval_thresh, truth)]
+        hard_m = M[:, 0] > args.eval_thresh
+        ious = [self.get_iou(hard_m, truth)]
+        crf_m = maps = sal_hard = sal_crf = None
         if args.crf:                                                      # main.py:969-972
-            ious.append(self.get_iou(self.crf(frames, M, truth)[:, 0], truth))
+            crf_m = self.crf(frames, M, truth)[:, 0]
+            ious.append(self.get_iou(crf_m, truth))
         if want_sal:
-            maps, hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
-            ious.append(self.get_iou(hard[:, 0], truth))
+            maps, sal_hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
+            ious.append(self.get_iou(sal_hard[:, 0], truth))
             if args.crf:                                                  # main.py:1000-1003
-                ious.append(self.get_iou(self.crf(frames, maps, truth)[:, 0], truth))
+                sal_crf = self.crf(frames, maps, truth)[:, 0]
+                ious.append(self.get_iou(sal_crf, truth))
         print("\nRESULTS", ious)
+        if vid is not None and self.rank == 0 and ious[0] > self.ious[0]:          # main.py:1027
+            layout, exe = vid
+            sources = {"X": frames, "Y": truth, "M": M[:, 0], "hardM": hard_m, "crfM": crf_m, "salM": maps[:, 0],
+                       "salhardM": sal_hard[:, 0], "salcrfM": sal_crf}
+            path = video.output_path(args.output_video, ious[0])
+            n = video.write_video(path, layout, {k: v for k, v in sources.items() if v is not None}, self.device, ffmpeg=exe)
+            print(f"video: {path} ({n} frames of {layout.width}x{layout.height})")
         return ious
 
     # ------------------------------------------------------------------ helpers

@@ -751,6 +751,31 @@ typedef struct {
 int cgs_dense_crf2(const uint8_t* frames, const float* p1, int32_t n, int32_t h, int32_t w, const cgs_crf_params* prm, uint8_t* labels,
                    float* q1_or_null, cgs_stream_t stream);
 
+/* ---- evaluation-video frame composition (csrc/video.hip; Handler.eval's video, main.py:1027-1087) ------------------------------------
+ * Replaces the host-side frame assembly of main.py:1039-1083: the np.concatenate of the tiles, (frames * 255).astype(np.uint8), the x3
+ * F.interpolate (nearest) and the concatenation with the np.tile'd title and legend bands.
+ * out [n, H, W, 3] uint8, H = h_top + 192 rows + h_bottom, W = 192 cols: rows 0..h_top-1 = top [h_top, W, 3]; then `rows` rows of
+ * `cols` cells, cell (r, c) = cells[r * cols + c] shown x3 nearest; then bottom [h_bottom, W, 3].  Frame i of the chunk shows source
+ * frame f0 + i of every cell.  A cell's source is a [>= f0 + n, 64, 64] stack (RGB8: [.., 64, 64, 3]) in device memory:
+ *   CGS_VIDEO_RGB8   uint8 RGB frames: the pixel as it is (= uint8(255 (x / 255.0)) for every byte x);
+ *   CGS_VIDEO_MASK8  uint8 0/1 mask: GREY 255 m; CODE against the truth y (uint8 0/1 [.., 64, 64]): TP (0,255,0), FN (255,0,0),
+ *                    FP (127,127,127), TN (0,0,0) -- main.py:1050-1051 after *255;
+ *   CGS_VIDEO_F32 / CGS_VIDEO_F64  fp32 / fp64 map in [0, 1]: GREY uint8(255.0 * (double)v) (truncation; outside [0, 1] clamped);
+ * mode CGS_VIDEO_CONST: every pixel uint8(255.0 * value) (src unused; 0.1 gives 25).  CODE needs MASK8.  top / bottom / out 16-byte
+ * aligned; flags: CGS_VIDEO_NONTEMPORAL = non-temporal stores.  1 <= n <= 65535, rows * cols <= CGS_VIDEO_MAX_CELLS, else
+ * CGS_ERR_BADARG.  `cells` is HOST memory (copied into the launch).                                                                       */
+enum { CGS_VIDEO_RGB8 = 0, CGS_VIDEO_MASK8 = 1, CGS_VIDEO_F32 = 2, CGS_VIDEO_F64 = 3 };
+enum { CGS_VIDEO_GREY = 0, CGS_VIDEO_CODE = 1, CGS_VIDEO_CONST = 2 };
+enum { CGS_VIDEO_MAX_CELLS = 16, CGS_VIDEO_NONTEMPORAL = 1 };
+typedef struct {
+    const void* src;
+    const uint8_t* y;      /* CODE: the truth */
+    double value;          /* CONST */
+    int32_t kind, mode;
+} cgs_video_cell;
+int cgs_video_compose(const cgs_video_cell* cells, int32_t rows, int32_t cols, int32_t f0, int32_t n, const uint8_t* top, int32_t h_top,
+                      const uint8_t* bottom, int32_t h_bottom, int32_t flags, uint8_t* out, cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
