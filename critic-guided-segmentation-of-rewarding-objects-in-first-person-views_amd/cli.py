@@ -3,6 +3,7 @@
     python main.py -train --model DIR
     python main.py -process [-concatenated] [--binarymaskthreshold t] --model DIR --source-imgs S --mask-output-imgs R
     python main.py -test --model DIR --output-video V       (evaluation sweep + the evaluation video V/iou=....mp4)
+    python main.py -train -critic '' -masker '' -vismasker --model DIR      (DIR/curves.mp4, -pred-sorted.mp4, -GT-sorted.mp4)
 
 Every flag of the reference parses (same names, defaults and the ``type=bool`` quirk: ``-cload False`` is
 still True, as in the reference); flags whose code path is outside this build raise NotImplementedError
@@ -76,8 +77,11 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
+    from . import vis
     from .handler import Handler
     args = parse_args(argv)
+    if (args.viscritic or args.vismasker) and not args.trainasvis:
+        vis.refuse_unbuilt(args)            # before any GPU work
     H = Handler(args)
     if args.train:
         H.load_data()
@@ -97,7 +101,7 @@ def main(argv=None):
     if args.eval:
         H.eval()
     if args.viscritic or args.vismasker:
-        raise NotImplementedError("-viscritic / -vismasker (videos) are outside this build's scope")
+        H.visualize()
     if args.process:
         H.segment(folder=args.source_imgs)
     return H

@@ -2,11 +2,12 @@
 (main.py:66-156, 158-236, 238-312, 314-575, 584-591, 1103-1223) with its inner loops replaced by the fused
 HIP engine.  Same method names, same checkpoint / dataset file naming, same output file names.
 
-Out of scope here: the -viscritic / -vismasker videos and the PNG debug grids.  ``collect_data`` reads an
+Out of scope here: the PNG debug grids, --trainasvis and --purevis.  ``collect_data`` reads an
 existing gz-pickle or, when the ``minerl`` package is importable, builds it from MineRL episodes exactly as the reference labels them
 (the MineRL download / decoder itself is the package's; it is absent from this image).  ``-eval`` (section 8 f2) is carried over, with
 the evaluation video of ``-test`` / ``--output-video`` (video.py: frames composed on the GPU); ``-crf`` runs the dense CRF of crf.py
-(exact mean field on the GPU) in both ``-process`` and ``-eval``.
+(exact mean field on the GPU) in both ``-process`` and ``-eval``.  ``-viscritic`` / ``-vismasker`` (main.py:702-884) write their videos
+through vis.py (frames composed on the GPU).
 """
 import gzip
 import math
@@ -16,7 +17,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, dataformat, parallel, video
+from . import _lib, dataformat, parallel, video, vis
 from .crf import dense_crf
 from .engine import HourglassEngine
 from .generic_engine import GenericEngine
@@ -442,11 +443,12 @@ class Handler:
                     Image.fromarray(to_u8(g[i])).save(f"{out_dir}/{stem}-{kind}.png")
         return M
 
-    def _sweep_masks(self, X, to_device, progress, want_saliency=False, fp16=False, batchsize=128):
+    def _sweep_masks(self, X, to_device, progress, want_saliency=False, fp16=False, batchsize=128, train_mode=None):
         """The inference loop shared by -process and -eval (main.py:1130-1151, 900-953): eval-mode critic + masker over X in batches
         of 128, optionally the saliency baseline |d mean(pred) / d batch| summed over the colour channels.
-        Returns (preds [n], masks [n,1,64,64], saliency [n,1,64,64] or None) as numpy."""
+        Returns (preds [n], masks [n,1,64,64], saliency [n,1,64,64] or None) as numpy.  train_mode: None follows -noevalmode."""
         args = self.args
+        train_mode = bool(args.noevalmode) if train_mode is None else train_mode
         self.critic.eval()
         self.masker.eval()
         eng = self._engine(2 * 32)
@@ -460,7 +462,7 @@ class Handler:
             if fp16:
                 pred, Z = eng.infer(batch, fp16=True)
             else:
-                pred, Z = eng.infer(batch, train_mode=bool(args.noevalmode))      # -noevalmode: Dropout stays on (main.py:1109-1118)
+                pred, Z = eng.infer(batch, train_mode=train_mode)                 # -noevalmode: Dropout stays on (main.py:1109-1118)
             preds.append(pred.cpu().numpy())
             masks.append(Z.cpu().numpy()[:, None])
         cat = lambda parts: np.concatenate(parts, axis=0)
@@ -564,6 +566,28 @@ class Handler:
             n = video.write_video(path, layout, {k: v for k, v in sources.items() if v is not None}, self.device, ffmpeg=exe)
             print(f"video: {path} ({n} frames of {layout.width}x{layout.height})")
         return ious
+
+    # ------------------------------------------------------------------ -viscritic / -vismasker: the value-curve videos
+    def visualize(self):
+        """main.py:702-884: the critic's value (and with -vismasker the mask) of every frame of the test split, eval mode in batches of
+        128 -- -noevalmode has no effect, the reference calls .eval() here itself -- then {path}{visname}.mp4, -pred-sorted.mp4 and,
+        with --sortidx != 0, -GT-sorted.mp4 (vis.py; rank 0 writes).  ffmpeg is looked for before the sweep.  Returns the paths."""
+        args = self.args
+        vis.refuse_unbuilt(args)
+        if not hasattr(self, "XX"):
+            raise ValueError("-viscritic / -vismasker need the test split of load_data() (self.XX): run with -train")
+        exe = video.find_ffmpeg()
+        to_device = lambda chunk: torch.from_numpy(np.ascontiguousarray(chunk)).to(self.device)
+        preds, M, _unused = self._sweep_masks(self.XX, to_device, "progress at", train_mode=False)
+        print()
+        values = np.stack((np.asarray(self.YY[args.rewidx], dtype=np.float64), preds.astype(np.float64)), axis=0)      # main.py:804
+        if self.rank != 0:
+            return []
+        paths = vis.write_videos(self.path, args.visname, args.sortidx, self.XX, M if args.vismasker else None, values, self.device,
+                                 ffmpeg=exe)
+        p = vis.plan(bool(args.vismasker))
+        print(f"videos: {', '.join(paths)} ({len(self.XX)} frames of {p.width}x{p.height})")
+        return paths
 
     # ------------------------------------------------------------------ helpers
     @staticmethod

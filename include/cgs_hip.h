@@ -776,6 +776,30 @@ typedef struct {
 int cgs_video_compose(const cgs_video_cell* cells, int32_t rows, int32_t cols, int32_t f0, int32_t n, const uint8_t* top, int32_t h_top,
                       const uint8_t* bottom, int32_t h_bottom, int32_t flags, uint8_t* out, cgs_stream_t stream);
 
+/* ---- -viscritic / -vismasker frame composition (csrc/vis.hip; Handler.visualize's make_video, main.py:818-874) ----------------------
+ * Replaces the host loop of main.py:835-870, run once per video: frames[:, sorting] (main.py:820-822), the np.concatenate of the tiles
+ * and of the plotbar windows (main.py:839-849, make_plotbar main.py:31-41), cv2.resize x4 INTER_NEAREST (main.py:852), np.uint8, the
+ * three PIL draw.text calls (main.py:856-862) and np.array(img).
+ * One launch composes frames j0 .. j0 + n - 1 of one video into out [n, H, 256, 3] uint8, H = 4 (64 R + 32 CGS_VIS_VALUES).  Frame j
+ * shows source frame p = perm[j] (perm_or_null int32 [N], the video's sorting; null = identity; entries are trusted):
+ *   tile 0: X[p] (uint8 [N,64,64,3]) as it is;  tile 1 (R = 2): uint8(float32(X[p]) * masks[p]) -- one IEEE fp32 product per byte,
+ *   truncated (main.py:811, 853); masks fp32 [N,64,64] in [0, 1];
+ *   plot strip v (32 source rows, v = 0 ground truth, 1 prediction): column c shows index k = j + c - 32 of the PERMUTED sequence; when
+ *   0 <= k < N the pixel at source row rows[v][perm[k]] (rows uint8 [CGS_VIS_VALUES, N], make_plotbar's ph - 1 - floor(ph x)) is white,
+ *   in column 32 (the current frame) red; everything else black;
+ *   every source pixel x4 nearest: out[y][x] = src[y / 4][x / 4];
+ *   labels: label_ids int32 [N, 1 + CGS_VIS_VALUES] gives source frame p its cells of atlas (uint8 [n_labels, CGS_VIS_CELL_H,
+ *   CGS_VIS_CELL_W], the coverage PIL rendered for each distinct string; an id outside [0, n_labels) draws nothing): first the index
+ *   label at (CGS_VIS_INDEX_X, H - 269), then value label v at (CGS_VIS_VALUE_X, CGS_VIS_VALUE_Y + CGS_VIS_VALUE_DY v), each blended
+ *   in that order per byte with PIL's v = dst (255 - a) + 255 a + 128; ((v >> 8) + v) >> 8, and clipped at the frame's right edge.
+ * out 16-byte aligned; flags: CGS_VIS_NONTEMPORAL = non-temporal stores.  R in {1, 2}, masks required for R = 2, 0 <= j0, 1 <= n,
+ * j0 + n <= N, else CGS_ERR_BADARG (nothing is launched).                                                                            */
+enum { CGS_VIS_VALUES = 2, CGS_VIS_CELL_W = 64, CGS_VIS_CELL_H = 16, CGS_VIS_NONTEMPORAL = 1 };
+enum { CGS_VIS_INDEX_X = 230, CGS_VIS_VALUE_X = 1, CGS_VIS_VALUE_Y = 1, CGS_VIS_VALUE_DY = 15 };
+int cgs_vis_compose(const uint8_t* X, const float* masks_or_null, const int32_t* perm_or_null, const uint8_t* rows,
+                    const int32_t* label_ids, const uint8_t* atlas, int32_t n_labels, int32_t N, int32_t R, int32_t j0, int32_t n,
+                    int32_t flags, uint8_t* out, cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
