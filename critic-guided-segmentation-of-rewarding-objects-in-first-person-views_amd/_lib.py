@@ -60,6 +60,7 @@ VIDEO_GREY, VIDEO_CODE, VIDEO_CONST = 0, 1, 2
 VIDEO_MAX_CELLS, VIDEO_NONTEMPORAL = 16, 1
 VIS_VALUES, VIS_CELL_W, VIS_CELL_H, VIS_NONTEMPORAL = 2, 64, 16, 1              # cgs_vis_compose (include/cgs_hip.h)
 VIS_INDEX_X, VIS_VALUE_X, VIS_VALUE_Y, VIS_VALUE_DY = 230, 1, 1, 15
+SHEET_ROWS, SHEET_MAX_N = 7, 1 << 20                                            # cgs_sheet_compose (include/cgs_hip.h)
 
 
 class ReduceJob(C.Structure):
@@ -204,6 +205,7 @@ SIGNATURES = {
     "cgs_dense_crf2": (i32, [vp, vp, i32, i32, i32, C.POINTER(CrfParams), vp, vp, vp]),
     "cgs_video_compose": (i32, [C.POINTER(VideoCell), i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp]),
     "cgs_vis_compose": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "cgs_sheet_compose": (i32, [vp, vp, vp, i32, vp, vp]),
     "cgs_build_arch": (C.c_char_p, []),
     "cgs_abi_version": (i32, []),
 }

@@ -345,6 +345,25 @@ class HourglassEngine:
         self._pver[0] += 1
         return self.losses
 
+    def last_phase2_views(self):
+        """(A, B, Z, pred, negpred, replacevalue, injectvalue) of the last phase-2 step as VIEWS of the step's buffers (no copy, no
+        launch): A, B uint8 [n,64,64,3], Z fp32 [n,64,64], the four critic values fp32 [n] -- pred = critic(A), negpred = critic(B),
+        then the values of the two mixes; injectvalue is None without inject.  They come from the forward with the weights BEFORE the
+        update, which is what the reference draws (its sheet uses Z from before opti.step(), main.py:461-474), and hold until the next
+        gather_contrastive / phase2_step on the stream: whoever reads them enqueues the read before that."""
+        n = self.n
+        if not hasattr(self, "ab") or "Z" not in self.mbuf:
+            raise _lib.CgsError("last_phase2_views: no phase-2 step has run on this engine")
+        pred = self.cbuf["pred"].reshape(-1)             # slots [B | A | replaced | injected], in the order the forward fills them
+        return (self.ab[n:], self.ab[:n], self.mbuf["Z"], pred[n:2 * n], pred[:n], pred[2 * n:3 * n],
+                pred[3 * n:4 * n] if self.inject else None)
+
+    def last_phase1_pred(self):
+        """The critic's values of the last phase-1 batch (a view, fp32 [n]): the forward with the weights before the update."""
+        if not hasattr(self, "cbuf"):
+            raise _lib.CgsError("last_phase1_pred: no phase-1 step has run on this engine")
+        return self.cbuf["pred"].reshape(-1)[:self.n]
+
     def gather_contrastive(self, Xpos: torch.Tensor, Xneg: torch.Tensor, ypos: torch.Tensor, yneg: torch.Tensor,
                            idx: torch.Tensor, shift_px: int = 0):
         """Assembles the resident batch of a phase-2 step on the device (main.py:344-356): A = [Xpos[idx[:h]] | Xneg[idx[h:n]]]

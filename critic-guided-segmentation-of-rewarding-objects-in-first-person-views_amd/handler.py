@@ -2,7 +2,9 @@
 (main.py:66-156, 158-236, 238-312, 314-575, 584-591, 1103-1223) with its inner loops replaced by the fused
 HIP engine.  Same method names, same checkpoint / dataset file naming, same output file names.
 
-Out of scope here: the PNG debug grids, --trainasvis and --purevis.  ``collect_data`` reads an
+Out of scope here: --trainasvis and --purevis.  The PNG sheets of the two training loops (main.py:203-226,
+465-530) and the two histograms of the contrastive split (main.py:255-264) are written through sheets.py: the segment sheet's pixels
+are composed on the GPU and every PNG is encoded by a writer thread, off the step path.  ``collect_data`` reads an
 existing gz-pickle or, when the ``minerl`` package is importable, builds it from MineRL episodes exactly as the reference labels them
 (the MineRL download / decoder itself is the package's; it is absent from this image).  ``-eval`` (section 8 f2) is carried over, with
 the evaluation video of ``-test`` / ``--output-video`` (video.py: frames composed on the GPU); ``-crf`` runs the dense CRF of crf.py
@@ -17,7 +19,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, dataformat, parallel, video, vis
+from . import _lib, dataformat, parallel, sheets, video, vis
 from .crf import dense_crf
 from .engine import HourglassEngine
 from .generic_engine import GenericEngine
@@ -238,23 +240,32 @@ class Handler:
             self.eval()
             if args.noevalmode:
                 self.critic.train()
-        for epoch in range(int(mode == "test") or args.cepochs):
-            for b_idx, (X, Y, idx) in enumerate(self._batches()):
-                if args.shift:
-                    X = self.shift_batch(X)
-                eng = self._engine(len(X), dropout=self._p1_dropout)
-                losses = eng.phase1_step(X.contiguous().to(self.device, non_blocking=True), Y.to(self.device, non_blocking=True))
-                if self._trace is not None:      # (tests: the loop-level pin G9) no host sync: device clones
-                    self._trace["p1_idx"].append(idx.copy())
-                    self._trace["p1_loss"].append(losses[:1].clone())
-                if not b_idx % 10:
-                    val = float(losses[0])       # the only host sync, every 10th batch
-                    llog.append(val)
-                    print(f"critic e{epoch + 1} b{b_idx}", val, end="\r")
-            if not (epoch + 1) % args.saveevery:
-                self.save_models(modelnames=[self.criticname])
-            if self.rank == 0:                    # (data parallel: one writer)
-                self._plot(result_path + "_loss.png", {"Train Loss": llog})
+        # critic/e{epoch}_b{b}.png every 100th batch (main.py:203-226), rank 0's shard: encoded by the writer thread
+        writer = sheets.SheetWriter() if self.rank == 0 else None
+        try:
+            for epoch in range(int(mode == "test") or args.cepochs):
+                for b_idx, (X, Y, idx) in enumerate(self._batches()):
+                    if args.shift:
+                        X = self.shift_batch(X)
+                    eng = self._engine(len(X), dropout=self._p1_dropout)
+                    losses = eng.phase1_step(X.contiguous().to(self.device, non_blocking=True), Y.to(self.device, non_blocking=True))
+                    if writer is not None and not b_idx % sheets.CRITIC_EVERY:
+                        # the prediction is the forward's, before the update (as the reference's); its copy is enqueued before the next step
+                        writer.submit_critic(sheets.segment_path(result_path, epoch, b_idx), X, Y, eng.last_phase1_pred())
+                    if self._trace is not None:      # (tests: the loop-level pin G9) no host sync: device clones
+                        self._trace["p1_idx"].append(idx.copy())
+                        self._trace["p1_loss"].append(losses[:1].clone())
+                    if not b_idx % 10:
+                        val = float(losses[0])       # the only host sync, every 10th batch
+                        llog.append(val)
+                        print(f"critic e{epoch + 1} b{b_idx}", val, end="\r")
+                if not (epoch + 1) % args.saveevery:
+                    self.save_models(modelnames=[self.criticname])
+                if self.rank == 0:                    # (data parallel: one writer)
+                    self._plot(result_path + "_loss.png", {"Train Loss": llog})
+        finally:
+            if writer is not None:
+                writer.close()
         print()
 
     # ------------------------------------------------------------------ contrastive split
@@ -285,8 +296,12 @@ class Handler:
         args = self.args
         self.critic.eval()
         eng = self._engine(2 * 32)
+        os.makedirs(self.path, exist_ok=True)
         if args.critic or args.cload:
             preds = self._sweep_preds(eng, self.X)
+            if self.rank == 0:                    # main.py:255-264: the two histograms of the split
+                self._hist(self.path + f"pred_idx{args.rewidx}_hist.png", preds.numpy())
+                self._hist(self.path + f"GT_idx{args.rewidx}_hist.png", self.Y[args.rewidx])
             positives, negatives = preds > args.high_rew_thresh, preds < args.low_rew_thresh
         else:
             print("no critic provided -> using random pos and neg frames")
@@ -298,7 +313,6 @@ class Handler:
             negatives = ~positives
             preds = torch.cat((positives, negatives), dim=0)
         npos, nneg = int(positives.sum()), int(negatives.sum())
-        os.makedirs(self.path, exist_ok=True)
         if self.rank == 0:      # the reference leaves the two counts behind as an (empty) file name
             open(self.path + f"{npos}>{args.high_rew_thresh}__{nneg}<{args.low_rew_thresh}.txt", "w").close()
         assert npos >= 500 and nneg >= 500
@@ -319,9 +333,11 @@ class Handler:
 
     # ------------------------------------------------------------------ phase 2: mask training
     def segmentation_training(self):
-        """main.py:314-575 without the debug image grids: per step three index draws (numpy RNG, as the reference), the two
-        shift draws (torch RNG), ONE 128-entry index upload; the frames are gathered, rolled and trained on without leaving
-        the device."""
+        """main.py:314-575: per step three index draws (numpy RNG, as the reference), the two shift draws (torch RNG), ONE 128-entry
+        index upload; the frames are gathered, rolled and trained on without leaving the device.  Every --visevery steps rank 0
+        leaves segment/e{epoch}_b{b}.png (main.py:465-530) behind: composed on the GPU from the step's own tensors right after the
+        step, copied out asynchronously and encoded by a writer thread (sheets.py) -- no host sync, no RNG draw.  --visevery 0
+        writes none (this build's own meaning of 0: the reference divides by zero there)."""
         import time
         args = self.args
         self._refuse_unbuilt_flags()
@@ -353,47 +369,66 @@ class Handler:
         self._last_idx_draws = []                # (debug / tests) the host draws of the last few steps, in order
         names = ["replace", "inject", "norm", "live-critic"]
         steps, steps_t0, t0, dt = 0, 0, time.perf_counter(), 0.0
-        for epoch in range(args.mepochs):
-            for b_idx in range(math.ceil(self.Xpos.shape[0] / self.contrastive_batchsize)):
-                Hidx, Lidx, Cidx = self.get_contrastive_idxs()
-                slot = steps % ring
-                if idx_events[slot] is not None:
-                    idx_events[slot].synchronize()                   # the upload that last used this buffer has finished
-                idx_host = idx_hosts[slot]
-                idx_host.copy_(torch.from_numpy(np.concatenate((Hidx, Lidx, Cidx))))
-                idx_dev.copy_(idx_host, non_blocking=True)
-                idx_events[slot] = torch.cuda.Event()
-                idx_events[slot].record()
-                if getattr(self, "_record_idx_draws", False):
-                    self._last_idx_draws.append(idx_host.clone())
-                roll = self._shift_draw() if args.shift else 0      # torch.roll(X, roll, dims=2): dst[x] = src[x - roll]
-                eng.gather_contrastive(self._Xpos_d, self._Xneg_d, self._ypos_d, self._yneg_d, idx_dev, shift_px=(-roll) % 64)
-                losses = eng.phase2_step()
-                steps += 1
-                if self._trace is not None:      # (tests: the loop-level pin G9)
-                    self._trace["p2_idx"].append(np.concatenate((Hidx, Lidx, Cidx)))
-                    self._trace["p2_roll"].append(roll)
-                    self._trace["p2_loss"].append(losses[:6].clone())
-                if steps == 20:                                      # throughput is reported for the steady state (after the
-                    torch.cuda.synchronize()                         # eager first step and the graph capture)
-                    t0, steps_t0, dt = time.perf_counter(), steps, 0.0
-                if not b_idx % 10:                                   # the only host sync
-                    c, r, i, l1, l2, total = losses[:6].tolist()
-                    log.append((r, i if args.inject else 0, l1 + l2, c if args.live else 0))
-                    msg = f"e{epoch} b{b_idx}" + (f"    live-critic {c}" if args.live else "") + f"   replace: {r}"
-                    msg += (f"   inject: {i}" if args.inject else "") + (f"   L1: {l1}" if args.L1 else "") + (f"   L2: {l2}" if args.L2 else "")
-                    print(msg, end="\r")
-            torch.cuda.synchronize()
-            dt += time.perf_counter() - t0            # (plots and checkpoints are not part of the step throughput)
-            if self.rank == 0:
-                llog = np.array(log)
-                self._plot(train_path + "_loss.png", {nm: llog[:, k] for k, nm in enumerate(names)})
-            if not (epoch + 1) % args.saveevery:
-                self.save_models(modelnames=[self.maskername])
-            t0 = time.perf_counter()
+        writer = sheets.SheetWriter() if (self.rank == 0 and args.visevery > 0) else None
+        drain = 0.0
+        try:
+            for epoch in range(args.mepochs):
+                for b_idx in range(math.ceil(self.Xpos.shape[0] / self.contrastive_batchsize)):
+                    Hidx, Lidx, Cidx = self.get_contrastive_idxs()
+                    slot = steps % ring
+                    if idx_events[slot] is not None:
+                        idx_events[slot].synchronize()                   # the upload that last used this buffer has finished
+                    idx_host = idx_hosts[slot]
+                    idx_host.copy_(torch.from_numpy(np.concatenate((Hidx, Lidx, Cidx))))
+                    idx_dev.copy_(idx_host, non_blocking=True)
+                    idx_events[slot] = torch.cuda.Event()
+                    idx_events[slot].record()
+                    if getattr(self, "_record_idx_draws", False):
+                        self._last_idx_draws.append(idx_host.clone())
+                    roll = self._shift_draw() if args.shift else 0      # torch.roll(X, roll, dims=2): dst[x] = src[x - roll]
+                    eng.gather_contrastive(self._Xpos_d, self._Xneg_d, self._ypos_d, self._yneg_d, idx_dev, shift_px=(-roll) % 64)
+                    losses = eng.phase2_step()
+                    steps += 1
+                    if writer is not None and sheets.wanted(args.visevery, b_idx):
+                        # views of the step's own buffers (forward with the pre-update weights, as the reference draws); the compose
+                        # and the copies are enqueued here, before the next gather_contrastive: stream order protects them
+                        A, B, Z, *values = eng.last_phase2_views()
+                        y_host = np.concatenate((self.Ypos[args.rewidx, Hidx], self.Yneg[args.rewidx, Lidx]))      # float64, as main.py:346-351
+                        writer.submit_segment(sheets.segment_path(train_path, epoch, b_idx), A, B, Z, y_host, values, args.inject)
+                    if self._trace is not None:      # (tests: the loop-level pin G9)
+                        self._trace["p2_idx"].append(np.concatenate((Hidx, Lidx, Cidx)))
+                        self._trace["p2_roll"].append(roll)
+                        self._trace["p2_loss"].append(losses[:6].clone())
+                    if steps == 20:                                      # throughput is reported for the steady state (after the
+                        torch.cuda.synchronize()                         # eager first step and the graph capture)
+                        t0, steps_t0, dt = time.perf_counter(), steps, 0.0
+                    if not b_idx % 10:                                   # the only host sync
+                        c, r, i, l1, l2, total = losses[:6].tolist()
+                        log.append((r, i if args.inject else 0, l1 + l2, c if args.live else 0))
+                        msg = f"e{epoch} b{b_idx}" + (f"    live-critic {c}" if args.live else "") + f"   replace: {r}"
+                        msg += (f"   inject: {i}" if args.inject else "") + (f"   L1: {l1}" if args.L1 else "") + (f"   L2: {l2}" if args.L2 else "")
+                        print(msg, end="\r")
+                torch.cuda.synchronize()
+                dt += time.perf_counter() - t0            # (plots and checkpoints are not part of the step throughput)
+                if self.rank == 0:
+                    llog = np.array(log)
+                    self._plot(train_path + "_loss.png", {nm: llog[:, k] for k, nm in enumerate(names)})
+                if not (epoch + 1) % args.saveevery:
+                    self.save_models(modelnames=[self.maskername])
+                t0 = time.perf_counter()
+        finally:
+            if writer is not None:           # the ring drains outside the timed region, like the plots and checkpoints
+                t_close = time.perf_counter()
+                writer.close()
+                drain = time.perf_counter() - t_close
         self.train_images_per_s = (steps - steps_t0) * n * self.world / dt if dt > 0 else 0.0
         print(f"\nmask training: {steps} steps of {n} A-images, {steps - steps_t0} of them in {dt:.3f} s = {self.train_images_per_s:.0f} images/s"
               + (f" over {self.world} ranks" if self.world > 1 else ""))
+        if writer is not None:
+            k = len(writer.written)
+            print(f"sheets: {k} written to {train_path}, {writer.encode_s / max(k, 1) * 1e3:.1f} ms of the writer thread per sheet; "
+                  f"drain at close {drain * 1e3:.1f} ms (not part of the throughput)")
+        self.sheet_drain_s = drain
         self.save_models(modelnames=[self.maskername])
 
     # ------------------------------------------------------------------ -process: masks for a folder of images
@@ -607,4 +642,18 @@ class Handler:
             avg = np.convolve(vals, np.ones(k) / k, mode="valid")
             plt.plot(avg, label=name)
         plt.legend()
+        plt.savefig(path)
+
+    @staticmethod
+    def _hist(path, values):
+        """plt.clf(); plt.hist(values); plt.savefig(path) of main.py:257-264."""
+        try:
+            import matplotlib
+            matplotlib.use("Agg")
+            from matplotlib import pyplot as plt
+        except Exception:
+            return
+        plt.clf()
+        plt.hist(np.asarray(values))
+        print("saving histogramm", path)
         plt.savefig(path)

@@ -800,6 +800,18 @@ int cgs_vis_compose(const uint8_t* X, const float* masks_or_null, const int32_t*
                     const int32_t* label_ids, const uint8_t* atlas, int32_t n_labels, int32_t N, int32_t R, int32_t j0, int32_t n,
                     int32_t flags, uint8_t* out, cgs_stream_t stream);
 
+/* ---- mask-training PNG sheet (csrc/sheet.hip; Handler.segmentation_training's debug grid, main.py:465-496) -----------------------------
+ * Replaces the host-side pixels of main.py:470-496: A / B / Z pulled to the host and permuted, the two mixes recomputed in torch on the
+ * CPU, seven np.concatenate(viz, axis=1) rows (two of zeros), np.concatenate(vizs, axis=0) and np.uint8(255 * viz).  The text of
+ * main.py:497-515 is NOT blended here: it is drawn on the host into the two zero rows (cgs_amd/sheets.py), off the step path.
+ * A, B uint8 NHWC [n,64,64,3], Z fp32 [n,64,64] in [0, 1]; out uint8 [7 * 64, 64 n, 3] row-major, image i in columns 64 i .. 64 i + 63.
+ * Rows of tiles, top to bottom: zeros, zeros, A, B, replaced = A (1 - Z) + Z B, injected = B (1 - Z) + Z A, Z on all three channels.
+ * Every byte is np.uint8(255 * v) with v in fp32: a = float(u8) / 255.0f (a true division), then 1 - Z, both products, the sum and the
+ * 255 * each rounded on its own in that operand order (no FMA), then truncated; for the A and B rows that gives back the frame's byte.
+ * A, B, out 16-byte aligned; 1 <= n <= CGS_SHEET_MAX_N, else CGS_ERR_BADARG (nothing is launched).                                     */
+enum { CGS_SHEET_ROWS = 7, CGS_SHEET_MAX_N = 1 << 20 };
+int cgs_sheet_compose(const uint8_t* A, const uint8_t* B, const float* Z, int32_t n, uint8_t* out, cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
