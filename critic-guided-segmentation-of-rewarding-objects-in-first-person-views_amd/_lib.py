@@ -206,6 +206,8 @@ SIGNATURES = {
     "cgs_video_compose": (i32, [C.POINTER(VideoCell), i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp]),
     "cgs_vis_compose": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "cgs_sheet_compose": (i32, [vp, vp, vp, i32, vp, vp]),
+    "cgs_iou_curve": (i32, [vp, vp, vp, i32, i32, i64, vp, vp]),
+    "cgs_iou_counts": (i32, [vp, vp, i32, i64, vp, vp]),
     "cgs_build_arch": (C.c_char_p, []),
     "cgs_abi_version": (i32, []),
 }

@@ -20,6 +20,11 @@ def build_parser():
         p.add_argument(flag, action="store_true")
     # (this build's own switch, not a flag of the reference) -process / -eval with fp16 activations and weights, fp32 accumulation
     p.add_argument("-fp16", action="store_true")
+    # (this build's own flags) -eval sweeps, scored on the GPU (metrics.py): --thresh-grid "0.01-0.05-0.5" or "lo:hi:n" scores the masks
+    # at every threshold (the grid main.py:974 left commented out); --crf-grid "w1=5,22;it=2,10" makes -crf the parameter grid search
+    # main.py:1226-1263 is written as.  Both leave {model}/eval_sweep.json
+    p.add_argument("--thresh-grid", type=str, default="")
+    p.add_argument("--crf-grid", type=str, default="")
     for flag in ("-masker", "-critic", "-cload", "-mload", "-staticnorm", "-visbesteval", "-salglobal"):
         p.add_argument(flag, type=bool, default=True)
     p.add_argument("--salience-thresh", type=float, default="1.5")
@@ -73,7 +78,24 @@ def parse_args(argv=None):
         args.visbesteval = True
         args.crf = False
         args.salience = True
+    check_sweep_flags(args)
     return args
+
+
+def check_sweep_flags(args):
+    """--thresh-grid / --crf-grid: malformed grids and combinations that could not run are refused here, before any GPU work."""
+    if args.thresh_grid:
+        from .metrics import parse_thresh_grid
+        parse_thresh_grid(args.thresh_grid)
+        if not args.eval:
+            raise ValueError("--thresh-grid sweeps the threshold of -eval: give -eval (or -test)")
+    if args.crf_grid:
+        from .crf import parse_crf_grid
+        parse_crf_grid(args.crf_grid)
+        if args.process:
+            raise ValueError("--crf-grid scores every point against the labels of -eval; -process has none")
+        if not (args.crf and args.eval):
+            raise ValueError("--crf-grid is the parameter grid of -eval -crf: give both (-test switches -crf off)")
 
 
 def main(argv=None):

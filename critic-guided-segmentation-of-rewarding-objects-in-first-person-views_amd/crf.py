@@ -9,6 +9,49 @@ from . import _lib
 
 # (w_bilateral, alpha, beta, w_gaussian, gamma, iterations): the one-point grid of Handler.crf (main.py:1230-1235)
 REFERENCE_PARAMS = (22, 12, 3.1, 8, 1.8, 10)
+# the names of the reference's six lists (main.py:1230-1235), in the nesting order of its product (main.py:1238): w1 outermost
+GRID_KEYS = ("w1", "alpha", "beta", "w2", "gamma", "it")
+
+
+def parse_crf_grid(s):
+    """``--crf-grid "w1=5,22;alpha=12;it=2,10"`` -> {key: [values]} over all six GRID_KEYS; a key not given keeps its one
+    REFERENCE_PARAMS value.  `it` takes integers >= 0, the stds (alpha, beta, gamma) positive numbers.  An empty string is the
+    reference's one-point grid."""
+    grid = {k: [v] for k, v in zip(GRID_KEYS, REFERENCE_PARAMS)}
+    seen = set()
+    for item in filter(None, (part.strip() for part in str(s).split(";"))):
+        key, eq, vals = item.partition("=")
+        key = key.strip()
+        if not eq or key not in GRID_KEYS:
+            raise ValueError(f"--crf-grid {item!r}: expected KEY=v1,v2,... with KEY one of {', '.join(GRID_KEYS)}")
+        if key in seen:
+            raise ValueError(f"--crf-grid: {key} is given twice")
+        seen.add(key)
+        out = []
+        for tok in vals.split(","):
+            tok = tok.strip()
+            try:
+                v = int(tok)
+            except ValueError:
+                try:
+                    v = float(tok)
+                except ValueError:
+                    raise ValueError(f"--crf-grid {item!r}: {tok!r} is not a number") from None
+                if key == "it":
+                    raise ValueError(f"--crf-grid {item!r}: it takes whole numbers") from None
+            if v != v or v in (float("inf"), float("-inf")):
+                raise ValueError(f"--crf-grid {item!r}: {tok!r} is not finite")
+            if (key == "it" and v < 0) or (key in ("alpha", "beta", "gamma") and v <= 0):
+                raise ValueError(f"--crf-grid {item!r}: {key} must be {'>= 0' if key == 'it' else 'positive'}")
+            out.append(v)
+        grid[key] = out
+    return grid
+
+
+def grid_points(grid):
+    """The points of a parse_crf_grid() dict in the reference's product order (main.py:1238): w1 outermost, `it` innermost."""
+    w1, alpha, beta, w2, gamma, it = (grid[k] for k in GRID_KEYS)
+    return [(a, b, c, d, e, i) for a in w1 for b in alpha for c in beta for d in w2 for e in gamma for i in it]
 
 
 def dense_crf(frames_u8, prob1, params=REFERENCE_PARAMS, return_q=False):

@@ -12,6 +12,7 @@ the evaluation video of ``-test`` / ``--output-video`` (video.py: frames compose
 through vis.py (frames composed on the GPU).
 """
 import gzip
+import json
 import math
 import os
 import pickle
@@ -19,8 +20,8 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, dataformat, parallel, sheets, video, vis
-from .crf import dense_crf
+from . import _lib, dataformat, metrics, parallel, sheets, video, vis
+from .crf import GRID_KEYS, dense_crf, grid_points, parse_crf_grid
 from .engine import HourglassEngine
 from .generic_engine import GenericEngine
 from .nets import NewCritic, UnetDecoder
@@ -39,6 +40,15 @@ def checkpoint_names(args):
                            ["rewidx", "cepochs", "datamode", "datasize", "threshrew", "shift", "chfak", "dropout"] if d[a])
     masker_args = "-".join(f"{a}={d[a]}" for a in ["mepochs", "L1", "L2", "inject"] if d[a])
     return critic_args, masker_args
+
+
+def _json_safe(obj):
+    """NaN (an empty union or denominator) has no JSON spelling: it is written as null."""
+    if isinstance(obj, dict):
+        return {k: _json_safe(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return [_json_safe(v) for v in obj]
+    return None if isinstance(obj, float) and math.isnan(obj) else obj
 
 
 class Handler:
@@ -65,6 +75,7 @@ class Handler:
         self.save_paths = {name: f"{self.save_path}{name}-{tag}.pt"
                            for name, tag in ((self.criticname, self.critic_args), (self.maskername, self.masker_args))}
         self._engines = {}
+        self.crf_reports, self.sweep = [], None      # --crf-grid / --thresh-grid: the tables of Handler.crf, the dict of eval_sweep.json
         self._trace = None          # tests set a dict of lists (Handler.start_trace): per-step indices / losses of the two training loops
 
     def start_trace(self):
@@ -518,17 +529,38 @@ class Handler:
 
     # ------------------------------------------------------------------ -crf: dense-CRF refinement of mask stacks
     def crf(self, imgs, mask, Y, skip=1):
-        """main.py:1226-1263: every `skip`-th frame's mask [n,1,h,w] (P of label 1) refined by the two-label dense CRF at the reference's
-        parameters (crf.REFERENCE_PARAMS), the whole stack in one GPU call; the other frames keep their mask.  Returns (mask >= 1) as
-        NCHW bool.  imgs: NHWC uint8, or float in [0,1] (then (255 * img).astype(uint8) as the reference, which gives back the uint8 frame).
-        Like the reference, every 50th refined frame leaves {path}crf/{i}_mask.png, {i}_img.png, {i}_crf.png (rank 0).  Y (the labels the
-        reference's parameter grid is scored with) is not used: the grid has one point."""
+        """main.py:1226-1263: every `skip`-th frame's mask [n,1,h,w] (P of label 1) refined by the two-label dense CRF, the whole stack in
+        one GPU call per grid point; the other frames keep their mask.  Returns (mask >= 1) as NCHW bool.  imgs: NHWC uint8, or float in
+        [0,1] (then (255 * img).astype(uint8) as the reference, which gives back the uint8 frame).  Like the reference, every 50th refined
+        frame leaves {path}crf/{i}_mask.png, {i}_img.png, {i}_crf.png (rank 0).
+        The grid is --crf-grid's (crf.parse_crf_grid), by default the reference's one point (crf.REFERENCE_PARAMS); then Y is not used.
+        With --crf-grid the frames, the probabilities and Y[::skip] are uploaded once, every point's labels are scored on the GPU against
+        Y[::skip] with the reference's sum(Y & M) / sum(Y | M) (metrics.iou_counts), the table goes to self.crf_reports, and the labels
+        of the BEST point come back (ties: the first in grid order; an empty union ranks last) -- the reference computes the ranking
+        and then returns the labels of the LAST point.  A grid of several points needs Y."""
+        grid = getattr(self.args, "crf_grid", "")
+        points = grid_points(parse_crf_grid(grid))
+        if len(points) > 1 and Y is None:
+            raise ValueError("a CRF grid of more than one point is scored against the labels Y, and there are none (-process)")
         mask = np.array(mask, copy=True)
         imgs = np.asarray(imgs)[::skip]
         frames = imgs if imgs.dtype == np.uint8 else (255 * imgs).astype(np.uint8)
         prob = np.ascontiguousarray(mask[::skip, 0], dtype=np.float32)
-        labels = dense_crf(torch.from_numpy(np.ascontiguousarray(frames)).to(self.device),
-                           torch.from_numpy(prob).to(self.device)).cpu().numpy()
+        dev_frames, dev_prob = torch.from_numpy(np.ascontiguousarray(frames)).to(self.device), torch.from_numpy(prob).to(self.device)
+        if grid and Y is not None:
+            truth = torch.from_numpy(np.ascontiguousarray(np.asarray(Y)[::skip], dtype=bool)).to(self.device)
+            rows, best = [], None
+            for point in points:
+                dev_labels = dense_crf(dev_frames, dev_prob, point)
+                inter, union = metrics.iou_counts(dev_labels, truth).tolist()
+                rows.append({"params": dict(zip(GRID_KEYS, point)), "inter": inter, "union": union, "iou": metrics.ratio(inter, union)})
+                if metrics.best_index([r["iou"] for r in rows]) == len(rows) - 1:
+                    best = dev_labels                                  # the only labels kept on the device, and the only ones copied back
+            b = metrics.best_index([r["iou"] for r in rows])
+            self.crf_reports.append({"rows": rows, "best": {"index": b, "params": rows[b]["params"], "iou": rows[b]["iou"]}})
+            labels = best.cpu().numpy()
+        else:
+            labels = dense_crf(dev_frames, dev_prob, points[0]).cpu().numpy()
         if self.rank == 0:
             self._crf_debug_pngs(imgs, prob, labels)
         mask[::skip, 0] = labels
@@ -582,6 +614,15 @@ class Handler:
         preds, M, sal = self._sweep_masks(frames, to_device, "eval at", want_saliency=want_sal)
         hard_m = M[:, 0] > args.eval_thresh
         ious = [self.get_iou(hard_m, truth)]
+        thresh_grid, crf_grid = getattr(args, "thresh_grid", ""), getattr(args, "crf_grid", "")
+        sweep, n_reports = {}, len(self.crf_reports)
+        if thresh_grid:       # (this build's flag) the mask threshold only: the saliency threshold is also _saliency_post's normaliser
+            thr = metrics.parse_thresh_grid(thresh_grid)
+            inter, union = metrics.iou_curve(torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device),
+                                             torch.from_numpy(np.ascontiguousarray(truth)).to(self.device), thr)    # strict >, main.py:964
+            sweep["thresholds"] = metrics.curve_report(thr, inter.cpu().numpy(), union.cpu().numpy(), np.count_nonzero(truth))
+            b = sweep["thresholds"]["best"]
+            print(f"\nTHRESH SWEEP {len(thr)} thresholds, best {b['thresh']:.6g} (index {b['index']}) iou {b['iou']:.6f}")
         crf_m = maps = sal_hard = sal_crf = None
         if args.crf:                                                      # main.py:969-972
             crf_m = self.crf(frames, M, truth)[:, 0]
@@ -592,6 +633,16 @@ class Handler:
             if args.crf:                                                  # main.py:1000-1003
                 sal_crf = self.crf(frames, maps, truth)[:, 0]
                 ious.append(self.get_iou(sal_crf, truth))
+        if crf_grid and args.crf:
+            sweep["crf"] = dict(zip(("mask", "saliency"), self.crf_reports[n_reports:]))
+            print("\nCRF GRID " + "; ".join(f"{k}: {len(r['rows'])} points, best {r['best']['params']} iou {r['best']['iou']:.6f}"
+                                            for k, r in sweep["crf"].items()))
+        if sweep:
+            self.sweep = sweep
+            if self.rank == 0:
+                os.makedirs(self.path, exist_ok=True)
+                with open(self.path + "eval_sweep.json", "w") as fp:
+                    json.dump(_json_safe(sweep), fp, indent=1)
         print("\nRESULTS", ious)
         if vid is not None and self.rank == 0 and ious[0] > self.ious[0]:          # main.py:1027
             layout, exe = vid

@@ -812,6 +812,26 @@ int cgs_vis_compose(const uint8_t* X, const float* masks_or_null, const int32_t*
 enum { CGS_SHEET_ROWS = 7, CGS_SHEET_MAX_N = 1 << 20 };
 int cgs_sheet_compose(const uint8_t* A, const uint8_t* B, const float* Z, int32_t n, uint8_t* out, cgs_stream_t stream);
 
+/* ---- evaluation scoring (csrc/metrics.hip; Handler.get_iou main.py:1265-1270, the CRF grid's score main.py:1253, the commented
+ * threshold grid of main.py:974-975) ---------------------------------------------------------------------------------------------------
+ * Integer counts of intersection and union over a whole stack, taken where the data is: only 2 T (2 K) integers go back to the host.
+ * Both run on `stream` without synchronising and can be captured in a graph; counts is written (not accumulated into).
+ *
+ * cgs_iou_curve: v fp32 [px], truth uint8 [px] (non-zero = set), thr fp32 [T] in DEVICE memory, ascending (duplicates allowed),
+ * counts int64 [T][2]: counts[t] = (#{truth and on_t}, #{truth or on_t}) with on_t = v > thr[t] (inclusive = 0) or v >= thr[t]
+ * (inclusive = 1), compared in fp32 as numpy compares a float32 array with a float32 scalar; a NaN in v is on for no threshold.
+ * One pass over v and truth however large T is (two (T+1)-bin histograms of #{t : thr[t] < v}, then suffix sums).  Thresholds that
+ * are not ascending give unspecified counts (no fault).  1 <= T <= 1024, px >= 1, inclusive in {0, 1}, v / thr 4-byte and counts
+ * 8-byte aligned, else CGS_ERR_BADARG.  Like cgs_dense_crf2 it allocates its scratch (2 (T + 1) 64-bit bins) stream-ordered.
+ *
+ * cgs_iou_counts: labels uint8 [K][px] (non-zero = on), truth uint8 [px], counts int64 [K][2] = (#{truth and labels_k},
+ * #{truth or labels_k}): K stacks scored against one truth in one launch.  K >= 1, px >= 1, counts 8-byte aligned, else
+ * CGS_ERR_BADARG; CGS_ERR_UNSUPPORTED when K times the workgroups per stack (at most 1024 below 2^41 pixels) exceeds 2^31 - 1.
+ * Neither needs px to be a multiple of anything, nor 16-byte aligned pointers.                                                        */
+int cgs_iou_curve(const float* v, const uint8_t* truth, const float* thr, int32_t T, int32_t inclusive, int64_t px, int64_t* counts,
+                  cgs_stream_t stream);
+int cgs_iou_counts(const uint8_t* labels, const uint8_t* truth, int32_t K, int64_t px, int64_t* counts, cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
