@@ -25,6 +25,12 @@ def build_parser():
     # main.py:1226-1263 is written as.  Both leave {model}/eval_sweep.json
     p.add_argument("--thresh-grid", type=str, default="")
     p.add_argument("--crf-grid", type=str, default="")
+    # (this build's own flags) -objects: the masks of -process / -eval labelled into connected components on the GPU (objects.py),
+    # components below --min-area pixels removed.  -process leaves objects.json and {stem}-objects-mask.png, -eval eval_objects.json.
+    # The two options default to 1 and 8 (filled in by check_objects_flags, which has to see whether they were given)
+    p.add_argument("-objects", action="store_true")
+    p.add_argument("--min-area", type=int, default=None)
+    p.add_argument("--connectivity", type=int, default=None)
     for flag in ("-masker", "-critic", "-cload", "-mload", "-staticnorm", "-visbesteval", "-salglobal"):
         p.add_argument(flag, type=bool, default=True)
     p.add_argument("--salience-thresh", type=float, default="1.5")
@@ -79,6 +85,7 @@ def parse_args(argv=None):
         args.crf = False
         args.salience = True
     check_sweep_flags(args)
+    check_objects_flags(args)
     return args
 
 
@@ -96,6 +103,26 @@ def check_sweep_flags(args):
             raise ValueError("--crf-grid scores every point against the labels of -eval; -process has none")
         if not (args.crf and args.eval):
             raise ValueError("--crf-grid is the parameter grid of -eval -crf: give both (-test switches -crf off)")
+
+
+def check_objects_flags(args):
+    """-objects / --min-area / --connectivity: combinations that could not run are refused here, before any GPU work; the defaults
+    (--min-area 1, --connectivity 8) are filled in."""
+    given = [f for f, v in (("--min-area", args.min_area), ("--connectivity", args.connectivity)) if v is not None]
+    if not args.objects:
+        if given:
+            raise ValueError(f"{' / '.join(given)} belong to -objects: give -objects")
+    elif not (args.process or args.eval):
+        raise ValueError("-objects labels the masks of -process or -eval (or -test): give one of them")
+    args.min_area = 1 if args.min_area is None else args.min_area
+    args.connectivity = 8 if args.connectivity is None else args.connectivity
+    if args.min_area < 1:
+        raise ValueError(f"--min-area {args.min_area}: an object has at least 1 pixel")
+    if args.connectivity not in (4, 8):
+        raise ValueError(f"--connectivity {args.connectivity}: 4 or 8")
+    if args.objects and args.process and not args.binarymaskthreshold and not args.crf:
+        raise ValueError("-process -objects labels the thresholded mask (or with -crf the CRF mask): --binarymaskthreshold 0 without "
+                         "-crf leaves no binary mask")
 
 
 def main(argv=None):

@@ -20,7 +20,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, dataformat, metrics, parallel, sheets, video, vis
+from . import _lib, dataformat, metrics, objects, parallel, sheets, video, vis
 from .crf import GRID_KEYS, dense_crf, grid_points, parse_crf_grid
 from .engine import HourglassEngine
 from .generic_engine import GenericEngine
@@ -76,6 +76,7 @@ class Handler:
                            for name, tag in ((self.criticname, self.critic_args), (self.maskername, self.masker_args))}
         self._engines = {}
         self.crf_reports, self.sweep = [], None      # --crf-grid / --thresh-grid: the tables of Handler.crf, the dict of eval_sweep.json
+        self.objects = None         # -eval -objects: the dict of eval_objects.json
         self._trace = None          # tests set a dict of lists (Handler.start_trace): per-step indices / losses of the two training loops
 
     def start_trace(self):
@@ -470,6 +471,8 @@ class Handler:
             cols.append(M >= args.binarymaskthreshold)
         if args.crf:                    # main.py:1169-1172 (with --binarymaskthreshold 0 this column lands in position 2)
             cols.append(self.crf(frames, M, None))
+        if getattr(args, "objects", False):     # (this build's flag) not a column: the by-position naming and the strip stay as they are
+            self._process_objects(M, cols[-1] if args.crf else None, stems[:len(frames)])
         if args.process_salience:       # main.py:1176-1197
             sal_maps, sal_hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
             cols += [sal_maps, sal_hard]
@@ -488,6 +491,54 @@ class Handler:
                 for kind, g in zip(kinds, grey_rgb):
                     Image.fromarray(to_u8(g[i])).save(f"{out_dir}/{stem}-{kind}.png")
         return M
+
+    PROCESS_MAX_OBJECTS = 256       # rows of the object table of -process -objects
+
+    def _process_objects(self, M, crf_mask, stems):
+        """-process -objects: the thresholded masks (M >= --binarymaskthreshold, the comparison of the thresholded column), or with -crf
+        the CRF masks, labelled on the GPU (objects.py).  Rank 0 writes {R}/objects.json and per frame {R}/{stem}-objects-mask.png,
+        the pixels of the kept objects as 0 / 255 grey RGB."""
+        from PIL import Image
+        args = self.args
+        kw = dict(connectivity=args.connectivity, min_area=args.min_area, max_objects=self.PROCESS_MAX_OBJECTS, want_labels=False,
+                  want_mask=True)
+        if crf_mask is not None:
+            source, thresh = "crf-mask", None
+            res = objects.label(torch.from_numpy(np.ascontiguousarray(crf_mask[:, 0])).to(self.device), **kw)
+        else:
+            source, thresh = "thresholded-mask", float(args.binarymaskthreshold)
+            res = objects.label(torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device), thresh=thresh,
+                                inclusive=True, **kw)
+        if self.rank != 0:
+            return
+        kept, found, mask = res.kept.cpu().numpy(), res.found.cpu().numpy(), res.mask.cpu().numpy()
+        rows = objects.table_rows(res.table, kept, width=M.shape[-1])
+        report = {"source": source, "threshold": thresh, "connectivity": args.connectivity, "min_area": args.min_area,
+                  "max_objects": self.PROCESS_MAX_OBJECTS,
+                  "frames": {stem: {"found": int(found[i]), "kept": int(kept[i]), "objects": rows[i]} for i, stem in enumerate(stems)}}
+        out_dir = args.mask_output_imgs
+        os.makedirs(out_dir, exist_ok=True)
+        with open(f"{out_dir}/objects.json", "w") as fp:
+            json.dump(report, fp, indent=1)
+        for i, stem in enumerate(stems):
+            Image.fromarray(np.repeat((mask[i] * np.uint8(255))[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-objects-mask.png")
+
+    def _eval_objects(self, src, truth, thresh=None):
+        """One block of eval_objects.json: the stack `src` (device; float32 with the strict compare of -eval, or bool labels) labelled
+        and filtered on the GPU, the kept pixels and the unfiltered stack scored against `truth` (device bool) with metrics.iou_counts
+        / iou_curve.  Only the counts come back."""
+        args = self.args
+        res = objects.label(src, thresh=thresh, connectivity=args.connectivity, min_area=args.min_area, max_objects=1, want_labels=False,
+                            want_mask=True)
+        inter, union = metrics.iou_counts(res.mask, truth).tolist()
+        if thresh is None:
+            inter0, union0 = metrics.iou_counts(src, truth).tolist()
+        else:
+            inter0, union0 = (int(c[0]) for c in metrics.iou_curve(src, truth, [thresh]))
+        kept, found = res.kept.cpu().numpy(), res.found.cpu().numpy()
+        return {"inter": inter, "union": union, "iou": metrics.ratio(inter, union),
+                "unfiltered": {"inter": inter0, "union": union0, "iou": metrics.ratio(inter0, union0)},
+                "found": int(found.sum()), "kept": int(kept.sum()), "frames_without_objects": int(np.count_nonzero(kept == 0))}
 
     def _sweep_masks(self, X, to_device, progress, want_saliency=False, fp16=False, batchsize=128, train_mode=None):
         """The inference loop shared by -process and -eval (main.py:1130-1151, 900-953): eval-mode critic + masker over X in batches
@@ -643,6 +694,22 @@ class Handler:
                 os.makedirs(self.path, exist_ok=True)
                 with open(self.path + "eval_sweep.json", "w") as fp:
                     json.dump(_json_safe(sweep), fp, indent=1)
+        if getattr(args, "objects", False):     # (this build's flag) the masks as objects: labelled, filtered and scored on the GPU
+            dev_truth = torch.from_numpy(np.ascontiguousarray(truth)).to(self.device)
+            report = {"connectivity": args.connectivity, "min_area": args.min_area, "threshold": float(args.eval_thresh)}
+            report["mask"] = self._eval_objects(torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device),
+                                                dev_truth, thresh=float(args.eval_thresh))            # strict >, main.py:964
+            if args.crf:
+                report["crf"] = self._eval_objects(torch.from_numpy(np.ascontiguousarray(crf_m)).to(self.device), dev_truth)
+            self.objects = report = _json_safe(report)
+            if self.rank == 0:
+                os.makedirs(self.path, exist_ok=True)
+                with open(self.path + "eval_objects.json", "w") as fp:
+                    json.dump(report, fp, indent=1)
+            fmt = lambda v: "nan" if v is None else f"{v:.6f}"
+            print(f"\nOBJECTS conn={args.connectivity} min_area={args.min_area}: " + "; ".join(
+                f"{name}iou {fmt(b['iou'])} (unfiltered {fmt(b['unfiltered']['iou'])}), kept {b['kept']}/found {b['found']} objects"
+                for name, b in (("", report["mask"]),) + ((("crf ", report["crf"]),) if args.crf else ())))
         print("\nRESULTS", ious)
         if vid is not None and self.rank == 0 and ious[0] > self.ious[0]:          # main.py:1027
             layout, exe = vid

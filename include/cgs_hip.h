@@ -832,6 +832,28 @@ int cgs_iou_curve(const float* v, const uint8_t* truth, const float* thr, int32_
                   cgs_stream_t stream);
 int cgs_iou_counts(const uint8_t* labels, const uint8_t* truth, int32_t K, int64_t px, int64_t* counts, cgs_stream_t stream);
 
+/* ---- from masks to objects (csrc/objects.hip; this build's own -objects, no counterpart in the reference) --------------------------------
+ * Connected-component labelling of n frames of h x w (contiguous), one workgroup per frame in LDS, with an area filter, the numbering
+ * of scipy.ndimage.label and a table of the objects.  Integer throughout: deterministic, bit for bit the raster-scan flood fill.
+ * src_kind says when a pixel is on: CGS_OBJ_U8 uint8, non-zero (a bool stack is this); CGS_OBJ_F32_GT fp32, v > thresh (-eval's compare);
+ * CGS_OBJ_F32_GE fp32, v >= thresh (-process's compare); compared in fp32, a NaN is off.  connectivity 4 or 8.
+ * Per frame: a component is a maximal connected set of on pixels; those with area >= min_area are kept and numbered 1..K in raster
+ * order of their first pixel (the smallest y w + x).
+ *   labels    int32 [n][h][w] or NULL: the number of the pixel's component, 0 for off pixels and removed components; every kept
+ *             component is numbered, also those beyond max_objects
+ *   kept_mask uint8 [n][h][w] or NULL: 1 where labels is non-zero
+ *   count     int32 [n][2]: (kept, found), found counting the components before the filter
+ *   table     int32 [n][max_objects][8] or NULL: row k-1 is object k: area, x0, y0, x1, y1 (inclusive bounds), sum_x, sum_y, first
+ *             (the raster index of its first pixel); rows from min(kept, max_objects) on are zero
+ * Runs on `stream` without synchronising, allocates nothing, can be captured in a graph.  1 <= h, w <= 64, else CGS_ERR_UNSUPPORTED;
+ * src, count not NULL, n >= 1, a valid src_kind and connectivity, min_area >= 1, max_objects >= 1 (also when table is NULL), fp32 src /
+ * labels / count / table 4-byte aligned, else CGS_ERR_BADARG (nothing is launched).                                                     */
+enum { CGS_OBJ_U8 = 0, CGS_OBJ_F32_GT = 1, CGS_OBJ_F32_GE = 2 };
+enum { CGS_OBJ_FIELDS = 8, CGS_OBJ_MAX_SIDE = 64 };
+int cgs_objects_label(const void* src, int32_t src_kind, float thresh, int32_t n, int32_t h, int32_t w, int32_t connectivity,
+                      int32_t min_area, int32_t max_objects, int32_t* labels, uint8_t* kept_mask, int32_t* count, int32_t* table,
+                      cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
