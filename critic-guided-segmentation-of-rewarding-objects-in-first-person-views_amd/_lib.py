@@ -62,6 +62,7 @@ VIS_VALUES, VIS_CELL_W, VIS_CELL_H, VIS_NONTEMPORAL = 2, 64, 16, 1              
 VIS_INDEX_X, VIS_VALUE_X, VIS_VALUE_Y, VIS_VALUE_DY = 230, 1, 1, 15
 SHEET_ROWS, SHEET_MAX_N = 7, 1 << 20                                            # cgs_sheet_compose (include/cgs_hip.h)
 OBJ_U8, OBJ_F32_GT, OBJ_F32_GE, OBJ_FIELDS, OBJ_MAX_SIDE = 0, 1, 2, 8, 64       # cgs_objects_label (include/cgs_hip.h)
+OBJ_MATCH_MAX_OBJECTS, OBJ_MATCH_MAX_IOU = 64, 16                               # cgs_objects_match (include/cgs_hip.h)
 
 
 class ReduceJob(C.Structure):
@@ -210,6 +211,7 @@ SIGNATURES = {
     "cgs_iou_curve": (i32, [vp, vp, vp, i32, i32, i64, vp, vp]),
     "cgs_iou_counts": (i32, [vp, vp, i32, i64, vp, vp]),
     "cgs_objects_label": (i32, [vp, i32, f32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "cgs_objects_match": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]),
     "cgs_build_arch": (C.c_char_p, []),
     "cgs_abi_version": (i32, []),
 }

@@ -77,6 +77,7 @@ class Handler:
         self._engines = {}
         self.crf_reports, self.sweep = [], None      # --crf-grid / --thresh-grid: the tables of Handler.crf, the dict of eval_sweep.json
         self.objects = None         # -eval -objects: the dict of eval_objects.json
+        self.matches = None         # -eval -objects --match-iou: the dict of eval_match.json
         self._trace = None          # tests set a dict of lists (Handler.start_trace): per-step indices / losses of the two training loops
 
     def start_trace(self):
@@ -540,6 +541,18 @@ class Handler:
                 "unfiltered": {"inter": inter0, "union": union0, "iou": metrics.ratio(inter0, union0)},
                 "found": int(found.sum()), "kept": int(kept.sum()), "frames_without_objects": int(np.count_nonzero(kept == 0))}
 
+    MATCH_MAX_OBJECTS = 64          # objects per frame and side that -eval -objects --match-iou matches
+
+    def _eval_match(self, src, truth_labels, iou, thresh=None):
+        """One block of eval_match.json: the stack `src` (as _eval_objects takes it) labelled with --connectivity and --min-area -- the
+        objects eval_objects.json counts -- and matched on the GPU against the labelled truth (objects.match).  Only the counts and
+        the T sums of IoU come back."""
+        args = self.args
+        pred = objects.label(src, thresh=thresh, connectivity=args.connectivity, min_area=args.min_area, max_objects=self.MATCH_MAX_OBJECTS)
+        m = objects.match(pred.labels, truth_labels, iou=iou, max_objects=self.MATCH_MAX_OBJECTS)
+        return objects.match_report(m.pred_max, m.truth_max, m.matched_pred, m.matched_truth, objects.sum_iou(m.best, iou), iou,
+                                    max_objects=self.MATCH_MAX_OBJECTS)
+
     def _sweep_masks(self, X, to_device, progress, want_saliency=False, fp16=False, batchsize=128, train_mode=None):
         """The inference loop shared by -process and -eval (main.py:1130-1151, 900-953): eval-mode critic + masker over X in batches
         of 128, optionally the saliency baseline |d mean(pred) / d batch| summed over the colour channels.
@@ -710,6 +723,25 @@ class Handler:
             print(f"\nOBJECTS conn={args.connectivity} min_area={args.min_area}: " + "; ".join(
                 f"{name}iou {fmt(b['iou'])} (unfiltered {fmt(b['unfiltered']['iou'])}), kept {b['kept']}/found {b['found']} objects"
                 for name, b in (("", report["mask"]),) + ((("crf ", report["crf"]),) if args.crf else ())))
+            if getattr(args, "match_iou", ""):  # (this build's flag) those objects matched to the truth's objects, on the GPU
+                iou = objects.parse_match_iou(args.match_iou)
+                truth_labels = objects.label(dev_truth, connectivity=args.connectivity, min_area=1,      # the truth is not filtered
+                                             max_objects=self.MATCH_MAX_OBJECTS).labels
+                matched = {"connectivity": args.connectivity, "min_area": args.min_area, "threshold": float(args.eval_thresh),
+                           "max_objects": self.MATCH_MAX_OBJECTS, "iou": iou}
+                matched["mask"] = self._eval_match(torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device),
+                                                    truth_labels, iou, thresh=float(args.eval_thresh))    # strict >, main.py:964
+                if args.crf:
+                    matched["crf"] = self._eval_match(torch.from_numpy(np.ascontiguousarray(crf_m)).to(self.device), truth_labels, iou)
+                self.matches = matched = _json_safe(matched)
+                if self.rank == 0:
+                    with open(self.path + "eval_match.json", "w") as fp:
+                        json.dump(matched, fp, indent=1)
+                first = lambda b: b["per_iou"][0]
+                print(f"\nMATCH conn={args.connectivity} min_area={args.min_area} iou>={iou[0]:g} ({len(iou)} thresholds): " + "; ".join(
+                    f"{name}matched {first(b)['matched_pred']}/{b['pred_objects']} predicted, {first(b)['matched_truth']}/"
+                    f"{b['truth_objects']} truth objects, f1 {fmt(first(b)['f1'])}, pq {fmt(first(b)['pq'])}"
+                    for name, b in (("", matched["mask"]),) + ((("crf ", matched["crf"]),) if args.crf else ())))
         print("\nRESULTS", ious)
         if vid is not None and self.rank == 0 and ious[0] > self.ious[0]:          # main.py:1027
             layout, exe = vid

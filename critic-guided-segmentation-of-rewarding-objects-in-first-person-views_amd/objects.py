@@ -1,7 +1,11 @@
 """From masks to objects on the GPU (csrc/objects.hip): connected-component labelling of a mask stack where it is, an area filter, the
 numbering of ``scipy.ndimage.label`` and a table of the objects (area, bounding box, coordinate sums, first pixel).  Everything is
 integer and stays on the device; ``table_rows`` is the host helper that turns a table into the dicts of ``objects.json``
-(handler.py: ``-process -objects`` / ``-eval -objects``)."""
+(handler.py: ``-process -objects`` / ``-eval -objects``).
+
+``match`` (csrc/objects_match.hip) matches the objects of two label stacks frame by frame at a list of IoU thresholds; ``sum_iou`` adds
+up the matched pairs' IoU on the device, and ``parse_match_iou`` / ``match_report`` are the pure host helpers of
+``-eval -objects --match-iou`` (eval_match.json)."""
 from collections import namedtuple
 
 import numpy as np
@@ -11,8 +15,10 @@ from . import _lib
 
 MAX_SIDE = _lib.OBJ_MAX_SIDE
 FIELDS = ("area", "x0", "y0", "x1", "y1", "sum_x", "sum_y", "first")
+MATCH_MAX_OBJECTS, MATCH_MAX_IOU = _lib.OBJ_MATCH_MAX_OBJECTS, _lib.OBJ_MATCH_MAX_IOU
 
 Objects = namedtuple("Objects", ["labels", "mask", "kept", "found", "table"])
+Matches = namedtuple("Matches", ["pred_max", "truth_max", "matched_pred", "matched_truth", "best"])
 
 
 def label(src, thresh=None, inclusive=False, connectivity=8, min_area=1, max_objects=64, want_labels=True, want_mask=False):
@@ -74,7 +80,142 @@ def _as_int(v, what):
     return int(v)
 
 
-# ---------------------------------------------------------------------------------------------------------------- host helper
+# ---------------------------------------------------------------------------------------------------------------- matching
+def iou_milli(iou):
+    """A sequence of IoU thresholds as whole thousandths: round(t * 1000) for each.  ValueError for an empty list, more than 16, a value
+    that is not within 1e-6 of a thousandth or lies outside [0.5, 1] (below 0.5 a match would not be unique), or a duplicate."""
+    try:
+        vals = [float(t) for t in iou]
+    except TypeError:
+        raise ValueError(f"iou must be a sequence of numbers, got {iou!r}") from None
+    if not 1 <= len(vals) <= MATCH_MAX_IOU:
+        raise ValueError(f"1 to {MATCH_MAX_IOU} IoU thresholds, got {len(vals)}")
+    out = []
+    for t in vals:
+        if t != t or abs(t) == float("inf"):
+            raise ValueError(f"IoU threshold {t!r} is not a number")
+        m = round(t * 1000)
+        if abs(t * 1000 - m) > 1e-3:
+            raise ValueError(f"IoU threshold {t!r} is not a whole number of thousandths")
+        if not 500 <= m <= 1000:
+            raise ValueError(f"IoU threshold {t!r} is outside [0.5, 1]")
+        if m in out:
+            raise ValueError(f"IoU threshold {t!r} is given twice")
+        out.append(m)
+    return out
+
+
+def match(pred_labels, truth_labels, iou=(0.5,), max_objects=64, want_best=True):
+    """pred_labels, truth_labels: int32 device tensors [n,h,w] or [h,w] of one shape, 1 <= h, w <= 64, label maps as ``label`` gives
+    them (a value <= 0 is background; hand-made maps need not be connected components).  Objects numbered above max_objects (1..64)
+    take no part in the matching but show in pred_max / truth_max.  iou: 1..16 distinct thresholds in [0.5, 1], whole thousandths; a
+    predicted and a truth object match at t when inter > 0 and inter / union >= t, compared exactly in integers.
+    Returns Matches(pred_max int32 [n], truth_max int32 [n] (the largest label of each frame), matched_pred int32 [n,T] (objects
+    <= max_objects with at least one match), matched_truth int32 [n,T], best int32 [n,2,max_objects,4] or None: side 0, row p-1 is
+    (t, inter, area_p, area_t) of the truth object of largest IoU with p (ties: the smallest t; (0, 0, area_p, 0) without overlap), side
+    1, row t-1 is (p, inter, area_t, area_p); zero rows from min(largest label, max_objects) on), all on the inputs' device.
+    No CPU path: raises CgsError without a GPU."""
+    for name, t in (("pred_labels", pred_labels), ("truth_labels", truth_labels)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != torch.int32:
+            raise ValueError(f"{name} must be torch.int32, got {t.dtype}")
+    if pred_labels.dim() not in (2, 3) or pred_labels.shape != truth_labels.shape:
+        raise ValueError(f"the label maps must be [n,h,w] or [h,w] and of one shape, got {tuple(pred_labels.shape)} and "
+                         f"{tuple(truth_labels.shape)}")
+    if pred_labels.dim() == 2:
+        pred_labels, truth_labels = pred_labels[None], truth_labels[None]
+    n, h, w = (int(s) for s in pred_labels.shape)
+    if n < 1 or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError(f"label maps {tuple(pred_labels.shape)}: at least one frame of 1..{MAX_SIDE} x 1..{MAX_SIDE} pixels")
+    milli = iou_milli(iou)
+    max_objects = _as_int(max_objects, "max_objects")
+    if not 1 <= max_objects <= MATCH_MAX_OBJECTS:
+        raise ValueError(f"max_objects must be 1..{MATCH_MAX_OBJECTS}, got {max_objects}")
+    if not torch.cuda.is_available() or not (pred_labels.is_cuda and truth_labels.is_cuda):
+        raise _lib.CgsError("objects.match runs on the GPU (cgs_objects_match); " + ("no GPU is visible" if not torch.cuda.is_available()
+                            else f"the tensors are on {pred_labels.device} and {truth_labels.device}") + " and there is no CPU fallback")
+    if pred_labels.device != truth_labels.device:
+        raise ValueError(f"the label maps are on two devices, {pred_labels.device} and {truth_labels.device}")
+    pred_labels, truth_labels = pred_labels.contiguous(), truth_labels.contiguous()
+    dev, T = pred_labels.device, len(milli)
+    with torch.cuda.device(dev):
+        thr = torch.tensor(milli, dtype=torch.int32).to(dev)
+        counts = torch.empty((n, 2 + 2 * T), dtype=torch.int32, device=dev)
+        best = torch.empty((n, 2, max_objects, 4), dtype=torch.int32, device=dev) if want_best else None
+        _lib.call("cgs_objects_match", pred_labels.data_ptr(), truth_labels.data_ptr(), n, h, w, max_objects, thr.data_ptr(), T,
+                  counts.data_ptr(), best.data_ptr() if want_best else None, torch.cuda.current_stream().cuda_stream)
+    pairs = counts[:, 2:].reshape(n, T, 2)
+    return Matches(counts[:, 0].contiguous(), counts[:, 1].contiguous(), pairs[:, :, 0].contiguous(), pairs[:, :, 1].contiguous(), best)
+
+
+def sum_iou(best, iou):
+    """best: Matches.best [n,2,K,4] (a tensor, on any device).  float64 [T] on its device: for each threshold the sum, over the predicted
+    objects whose best IoU reaches it, of that IoU (the numerator of panoptic quality).  The compare is the kernel's, in integers."""
+    milli = torch.tensor(iou_milli(iou), dtype=torch.int64, device=best.device)
+    rows = best[:, 0].reshape(-1, 4).to(torch.int64)
+    inter, union = rows[:, 1], rows[:, 2] + rows[:, 3] - rows[:, 1]
+    value = inter.double() / union.clamp(min=1).double()                 # a row without overlap has inter = 0: it adds nothing
+    reach = (inter[None] > 0) & (1000 * inter[None] >= milli[:, None] * union[None])
+    return (value[None] * reach).sum(dim=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- host helpers
+def parse_match_iou(s):
+    """``"0.5-0.75-0.95"`` (dash-separated) or ``"lo:hi:n"`` (np.linspace(lo, hi, n) in float64), as --thresh-grid is written.  Returns
+    the thresholds as floats, whole thousandths (0.5:0.95:10 gives exactly 0.5, 0.55, ..., 0.95); ValueError as ``iou_milli``."""
+    s = str(s).strip()
+    try:
+        if ":" in s:
+            lo, hi, n = s.split(":")
+            if int(n) < 1:
+                raise ValueError
+            vals = np.linspace(float(lo), float(hi), int(n), dtype=np.float64).tolist()
+        else:
+            vals = [float(p) for p in s.split("-")]                      # an empty item ("0.5-", "0.5--0.6") is no number
+    except ValueError:
+        raise ValueError(f"--match-iou {s!r}: expected dash-separated numbers (0.5-0.75-0.95) or lo:hi:n") from None
+    try:
+        return [m / 1000 for m in iou_milli(vals)]
+    except ValueError as e:
+        raise ValueError(f"--match-iou {s!r}: {e}") from None
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def match_report(pred_max, truth_max, matched_pred, matched_truth, sum_iou, iou, max_objects=MATCH_MAX_OBJECTS):
+    """One block of eval_match.json from the outputs of ``match`` over a stack (tensors or arrays: pred_max, truth_max [n],
+    matched_pred, matched_truth [n,T]) and sum_iou [T]: {"pred_objects": sum of pred_max, "truth_objects", "overflow_frames": frames
+    where either map holds more than max_objects objects (those beyond it can never match), "per_iou": per threshold {"iou",
+    "matched_pred", "matched_truth", "fp": pred_objects - matched_pred, "fn": truth_objects - matched_truth, "precision": matched_pred /
+    pred_objects, "recall": matched_truth / truth_objects, "f1": their harmonic mean, "sum_iou", "pq": sum_iou / (matched_pred + fp / 2
+    + fn / 2)}}.  A ratio with a zero denominator is None."""
+    milli = iou_milli(iou)
+    pred_max, truth_max = _host(pred_max).reshape(-1).astype(np.int64), _host(truth_max).reshape(-1).astype(np.int64)
+    mp, mt = _host(matched_pred).astype(np.int64), _host(matched_truth).astype(np.int64)
+    sums = _host(sum_iou).reshape(-1).astype(np.float64)
+    n, T = pred_max.shape[0], len(milli)
+    if truth_max.shape[0] != n or mp.shape != (n, T) or mt.shape != (n, T) or sums.shape[0] != T:
+        raise ValueError(f"{n} and {truth_max.shape[0]} frames, matched counts {mp.shape} and {mt.shape}, {sums.shape[0]} sums: "
+                         f"expected [n], [n], [n,{T}], [n,{T}] and [{T}]")
+    ratio = lambda a, b: a / b if b else None
+    n_pred, n_truth = int(pred_max.sum()), int(truth_max.sum())
+    rows = []
+    for k, m in enumerate(milli):
+        tp_p, tp_t, s = int(mp[:, k].sum()), int(mt[:, k].sum()), float(sums[k])
+        fp, fn = n_pred - tp_p, n_truth - tp_t
+        if tp_p < 0 or tp_t < 0 or fp < 0 or fn < 0:
+            raise ValueError(f"matched counts ({tp_p}, {tp_t}) do not fit {n_pred} predicted and {n_truth} truth objects")
+        precision, recall = ratio(tp_p, n_pred), ratio(tp_t, n_truth)
+        f1 = None if precision is None or recall is None else ratio(2 * precision * recall, precision + recall)
+        rows.append({"iou": m / 1000, "matched_pred": tp_p, "matched_truth": tp_t, "fp": fp, "fn": fn, "precision": precision,
+                     "recall": recall, "f1": f1, "sum_iou": s, "pq": ratio(s, tp_p + fp / 2 + fn / 2)})
+    return {"pred_objects": n_pred, "truth_objects": n_truth,
+            "overflow_frames": int(np.count_nonzero((pred_max > max_objects) | (truth_max > max_objects))), "per_iou": rows}
+
+
 def table_rows(table, kept, width=MAX_SIDE):
     """table [n,max_objects,8] and kept [n] (tensors or arrays) -> per frame the list of its first min(kept, max_objects) objects as
     {"label", "area", "bbox": [x0, y0, x1, y1] (inclusive), "centroid": [sum_x / area, sum_y / area], "first": [x, y]}.

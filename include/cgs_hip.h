@@ -854,6 +854,31 @@ int cgs_objects_label(const void* src, int32_t src_kind, float thresh, int32_t n
                       int32_t min_area, int32_t max_objects, int32_t* labels, uint8_t* kept_mask, int32_t* count, int32_t* table,
                       cgs_stream_t stream);
 
+/* ---- from objects to matches (csrc/objects_match.hip; this build's own -eval -objects --match-iou, no counterpart in the reference) -------
+ * Instance matching of two label maps per frame: every predicted object intersected with every truth object, one workgroup per frame,
+ * the K x K intersection table and the areas in LDS (K = max_objects).  No floating point and only LDS integer atomics: deterministic,
+ * bit for bit.
+ *   pred, truth  int32 [n][h][w] (contiguous) as cgs_objects_label writes `labels`: a value <= 0 is background, objects are numbered
+ *                from 1.  Hand-made maps are allowed, an object need not be connected.  Objects numbered above K take no part: their
+ *                pixels add to no area and no intersection (they still show in pred_max / truth_max); an object <= K keeps its full
+ *                area whatever the other map holds under it.
+ *   iou_milli    int32 [T] on the device: IoU thresholds in thousandths (the caller keeps them in 500..1000).  The pair (p, t) matches
+ *                at m when inter > 0 && 1000 inter >= m (area_p + area_t - inter), compared exactly in int32.
+ *   counts       int32 [n][2 + 2 T]: pred_max, truth_max (the largest label of the frame's map, 0 for an empty one), then for each
+ *                threshold k the two words matched_pred[k], matched_truth[k] (at 2 + 2 k and 3 + 2 k): the number of p <= K with at
+ *                least one matching t <= K, and the same from the truth side.  At 0.5 exactly one object can match two of the other
+ *                map, so the two can differ.
+ *   best         int32 [n][2][K][4] or NULL.  Side 0, row p - 1: (t, inter, area_p, area_t) of the truth object of largest IoU with p
+ *                (exact, by cross-multiplication; ties go to the smallest t), (0, 0, area_p, 0) when p overlaps none.  Side 1, row
+ *                t - 1: the same seen from the truth object, (p, inter, area_t, area_p).  Rows from min(max label of that side, K) on
+ *                are zero; every row is written.
+ * Runs on `stream` without synchronising, allocates nothing, can be captured in a graph.  pred, truth, iou_milli, counts not NULL,
+ * n, h, w, max_objects >= 1, 1 <= T <= CGS_OBJ_MATCH_MAX_IOU, every pointer 4-byte aligned, else CGS_ERR_BADARG (nothing is
+ * launched); then h, w <= 64 and max_objects <= CGS_OBJ_MATCH_MAX_OBJECTS, else CGS_ERR_UNSUPPORTED.                                   */
+enum { CGS_OBJ_MATCH_MAX_OBJECTS = 64, CGS_OBJ_MATCH_MAX_IOU = 16 };
+int cgs_objects_match(const int32_t* pred, const int32_t* truth, int32_t n, int32_t h, int32_t w, int32_t max_objects,
+                      const int32_t* iou_milli, int32_t T, int32_t* counts, int32_t* best, cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
