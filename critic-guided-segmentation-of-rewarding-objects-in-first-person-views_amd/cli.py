@@ -34,6 +34,9 @@ def build_parser():
     # (this build's own flag) -eval -objects --match-iou "0.5-0.75-0.95" or "lo:hi:n": the predicted objects matched to the objects of
     # the labelled truth at these IoU thresholds on the GPU (objects.match); leaves {model}/eval_match.json
     p.add_argument("--match-iou", type=str, default="")
+    # (this build's own flag) -objects --track-iou T with -process or -eval: the objects followed from frame to frame on the GPU
+    # (objects.track); leaves {model}/eval_tracks.json, or {R}/tracks.json and {R}/{stem}-tracks-mask.png
+    p.add_argument("--track-iou", type=str, default="")
     for flag in ("-masker", "-critic", "-cload", "-mload", "-staticnorm", "-visbesteval", "-salglobal"):
         p.add_argument(flag, type=bool, default=True)
     p.add_argument("--salience-thresh", type=float, default="1.5")
@@ -109,8 +112,8 @@ def check_sweep_flags(args):
 
 
 def check_objects_flags(args):
-    """-objects / --min-area / --connectivity / --match-iou: combinations that could not run and a malformed --match-iou are refused
-    here, before any GPU work; the defaults (--min-area 1, --connectivity 8) are filled in."""
+    """-objects / --min-area / --connectivity / --match-iou / --track-iou: combinations that could not run and a malformed --match-iou
+    or --track-iou are refused here, before any GPU work; the defaults (--min-area 1, --connectivity 8) are filled in."""
     given = [f for f, v in (("--min-area", args.min_area), ("--connectivity", args.connectivity)) if v is not None]
     if args.match_iou:
         from .objects import parse_match_iou
@@ -120,6 +123,10 @@ def check_objects_flags(args):
             raise ValueError("--match-iou matches the objects against the labels of -eval; -process has none")
         if args.objects and not args.eval:
             raise ValueError("--match-iou belongs to -eval -objects: give -eval (or -test)")
+    if args.track_iou:
+        from .objects import parse_track_iou
+        given.append("--track-iou")
+        parse_track_iou(args.track_iou)
     if not args.objects:
         if given:
             raise ValueError(f"{' / '.join(given)} belong to -objects: give -objects")

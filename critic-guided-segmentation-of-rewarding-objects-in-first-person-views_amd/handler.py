@@ -78,6 +78,7 @@ class Handler:
         self.crf_reports, self.sweep = [], None      # --crf-grid / --thresh-grid: the tables of Handler.crf, the dict of eval_sweep.json
         self.objects = None         # -eval -objects: the dict of eval_objects.json
         self.matches = None         # -eval -objects --match-iou: the dict of eval_match.json
+        self.tracks = None          # -eval -objects --track-iou: the dict of eval_tracks.json
         self._trace = None          # tests set a dict of lists (Handler.start_trace): per-step indices / losses of the two training loops
 
     def start_trace(self):
@@ -474,6 +475,8 @@ class Handler:
             cols.append(self.crf(frames, M, None))
         if getattr(args, "objects", False):     # (this build's flag) not a column: the by-position naming and the strip stay as they are
             self._process_objects(M, cols[-1] if args.crf else None, stems[:len(frames)])
+            if getattr(args, "track_iou", ""):
+                self._process_tracks(M, cols[-1] if args.crf else None, stems[:len(frames)])
         if args.process_salience:       # main.py:1176-1197
             sal_maps, sal_hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
             cols += [sal_maps, sal_hard]
@@ -523,6 +526,55 @@ class Handler:
             json.dump(report, fp, indent=1)
         for i, stem in enumerate(stems):
             Image.fromarray(np.repeat((mask[i] * np.uint8(255))[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-objects-mask.png")
+
+    def _process_tracks(self, M, crf_mask, stems):
+        """-process -objects --track-iou: the objects objects.json describes (the same source, --connectivity and --min-area), followed
+        through the frames in natural order of their names on the GPU (objects.track); labels above 64 are untracked.  Rank 0 writes
+        {R}/tracks.json and per frame {R}/{stem}-tracks-mask.png, a colour per track."""
+        from PIL import Image
+        args = self.args
+        K, iou = self.MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou)
+        kw = dict(connectivity=args.connectivity, min_area=args.min_area, max_objects=K)
+        if crf_mask is not None:
+            source, thresh = "crf-mask", None
+            res = objects.label(torch.from_numpy(np.ascontiguousarray(crf_mask[:, 0])).to(self.device), **kw)
+        else:
+            source, thresh = "thresholded-mask", float(args.binarymaskthreshold)
+            res = objects.label(torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device), thresh=thresh,
+                                inclusive=True, **kw)
+        order = objects.natural_order(stems)                             # os.listdir's order is arbitrary; only the label stack is reordered
+        pick = torch.tensor(order, dtype=torch.int64, device=res.labels.device)
+        tr = objects.track(res.labels[pick], iou=iou, max_objects=K, want_rgb=True)
+        if self.rank != 0:
+            return
+        totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
+        side = objects.track_report(totals, tr.table[:, 2], tr.table[:, 6].sum(dtype=torch.int64), tr.table[:, 7].sum(dtype=torch.int64),
+                                    (res.kept[pick] - K).clamp(min=0).sum())
+        rows = objects.track_rows(tr.table, side["tracks"])
+        names = [stems[i] for i in order]
+        prev, trk, rgb = tr.prev.cpu().numpy(), tr.track.cpu().numpy(), tr.rgb.cpu().numpy()
+        report = {"source": source, "threshold": thresh, "connectivity": args.connectivity, "min_area": args.min_area, "max_objects": K,
+                  "track_iou": iou, "summary": side, "order": names,
+                  "frames": {stem: [{"label": int(l) + 1, "track": int(trk[j, l]), "prev": int(prev[j, l])} for l in np.flatnonzero(trk[j])]
+                             for j, stem in enumerate(names)},
+                  "tracks": [{"track": r["track"], "first": names[r["first_frame"]], "last": names[r["first_frame"] + r["length"] - 1],
+                              "length": r["length"], "area_sum": r["area_sum"], "area_min": r["area_min"], "area_max": r["area_max"],
+                              "link_iou": r["link_iou"]} for r in rows]}
+        out_dir = args.mask_output_imgs
+        os.makedirs(out_dir, exist_ok=True)
+        with open(f"{out_dir}/tracks.json", "w") as fp:
+            json.dump(_json_safe(report), fp, indent=1)
+        for j, stem in enumerate(names):
+            Image.fromarray(rgb[j]).save(f"{out_dir}/{stem}-tracks-mask.png")
+
+    def _eval_tracks(self, labelled, iou):
+        """(Tracks, one side of eval_tracks.json) of a labelled stack (objects.label's result with max_objects = 64): tracked on the
+        GPU, the length histogram and the link sums formed there; only the totals, 7 counts and 3 sums come back."""
+        K = self.MATCH_MAX_OBJECTS
+        tr = objects.track(labelled.labels, iou=iou, max_objects=K)
+        totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
+        return tr, objects.track_report(totals, tr.table[:, 2], tr.table[:, 6].sum(dtype=torch.int64), tr.table[:, 7].sum(dtype=torch.int64),
+                                        (labelled.kept - K).clamp(min=0).sum())
 
     def _eval_objects(self, src, truth, thresh=None):
         """One block of eval_objects.json: the stack `src` (device; float32 with the strict compare of -eval, or bool labels) labelled
@@ -742,6 +794,34 @@ class Handler:
                     f"{name}matched {first(b)['matched_pred']}/{b['pred_objects']} predicted, {first(b)['matched_truth']}/"
                     f"{b['truth_objects']} truth objects, f1 {fmt(first(b)['f1'])}, pq {fmt(first(b)['pq'])}"
                     for name, b in (("", matched["mask"]),) + ((("crf ", matched["crf"]),) if args.crf else ())))
+            if getattr(args, "track_iou", ""):  # (this build's flag) the same objects followed from frame to frame, on the GPU
+                K, t_iou = self.MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou)
+                m_iou = objects.parse_match_iou(args.match_iou) if getattr(args, "match_iou", "") else None
+                truth_obj = objects.label(dev_truth, connectivity=args.connectivity, min_area=1, max_objects=K)   # not filtered
+                truth_tr, truth_side = self._eval_tracks(truth_obj, t_iou)
+                tracked = {"connectivity": args.connectivity, "min_area": args.min_area, "threshold": float(args.eval_thresh),
+                           "max_objects": K, "track_iou": t_iou, "truth": truth_side}
+                sources = [("mask", torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device), float(args.eval_thresh))]
+                if args.crf:
+                    sources.append(("crf", torch.from_numpy(np.ascontiguousarray(crf_m)).to(self.device), None))
+                for name, src, thr in sources:
+                    pred = objects.label(src, thresh=thr, connectivity=args.connectivity, min_area=args.min_area, max_objects=K)
+                    pred_tr, side = self._eval_tracks(pred, t_iou)
+                    tracked[name] = {"pred": side}
+                    if m_iou is not None:                                 # identity switches at the thresholds of --match-iou
+                        best = objects.match(pred.labels, truth_obj.labels, iou=m_iou, max_objects=K).best
+                        counts = objects.switches(truth_tr.prev, pred_tr.track, best, m_iou).cpu().numpy()
+                        tracked[name]["switches"] = [{"iou": t, "covered": int(c[0]), "continued": int(c[1]), "switches": int(c[2]),
+                                                      "switch_rate": int(c[2]) / int(c[1]) if c[1] else None}
+                                                     for t, c in zip(m_iou, counts)]
+                self.tracks = tracked = _json_safe(tracked)
+                if self.rank == 0:
+                    with open(self.path + "eval_tracks.json", "w") as fp:
+                        json.dump(tracked, fp, indent=1)
+                p = tracked["mask"]["pred"]
+                print(f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g}: {p['tracks']} tracks over {p['objects']} "
+                      f"objects, mean length {fmt(p['mean_length'])}, longest {p['max_length']}; truth {truth_side['tracks']} tracks over "
+                      f"{truth_side['objects']} objects")
         print("\nRESULTS", ious)
         if vid is not None and self.rank == 0 and ious[0] > self.ious[0]:          # main.py:1027
             layout, exe = vid

@@ -5,7 +5,13 @@ integer and stays on the device; ``table_rows`` is the host helper that turns a 
 
 ``match`` (csrc/objects_match.hip) matches the objects of two label stacks frame by frame at a list of IoU thresholds; ``sum_iou`` adds
 up the matched pairs' IoU on the device, and ``parse_match_iou`` / ``match_report`` are the pure host helpers of
-``-eval -objects --match-iou`` (eval_match.json)."""
+``-eval -objects --match-iou`` (eval_match.json).
+
+``track`` (csrc/objects_track.hip) follows the objects of one label stack from frame to frame (mutual best partners above an IoU
+threshold, chains resolved on the device), ``switches`` counts identity switches of a prediction's tracks against the truth's, and
+``parse_track_iou`` / ``natural_order`` / ``track_report`` / ``track_rows`` are the pure host helpers of ``-objects --track-iou``
+(eval_tracks.json, tracks.json)."""
+import re
 from collections import namedtuple
 
 import numpy as np
@@ -19,6 +25,10 @@ MATCH_MAX_OBJECTS, MATCH_MAX_IOU = _lib.OBJ_MATCH_MAX_OBJECTS, _lib.OBJ_MATCH_MA
 
 Objects = namedtuple("Objects", ["labels", "mask", "kept", "found", "table"])
 Matches = namedtuple("Matches", ["pred_max", "truth_max", "matched_pred", "matched_truth", "best"])
+TRACK_FIELDS = ("first_frame", "first_label", "length", "area_sum", "area_min", "area_max", "inter_sum", "union_sum")
+TRACK_MAX_FRAMES = _lib.OBJ_TRACK_MAX_FRAMES
+LENGTH_BINS = ("1", "2", "3-4", "5-8", "9-16", "17-32", "33+")             # upper ends 1, 2, 4, 8, 16, 32, then the rest
+Tracks = namedtuple("Tracks", ["prev", "track", "n_tracks", "n_links", "n_objects", "longest", "table", "track_labels", "rgb"])
 
 
 def label(src, thresh=None, inclusive=False, connectivity=8, min_area=1, max_objects=64, want_labels=True, want_mask=False):
@@ -160,7 +170,178 @@ def sum_iou(best, iou):
     return (value[None] * reach).sum(dim=1)
 
 
+# ---------------------------------------------------------------------------------------------------------------- tracking
+def _track_milli(iou):
+    """One link threshold in (0, 1] as whole thousandths; ValueError in the style of ``iou_milli``."""
+    if isinstance(iou, bool) or not isinstance(iou, (int, float, np.integer, np.floating)):
+        raise ValueError(f"the track IoU must be one number, got {iou!r}")
+    t = float(iou)
+    if t != t or abs(t) == float("inf"):
+        raise ValueError(f"track IoU {t!r} is not a number")
+    m = round(t * 1000)
+    if abs(t * 1000 - m) > 1e-3:
+        raise ValueError(f"track IoU {t!r} is not a whole number of thousandths")
+    if not 1 <= m <= 1000:
+        raise ValueError(f"track IoU {t!r} is outside (0, 1]")
+    return m
+
+
+def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, want_rgb=False):
+    """labels: int32 device tensor [n,h,w] or [h,w] (then n = 1), 1 <= h, w <= 64, n <= 2^17, a label stack as ``label`` gives it
+    (hand-made maps allowed; views are made contiguous).  An object of frame f is a label in 1..max_objects (at most 64) with a pixel
+    in f.  Objects p of f and q of f + 1 are linked when each is the other's best partner (``match``'s `best`: largest IoU, ties to the
+    smallest number) and inter / union >= iou, compared in integers; iou is one number in (0, 1], whole thousandths -- mutual best keeps
+    links one-to-one below 0.5 too.  A track is a maximal chain of links; tracks are numbered from 1 by their first frame, then label.
+    Returns Tracks(prev int32 [n,K]: the label in f - 1 that object l of f continues (0: none), track int32 [n,K]: the track number (0:
+    no object), n_tracks, n_links, n_objects, longest: int32 scalars ON THE DEVICE (no synchronisation here; int() them), table int32
+    [max_tracks,8]: first_frame, first_label, length, area_sum, area_min, area_max, inter_sum, union_sum per track (the last two over
+    its links), zero rows from min(n_tracks, max_tracks) on; max_tracks defaults to n * max_objects, which holds every track;
+    track_labels int32 [n,h,w] or None: per pixel its object's track, rgb uint8 [n,h,w,3] or None: a colour per track, black where
+    there is none).  No CPU path: raises CgsError without a GPU."""
+    if not isinstance(labels, torch.Tensor):
+        raise ValueError(f"labels must be a torch tensor, got {type(labels).__name__}")
+    if labels.dtype != torch.int32:
+        raise ValueError(f"labels must be torch.int32, got {labels.dtype}")
+    if labels.dim() not in (2, 3):
+        raise ValueError(f"labels must be [n,h,w] or [h,w], got {tuple(labels.shape)}")
+    if labels.dim() == 2:
+        labels = labels[None]
+    n, h, w = (int(s) for s in labels.shape)
+    if not 1 <= n <= TRACK_MAX_FRAMES or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError(f"labels {tuple(labels.shape)}: 1..{TRACK_MAX_FRAMES} frames of 1..{MAX_SIDE} x 1..{MAX_SIDE} pixels")
+    milli = _track_milli(iou)
+    max_objects = _as_int(max_objects, "max_objects")
+    if not 1 <= max_objects <= MATCH_MAX_OBJECTS:
+        raise ValueError(f"max_objects must be 1..{MATCH_MAX_OBJECTS}, got {max_objects}")
+    max_tracks = n * max_objects if max_tracks is None else _as_int(max_tracks, "max_tracks")
+    if not 1 <= max_tracks <= 0x7FFFFFFF // len(TRACK_FIELDS):
+        raise ValueError(f"max_tracks must be at least 1 (and its table fit 32-bit indices), got {max_tracks}")
+    if not torch.cuda.is_available() or not labels.is_cuda:
+        raise _lib.CgsError("objects.track runs on the GPU (cgs_objects_track); " + ("no GPU is visible" if not torch.cuda.is_available()
+                            else f"the tensor is on {labels.device}") + " and there is no CPU fallback")
+    labels = labels.contiguous()
+    dev, K = labels.device, max_objects
+    with torch.cuda.device(dev):
+        need = int(_lib.load().cgs_objects_track_scratch_bytes(n, K))
+        scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        prev = torch.empty((n, K), dtype=torch.int32, device=dev)
+        trk = torch.empty((n, K), dtype=torch.int32, device=dev)
+        totals = torch.empty(4, dtype=torch.int32, device=dev)
+        table = torch.empty((max_tracks, len(TRACK_FIELDS)), dtype=torch.int32, device=dev)
+        painted = torch.empty((n, h, w), dtype=torch.int32, device=dev) if want_labels else None
+        rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev) if want_rgb else None
+        _lib.call("cgs_objects_track", labels.data_ptr(), n, h, w, K, milli, max_tracks, prev.data_ptr(), trk.data_ptr(),
+                  totals.data_ptr(), table.data_ptr(), painted.data_ptr() if want_labels else None, rgb.data_ptr() if want_rgb else None,
+                  scratch.data_ptr(), scratch.numel() * 8, torch.cuda.current_stream().cuda_stream)
+    return Tracks(prev, trk, totals[0], totals[1], totals[2], totals[3], table, painted, rgb)
+
+
+def switches(truth_prev, pred_track, best, iou):
+    """truth_prev: ``track(truth).prev``, pred_track: ``track(pred).track``, both int32 [n,K]; best: ``match(pred, truth).best`` int32
+    [n,2,K,4], all on one device; iou as ``match`` takes it.  int32 [T,3] on the device, per threshold (covered: truth objects whose best
+    predicted partner reaches it, continued: truth links with both ends covered, switches: continued links whose two predicted partners
+    lie in different predicted tracks).  Gaps are not bridged: an uncovered frame ends the comparison there."""
+    for name, t in (("truth_prev", truth_prev), ("pred_track", pred_track), ("best", best)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != torch.int32:
+            raise ValueError(f"{name} must be torch.int32, got {t.dtype}")
+    if truth_prev.dim() != 2 or truth_prev.shape != pred_track.shape:
+        raise ValueError(f"truth_prev and pred_track must be [n,K] of one shape, got {tuple(truth_prev.shape)} and {tuple(pred_track.shape)}")
+    n, K = (int(s) for s in truth_prev.shape)
+    if n < 1 or not 1 <= K <= MATCH_MAX_OBJECTS or n > TRACK_MAX_FRAMES or tuple(best.shape) != (n, 2, K, 4):
+        raise ValueError(f"[n,K] = [{n},{K}] (1..{TRACK_MAX_FRAMES} frames, K in 1..{MATCH_MAX_OBJECTS}) needs best [{n},2,{K},4], got "
+                         f"{tuple(best.shape)}")
+    milli = iou_milli(iou)
+    if not torch.cuda.is_available() or not (truth_prev.is_cuda and pred_track.is_cuda and best.is_cuda):
+        raise _lib.CgsError("objects.switches runs on the GPU (cgs_objects_track_switches); there is no CPU fallback")
+    if not truth_prev.device == pred_track.device == best.device:
+        raise ValueError("truth_prev, pred_track and best are on different devices")
+    truth_prev, pred_track, best = truth_prev.contiguous(), pred_track.contiguous(), best.contiguous()
+    dev = best.device
+    with torch.cuda.device(dev):
+        thr = torch.tensor(milli, dtype=torch.int32).to(dev)
+        counts = torch.empty((len(milli), 3), dtype=torch.int32, device=dev)
+        _lib.call("cgs_objects_track_switches", truth_prev.data_ptr(), pred_track.data_ptr(), best.data_ptr(), thr.data_ptr(), len(milli),
+                  n, K, counts.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return counts
+
+
 # ---------------------------------------------------------------------------------------------------------------- host helpers
+def parse_track_iou(s):
+    """``--track-iou``: one number in (0, 1], a whole number of thousandths.  Returns it as a float; ValueError otherwise."""
+    s = str(s).strip()
+    try:
+        v = float(s)
+    except ValueError:
+        raise ValueError(f"--track-iou {s!r}: expected one number in (0, 1]") from None
+    try:
+        return _track_milli(v) / 1000
+    except ValueError as e:
+        raise ValueError(f"--track-iou {s!r}: {e}") from None
+
+
+def natural_order(stems):
+    """Indices that sort the names with every run of digits compared as a number (frame2 before frame10); names that compare equal
+    that way (frame01, frame1) are ordered as plain strings."""
+    stems = [str(s) for s in stems]
+
+    def key(i):
+        pieces = re.split(r"(\d+)", stems[i])
+        return [(0, int(p), "") if k % 2 else (1, 0, p) for k, p in enumerate(pieces) if p != ""], stems[i]
+
+    return sorted(range(len(stems)), key=key)
+
+
+def length_hist(lengths):
+    """The table's length column (tensor on any device, or array; zero rows are no tracks) -> the 7 counts of LENGTH_BINS, int64 on
+    the column's device (torch) or the host (numpy)."""
+    if isinstance(lengths, torch.Tensor):
+        v = lengths.reshape(-1).to(torch.int64)
+        v = v[v > 0]
+        bins = torch.bucketize(v, torch.tensor([1, 2, 4, 8, 16, 32], dtype=torch.int64, device=v.device))
+        return torch.bincount(bins, minlength=len(LENGTH_BINS))
+    v = np.asarray(lengths).reshape(-1).astype(np.int64)
+    v = v[v > 0]
+    return np.bincount(np.searchsorted(np.array([1, 2, 4, 8, 16, 32]), v, side="left"), minlength=len(LENGTH_BINS))
+
+
+def track_report(totals, lengths, inter_sum=0, union_sum=0, untracked=0):
+    """One side of eval_tracks.json / tracks.json.  totals: (tracks, links, objects, longest) of ``track``; lengths: the table's length
+    column (a tensor is binned where it is and only the 7 counts come to the host); inter_sum, union_sum: the sums of those columns;
+    untracked: objects numbered above max_objects.  {"objects", "untracked_objects", "tracks", "links", "singletons", "mean_length":
+    objects / tracks, "max_length", "length_hist": {"1", "2", "3-4", "5-8", "9-16", "17-32", "33+"}, "link_iou": inter_sum / union_sum};
+    a ratio with a zero denominator is None."""
+    n_tracks, n_links, n_objects, longest = (int(v) for v in _host(totals).reshape(-1))
+    hist = [int(v) for v in _host(length_hist(lengths))]
+    inter_sum, union_sum, untracked = int(inter_sum), int(union_sum), int(untracked)
+    if min(n_tracks, n_links, n_objects, longest, inter_sum, union_sum, untracked) < 0 or n_tracks + n_links != n_objects:
+        raise ValueError(f"{n_tracks} tracks and {n_links} links do not make {n_objects} objects")
+    if sum(hist) != n_tracks:
+        raise ValueError(f"the length column holds {sum(hist)} tracks, the totals say {n_tracks}")
+    ratio = lambda a, b: a / b if b else None
+    return {"objects": n_objects, "untracked_objects": untracked, "tracks": n_tracks, "links": n_links, "singletons": hist[0],
+            "mean_length": ratio(n_objects, n_tracks), "max_length": longest, "length_hist": dict(zip(LENGTH_BINS, hist)),
+            "link_iou": ratio(inter_sum, union_sum)}
+
+
+def track_rows(table, n_tracks):
+    """table [max_tracks,8] (tensor or array) -> the first min(n_tracks, max_tracks) tracks as {"track", "first_frame", "first_label",
+    "length", "area_sum", "area_min", "area_max", "inter_sum", "union_sum", "link_iou": inter_sum / union_sum (None for a singleton)}."""
+    table = _host(table)
+    if table.ndim != 2 or table.shape[1] != len(TRACK_FIELDS):
+        raise ValueError(f"table {table.shape} must be [max_tracks, {len(TRACK_FIELDS)}]")
+    n_tracks = int(n_tracks)
+    if n_tracks < 0:
+        raise ValueError(f"n_tracks must not be negative, got {n_tracks}")
+    rows = []
+    for t in range(min(n_tracks, table.shape[0])):
+        row = {"track": t + 1, **{k: int(v) for k, v in zip(TRACK_FIELDS, table[t])}}
+        row["link_iou"] = row["inter_sum"] / row["union_sum"] if row["union_sum"] else None
+        rows.append(row)
+    return rows
+
+
 def parse_match_iou(s):
     """``"0.5-0.75-0.95"`` (dash-separated) or ``"lo:hi:n"`` (np.linspace(lo, hi, n) in float64), as --thresh-grid is written.  Returns
     the thresholds as floats, whole thousandths (0.5:0.95:10 gives exactly 0.5, 0.55, ..., 0.95); ValueError as ``iou_milli``."""

@@ -879,6 +879,51 @@ enum { CGS_OBJ_MATCH_MAX_OBJECTS = 64, CGS_OBJ_MATCH_MAX_IOU = 16 };
 int cgs_objects_match(const int32_t* pred, const int32_t* truth, int32_t n, int32_t h, int32_t w, int32_t max_objects,
                       const int32_t* iou_milli, int32_t T, int32_t* counts, int32_t* best, cgs_stream_t stream);
 
+/* ---- from objects to tracks (csrc/objects_track.hip; this build's own -objects --track-iou, no counterpart in the reference) ------------
+ * Objects of one label stack followed from frame to frame.  All integer and deterministic: the only global atomics are integer add /
+ * min / max, so every output is bit-reproducible.
+ *   labels   int32 [n][h][w] (contiguous) as cgs_objects_label writes it; hand-made maps allowed.  An object of frame f is a label l in
+ *            1..K (K = max_objects) with at least one pixel in frame f; labels above K and labels <= 0 take no part.
+ *   link     object p of frame f and object q of frame f + 1 are linked at iou_milli = m (1..1000) when q is p's best partner in f + 1,
+ *            p is q's best partner in f ("best" is cgs_objects_match's `best`: largest IoU by cross-multiplication, ties to the smallest
+ *            number) and inter > 0 && 1000 inter >= m (area_p + area_q - inter) in int32.  Mutual best makes links one-to-one, so
+ *            thresholds below 500 are allowed here.
+ *   track    a maximal chain of links: consecutive frames, one object per frame.  An object with no link backwards is a head; tracks
+ *            are numbered 1..N in the order of their heads, by frame, then by label within the frame.
+ *   prev     int32 [n][K]: prev[f][l-1] is the label in frame f - 1 that object l continues; 0 for a head, for f = 0, for no object
+ *   track    int32 [n][K]: the object's track number, 0 for a row that is no object (numbers above max_tracks are still handed out)
+ *   totals   int32 [4]: tracks N, links, objects, the longest track's length
+ *   tracks   int32 [max_tracks][8] or NULL: row t-1 is track t: first_frame, first_label, length, area_sum, area_min, area_max,
+ *            inter_sum, union_sum (the last two over the track's links); rows from min(N, max_tracks) on are zero
+ *   track_labels  int32 [n][h][w] or NULL: per pixel the track number of the pixel's object, 0 for background and labels above K
+ *   rgb      uint8 [n][h][w][3] or NULL: black where track_labels is 0, else with hsh = (uint32) track * 2654435761u channel c is
+ *            64 + ((hsh >> 8 c) & 255) * 191 / 255 (integer division): never black
+ *   scratch  caller-owned, 8-byte aligned, at least cgs_objects_track_scratch_bytes(n, max_objects) bytes (0 for n or max_objects
+ *            < 1); holds nothing between calls
+ * The pairs are cgs_objects_match on (labels, labels + h w) with n - 1 frames plus one self-pair of the last frame for its areas; the
+ * chains are resolved by pointer doubling, ceil(log2(n - 1)) rounds.  Runs on `stream` without synchronising, allocates nothing, can
+ * be captured in a graph; the number of launches depends on n only.  labels, prev, track, totals, scratch not NULL, n, h, w,
+ * max_objects, max_tracks >= 1, 1 <= iou_milli <= 1000, int32 pointers 4-byte and scratch 8-byte aligned, scratch_bytes large enough,
+ * else CGS_ERR_BADARG (nothing is launched); then h, w <= 64, max_objects <= 64 and n <= CGS_OBJ_TRACK_MAX_FRAMES (which keeps
+ * area_sum and union_sum inside int32: 8191 * 2^17 < 2^31), else CGS_ERR_UNSUPPORTED.
+ *
+ * cgs_objects_track_switches: identity switches of a prediction's tracks against the truth's.  truth_prev int32 [n][K] (`prev` of the
+ * truth stack), pred_track int32 [n][K] (`track` of the predicted stack), match_best int32 [n][2][K][4] = cgs_objects_match(pred,
+ * truth)'s `best` (its side 1 rows give each truth object's best predicted object), iou_milli int32 [T] on the device, 1 <= T <= 16.
+ * counts int32 [T][3], zeroed by the entry itself on the stream, per threshold m: covered = truth objects whose best pair reaches m;
+ * continued = truth links q' -> q (frames f - 1, f) with both ends covered; switches = those continued links whose two predicted
+ * partners carry different pred_track numbers.  Gaps are NOT bridged: a truth object that is uncovered for a frame ends the
+ * comparison there, and the next covered frame starts afresh.  Same K for all three inputs.  NULL or misaligned pointers, T outside
+ * 1..16, n or max_objects < 1: CGS_ERR_BADARG; then max_objects > 64 or n > CGS_OBJ_TRACK_MAX_FRAMES: CGS_ERR_UNSUPPORTED.            */
+enum { CGS_OBJ_TRACK_FIELDS = 8, CGS_OBJ_TRACK_MAX_FRAMES = 1 << 17 };
+int64_t cgs_objects_track_scratch_bytes(int32_t n, int32_t max_objects);
+int cgs_objects_track(const int32_t* labels, int32_t n, int32_t h, int32_t w, int32_t max_objects, int32_t iou_milli,
+                      int32_t max_tracks, int32_t* prev, int32_t* track, int32_t* totals, int32_t* tracks, int32_t* track_labels,
+                      uint8_t* rgb, void* scratch, int64_t scratch_bytes, cgs_stream_t stream);
+int cgs_objects_track_switches(const int32_t* truth_prev, const int32_t* pred_track, const int32_t* match_best,
+                               const int32_t* iou_milli, int32_t T, int32_t n, int32_t max_objects, int32_t* counts,
+                               cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
