@@ -25,6 +25,9 @@ def build_parser():
     # main.py:1226-1263 is written as.  Both leave {model}/eval_sweep.json
     p.add_argument("--thresh-grid", type=str, default="")
     p.add_argument("--crf-grid", type=str, default="")
+    # (this build's own flag) -eval -salience --salience-grid "0.25-0.5-0.75" or "lo:hi:n": the saliency baseline thresholded at every
+    # value, each with its own normaliser (--salience-thresh is both), scored on the GPU (saliency.py); adds "saliency" to eval_sweep.json
+    p.add_argument("--salience-grid", type=str, default="")
     # (this build's own flags) -objects: the masks of -process / -eval labelled into connected components on the GPU (objects.py),
     # components below --min-area pixels removed.  -process leaves objects.json and {stem}-objects-mask.png, -eval eval_objects.json.
     # The two options default to 1 and 8 (filled in by check_objects_flags, which has to see whether they were given)
@@ -96,7 +99,7 @@ def parse_args(argv=None):
 
 
 def check_sweep_flags(args):
-    """--thresh-grid / --crf-grid: malformed grids and combinations that could not run are refused here, before any GPU work."""
+    """--thresh-grid / --crf-grid / --salience-grid: malformed grids and combinations that could not run are refused here, before any GPU work."""
     if args.thresh_grid:
         from .metrics import parse_thresh_grid
         parse_thresh_grid(args.thresh_grid)
@@ -109,6 +112,16 @@ def check_sweep_flags(args):
             raise ValueError("--crf-grid scores every point against the labels of -eval; -process has none")
         if not (args.crf and args.eval):
             raise ValueError("--crf-grid is the parameter grid of -eval -crf: give both (-test switches -crf off)")
+    if args.salience_grid:
+        from .saliency import frame_k, parse_salience_grid, PIXELS
+        thr = parse_salience_grid(args.salience_grid)
+        if args.process:
+            raise ValueError("--salience-grid scores every threshold against the labels of -eval; -process has none")
+        if not (args.eval and args.salience):
+            raise ValueError("--salience-grid sweeps the saliency baseline of -eval -salience: give both (or -test)")
+        if not args.salglobal and (frame_k(thr) > PIXELS - 1).any():
+            raise ValueError(f"--salience-grid {args.salience_grid!r}: with -salglobal '' a threshold t picks each map's int({PIXELS} * t)-th "
+                             "smallest value: every t must be below 1")
 
 
 def check_objects_flags(args):

@@ -20,7 +20,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, dataformat, metrics, objects, parallel, sheets, video, vis
+from . import _lib, dataformat, metrics, objects, parallel, saliency, sheets, video, vis
 from .crf import GRID_KEYS, dense_crf, grid_points, parse_crf_grid
 from .engine import HourglassEngine
 from .generic_engine import GenericEngine
@@ -75,7 +75,7 @@ class Handler:
         self.save_paths = {name: f"{self.save_path}{name}-{tag}.pt"
                            for name, tag in ((self.criticname, self.critic_args), (self.maskername, self.masker_args))}
         self._engines = {}
-        self.crf_reports, self.sweep = [], None      # --crf-grid / --thresh-grid: the tables of Handler.crf, the dict of eval_sweep.json
+        self.crf_reports, self.sweep = [], None      # --crf-grid / --thresh-grid / --salience-grid: the tables of Handler.crf, the dict of eval_sweep.json
         self.objects = None         # -eval -objects: the dict of eval_objects.json
         self.matches = None         # -eval -objects --match-iou: the dict of eval_match.json
         self.tracks = None          # -eval -objects --track-iou: the dict of eval_tracks.json
@@ -643,6 +643,17 @@ class Handler:
         out = np.minimum(salM / (scale + tiny) * preds.reshape(-1, 1, 1, 1), 1.0)
         return out, (out > thresh).astype(np.uint8)
 
+    def _saliency_sweep(self, salM, preds, truth, thr):
+        """--salience-grid: _saliency_post's hard mask at every threshold of thr (float64), each with its own normaliser, scored against
+        truth on the GPU (saliency.sweep): the maps, the predictions and the truth are uploaded once and 2 T counts come back.  The global
+        mode's mean is numpy's, of the host copy, so every row is what _saliency_post and get_iou's counts give at that threshold."""
+        glob = bool(self.args.salglobal)
+        to_dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
+        mean = np.where(salM >= 0, salM, 0.0).mean() if glob else None
+        inter, union, _scale = saliency.sweep(to_dev(salM[:, 0], np.float32), to_dev(preds, np.float32), to_dev(truth, bool), thr, glob, mean=mean)
+        rep = saliency.sweep_report(thr, inter.cpu().numpy(), union.cpu().numpy(), np.count_nonzero(truth), salglobal=glob)
+        return {"mode": "global" if glob else "frame", **rep}
+
     # ------------------------------------------------------------------ -crf: dense-CRF refinement of mask stacks
     def crf(self, imgs, mask, Y, skip=1):
         """main.py:1226-1263: every `skip`-th frame's mask [n,1,h,w] (P of label 1) refined by the two-label dense CRF, the whole stack in
@@ -732,7 +743,8 @@ class Handler:
         ious = [self.get_iou(hard_m, truth)]
         thresh_grid, crf_grid = getattr(args, "thresh_grid", ""), getattr(args, "crf_grid", "")
         sweep, n_reports = {}, len(self.crf_reports)
-        if thresh_grid:       # (this build's flag) the mask threshold only: the saliency threshold is also _saliency_post's normaliser
+        if thresh_grid:       # (this build's flag) the mask threshold only; the saliency threshold, which is also _saliency_post's
+            # normaliser, has a sweep of its own that renormalises per threshold: --salience-grid below
             thr = metrics.parse_thresh_grid(thresh_grid)
             inter, union = metrics.iou_curve(torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device),
                                              torch.from_numpy(np.ascontiguousarray(truth)).to(self.device), thr)    # strict >, main.py:964
@@ -746,6 +758,11 @@ class Handler:
         if want_sal:
             maps, sal_hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
             ious.append(self.get_iou(sal_hard[:, 0], truth))
+            if getattr(args, "salience_grid", ""):      # (this build's flag) the baseline at every threshold, renormalised, on the GPU
+                sweep["saliency"] = self._saliency_sweep(sal, preds, truth, saliency.parse_salience_grid(args.salience_grid))
+                b = sweep["saliency"]["best"]
+                print(f"\nSALIENCY SWEEP {len(sweep['saliency']['rows'])} thresholds ({sweep['saliency']['mode']}), best {b['thresh']:.6g} "
+                      f"(index {b['index']}) iou {b['iou']:.6f}")
             if args.crf:                                                  # main.py:1000-1003
                 sal_crf = self.crf(frames, maps, truth)[:, 0]
                 ious.append(self.get_iou(sal_crf, truth))

@@ -89,30 +89,35 @@ def iou_counts(labels, truth):
 
 
 # ---------------------------------------------------------------------------------------------------------------- host helpers
-def parse_thresh_grid(s):
-    """``"0.01-0.05-0.5"`` (the reference's dash-separated floats, main.py:974) or ``"lo:hi:n"`` (np.linspace(lo, hi, n) in float64).
-    Returns float32 [T], 1 <= T <= 1024, in the order given."""
+def parse_grid_values(s, flag):
+    """The syntax shared by ``--thresh-grid`` and ``--salience-grid``: dash-separated floats or ``lo:hi:n`` (np.linspace(lo, hi, n)).
+    Returns the values as float64 in the order given; ``flag`` names the option in the error."""
     s = str(s).strip()
     try:
         if ":" in s:
             lo, hi, n = s.split(":")
             if int(n) < 1:
                 raise ValueError
-            vals = np.linspace(float(lo), float(hi), int(n), dtype=np.float64)
-        else:
-            # a dash separates; a dash after the start, after another dash or after an exponent's e is a sign ("-0.1-0.5", "1e-3-0.5")
-            parts, cur = [], ""
-            for ch in s:
-                if ch == "-" and cur and cur[-1] not in "eE-":
-                    parts.append(cur)
-                    cur = ""
-                else:
-                    cur += ch
-            parts.append(cur)
-            vals = np.array([float(p) for p in parts], dtype=np.float64)
+            return np.linspace(float(lo), float(hi), int(n), dtype=np.float64)
+        # a dash separates; a dash after the start, after another dash or after an exponent's e is a sign ("-0.1-0.5", "1e-3-0.5")
+        parts, cur = [], ""
+        for ch in s:
+            if ch == "-" and cur and cur[-1] not in "eE-":
+                parts.append(cur)
+                cur = ""
+            else:
+                cur += ch
+        parts.append(cur)
+        return np.array([float(p) for p in parts], dtype=np.float64)
     except ValueError:
-        raise ValueError(f"--thresh-grid {s!r}: expected dash-separated numbers (0.01-0.05-0.5) or lo:hi:n") from None
-    thr = vals.astype(np.float32)
+        raise ValueError(f"{flag} {s!r}: expected dash-separated numbers (0.01-0.05-0.5) or lo:hi:n") from None
+
+
+def parse_thresh_grid(s):
+    """``"0.01-0.05-0.5"`` (the reference's dash-separated floats, main.py:974) or ``"lo:hi:n"`` (np.linspace(lo, hi, n) in float64).
+    Returns float32 [T], 1 <= T <= 1024, in the order given."""
+    s = str(s).strip()
+    thr = parse_grid_values(s, "--thresh-grid").astype(np.float32)
     if not 1 <= thr.size <= MAX_THRESHOLDS:
         raise ValueError(f"--thresh-grid {s!r}: 1 to {MAX_THRESHOLDS} thresholds, got {thr.size}")
     if np.isnan(thr).any():

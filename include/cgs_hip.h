@@ -924,6 +924,33 @@ int cgs_objects_track_switches(const int32_t* truth_prev, const int32_t* pred_tr
                                const int32_t* iou_milli, int32_t T, int32_t n, int32_t max_objects, int32_t* counts,
                                cgs_stream_t stream);
 
+/* ---- the saliency baseline over a threshold grid (csrc/saliency.hip; Handler._saliency_post, main.py:976-1003; this build's own
+ * -eval -salience --salience-grid) -----------------------------------------------------------------------------------------------------
+ * The baseline's whole post-processing for T thresholds at once, each threshold with its own normaliser as the host form has it.  A
+ * pixel of frame f is on at thr[t] when, in float64 with IEEE division and multiplication (no contraction, no fast-math),
+ *     min((double) sal / ((double) S + DBL_MIN) * (double) preds[f], 1.0) > thr[t]
+ * which numpy 2 evaluates for Handler._saliency_post; the on/off decision, and so every count, is that form's bit for bit.
+ *   sal     fp32 [n][64][64]: non-negative or NaN (-0.0 counts as 0); a NaN pixel is on for nothing
+ *   preds   fp32 [n]; a frame with preds <= 0 or NaN is on for nothing
+ *   truth   uint8 [n][64][64] (non-zero = set) or NULL: then counts is not written
+ *   thr     fp64 [T] in DEVICE memory, any order, > 0 (a threshold >= 1 switches everything off; one <= 0 gives unspecified counts)
+ *   gscale  fp32 [T] in device memory or NULL.  Not NULL: global mode, S = gscale[t] for every frame (the caller builds
+ *           float32(mean * float32(t))).  NULL: per-frame mode, S = the frame's k[t]-th smallest value with NaN sorted last (np.sort)
+ *   k       int32 [T] in device memory, read in per-frame mode only, 0..4095 (clamped to that range)
+ *   which   index of the threshold whose mask goes to `hard`, or -1 for none
+ *   counts  int64 [T][2], zeroed by the entry itself on the stream: (#{truth and on_t}, #{truth or on_t}) over the stack, in the
+ *           caller's threshold order; the frames add to it with integer atomics, so the result does not depend on their order
+ *   scale   fp32 [n][T]: the S used for each frame and threshold (a NaN comes back as the quiet NaN)
+ *   hard    uint8 [n][64][64], 0 / 1, or NULL when which is -1
+ * One workgroup per frame: its 4096 values sorted once in LDS with the truth bit riding along, a prefix count of the truth in sorted
+ * order, and per threshold a binary search over the sorted positions that evaluates the predicate above at every probe (for preds > 0
+ * it is monotone in sal).  Runs on `stream` without synchronising, allocates nothing, can be captured in a graph.
+ * 1 <= T <= 1024, n >= 1, h, w >= 1, -1 <= which < T, the pointers above not NULL, fp32 / int32 / hard 4-byte and thr / counts 8-byte
+ * aligned, else CGS_ERR_BADARG; then h = w = 64, else CGS_ERR_UNSUPPORTED.  The checks come before anything is launched.              */
+int cgs_saliency_sweep(const float* sal, const float* preds, const uint8_t* truth, const double* thr, const float* gscale,
+                       const int32_t* k, int32_t T, int32_t n, int32_t h, int32_t w, int32_t which, int64_t* counts, float* scale,
+                       uint8_t* hard, cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
