@@ -65,6 +65,7 @@ OBJ_U8, OBJ_F32_GT, OBJ_F32_GE, OBJ_FIELDS, OBJ_MAX_SIDE = 0, 1, 2, 8, 64       
 OBJ_MATCH_MAX_OBJECTS, OBJ_MATCH_MAX_IOU = 64, 16                               # cgs_objects_match (include/cgs_hip.h)
 OBJ_TRACK_FIELDS, OBJ_TRACK_MAX_FRAMES = 8, 1 << 17                             # cgs_objects_track (include/cgs_hip.h)
 SALIENCY_SIDE, SALIENCY_MAX_T = 64, 1024                                        # cgs_saliency_sweep (include/cgs_hip.h)
+BOUNDARY_MAX_TOL, BOUNDARY_MAX_TOL_PX = 16, 128                                 # cgs_boundary_score (include/cgs_hip.h)
 
 
 class ReduceJob(C.Structure):
@@ -218,6 +219,7 @@ SIGNATURES = {
     "cgs_objects_track": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "cgs_objects_track_switches": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "cgs_saliency_sweep": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "cgs_boundary_score": (i32, [vp, i32, f32, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
     "cgs_build_arch": (C.c_char_p, []),
     "cgs_abi_version": (i32, []),
 }

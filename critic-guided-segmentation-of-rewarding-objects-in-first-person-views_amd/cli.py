@@ -40,6 +40,10 @@ def build_parser():
     # (this build's own flag) -objects --track-iou T with -process or -eval: the objects followed from frame to frame on the GPU
     # (objects.track); leaves {model}/eval_tracks.json, or {R}/tracks.json and {R}/{stem}-tracks-mask.png
     p.add_argument("--track-iou", type=str, default="")
+    # (this build's own flag) -eval --boundary-tol "0-1-2-3" or "lo:hi:n": every evaluated stack's outline against the truth's outline at
+    # these tolerances in pixels -- boundary F, boundary IoU and the Hausdorff distance -- on the GPU (boundary.score); leaves
+    # {model}/eval_boundary.json
+    p.add_argument("--boundary-tol", type=str, default="")
     for flag in ("-masker", "-critic", "-cload", "-mload", "-staticnorm", "-visbesteval", "-salglobal"):
         p.add_argument(flag, type=bool, default=True)
     p.add_argument("--salience-thresh", type=float, default="1.5")
@@ -125,8 +129,9 @@ def check_sweep_flags(args):
 
 
 def check_objects_flags(args):
-    """-objects / --min-area / --connectivity / --match-iou / --track-iou: combinations that could not run and a malformed --match-iou
-    or --track-iou are refused here, before any GPU work; the defaults (--min-area 1, --connectivity 8) are filled in."""
+    """-objects / --min-area / --connectivity / --match-iou / --track-iou / --boundary-tol: combinations that could not run and a
+    malformed --match-iou, --track-iou or --boundary-tol are refused here, before any GPU work; the defaults (--min-area 1,
+    --connectivity 8) are filled in.  --boundary-tol needs -eval, not -objects."""
     given = [f for f, v in (("--min-area", args.min_area), ("--connectivity", args.connectivity)) if v is not None]
     if args.match_iou:
         from .objects import parse_match_iou
@@ -136,6 +141,11 @@ def check_objects_flags(args):
             raise ValueError("--match-iou matches the objects against the labels of -eval; -process has none")
         if args.objects and not args.eval:
             raise ValueError("--match-iou belongs to -eval -objects: give -eval (or -test)")
+    if args.boundary_tol:
+        from .boundary import parse_boundary_tol
+        parse_boundary_tol(args.boundary_tol)
+        if not args.eval:
+            raise ValueError("--boundary-tol scores the outlines against the labels of -eval: give -eval (or -test)")
     if args.track_iou:
         from .objects import parse_track_iou
         given.append("--track-iou")

@@ -20,7 +20,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, dataformat, metrics, objects, parallel, saliency, sheets, video, vis
+from . import _lib, boundary, dataformat, metrics, objects, parallel, saliency, sheets, video, vis
 from .crf import GRID_KEYS, dense_crf, grid_points, parse_crf_grid
 from .engine import HourglassEngine
 from .generic_engine import GenericEngine
@@ -79,6 +79,7 @@ class Handler:
         self.objects = None         # -eval -objects: the dict of eval_objects.json
         self.matches = None         # -eval -objects --match-iou: the dict of eval_match.json
         self.tracks = None          # -eval -objects --track-iou: the dict of eval_tracks.json
+        self.boundary = None        # -eval --boundary-tol: the dict of eval_boundary.json
         self._trace = None          # tests set a dict of lists (Handler.start_trace): per-step indices / losses of the two training loops
 
     def start_trace(self):
@@ -605,6 +606,12 @@ class Handler:
         return objects.match_report(m.pred_max, m.truth_max, m.matched_pred, m.matched_truth, objects.sum_iou(m.best, iou), iou,
                                     max_objects=self.MATCH_MAX_OBJECTS)
 
+    def _eval_boundary(self, src, truth, tol, thresh=None):
+        """One block of eval_boundary.json: the stack `src` (as _eval_objects takes it) scored against the truth's outline on the GPU
+        (boundary.score); only the per-frame counts come back."""
+        b = boundary.score(src, truth, tol=tol, thresh=thresh)
+        return boundary.boundary_report(*(t.cpu().numpy() for t in b[:8]), tol)
+
     def _sweep_masks(self, X, to_device, progress, want_saliency=False, fp16=False, batchsize=128, train_mode=None):
         """The inference loop shared by -process and -eval (main.py:1130-1151, 900-953): eval-mode critic + masker over X in batches
         of 128, optionally the saliency baseline |d mean(pred) / d batch| summed over the colour channels.
@@ -839,6 +846,33 @@ class Handler:
                 print(f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g}: {p['tracks']} tracks over {p['objects']} "
                       f"objects, mean length {fmt(p['mean_length'])}, longest {p['max_length']}; truth {truth_side['tracks']} tracks over "
                       f"{truth_side['objects']} objects")
+        if getattr(args, "boundary_tol", ""):   # (this build's flag) the outlines against the truth's outline, scored on the GPU
+            tol = boundary.parse_boundary_tol(args.boundary_tol)
+            dev_truth = torch.from_numpy(np.ascontiguousarray(truth)).to(self.device)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            stacks = [("mask", up(M[:, 0].astype(np.float32, copy=False)), float(args.eval_thresh))]      # strict >, main.py:964
+            if args.crf:
+                stacks.append(("crf", up(crf_m), None))
+            if want_sal:
+                stacks.append(("saliency", up(sal_hard[:, 0]), None))
+                if args.crf:
+                    stacks.append(("saliency_crf", up(sal_crf), None))
+            if getattr(args, "objects", False):                           # the mask eval_objects.json scores: small objects removed
+                kept = objects.label(stacks[0][1], thresh=stacks[0][2], connectivity=args.connectivity, min_area=args.min_area,
+                                     want_labels=False, want_mask=True).mask
+                stacks.append(("mask_objects", kept, None))
+            outlines = {"tol": tol, "tol2": boundary.tol_squared(tol), "threshold": float(args.eval_thresh)}
+            for name, src, thr in stacks:
+                outlines[name] = self._eval_boundary(src, dev_truth, tol, thresh=thr)
+            self.boundary = outlines = _json_safe(outlines)
+            if self.rank == 0:
+                os.makedirs(self.path, exist_ok=True)
+                with open(self.path + "eval_boundary.json", "w") as fp:
+                    json.dump(outlines, fp, indent=1)
+            fmt = lambda v: "nan" if v is None else f"{v:.6f}"
+            print(f"\nBOUNDARY tol={tol[0]:g} ({len(tol)} tolerances): " + "; ".join(
+                f"{name} f {fmt(outlines[name]['per_tol'][0]['f'])} boundary_iou {fmt(outlines[name]['per_tol'][0]['boundary_iou'])}"
+                for name, _src, _thr in stacks))
         print("\nRESULTS", ious)
         if vid is not None and self.rank == 0 and ious[0] > self.ious[0]:          # main.py:1027
             layout, exe = vid

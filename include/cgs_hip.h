@@ -951,6 +951,32 @@ int cgs_saliency_sweep(const float* sal, const float* preds, const uint8_t* trut
                        const int32_t* k, int32_t T, int32_t n, int32_t h, int32_t w, int32_t which, int64_t* counts, float* scale,
                        uint8_t* hard, cgs_stream_t stream);
 
+/* ---- boundary F and boundary IoU (csrc/boundary.hip; this build's own -eval --boundary-tol, no counterpart in the reference) ---------------
+ * How well a mask's outline follows the truth's: per frame the two boundaries, the exact squared Euclidean distance from every pixel to
+ * each, and the counts of the boundary F-measure, of boundary IoU (Cheng et al.) and of the Hausdorff distance.  One workgroup per
+ * frame in LDS, integer throughout, no atomics: deterministic, bit for bit.
+ *   pred      [n][h][w] (contiguous); pred_kind and thresh say when a pixel is on, exactly as cgs_objects_label's src_kind: CGS_OBJ_U8
+ *             (a bool stack is this), CGS_OBJ_F32_GT, CGS_OBJ_F32_GE; compared in fp32, a NaN is off
+ *   truth     uint8 [n][h][w], non-zero = on
+ *   boundary  a pixel is a boundary pixel of a mask when it is on and at least one of its four neighbours is off; everything outside
+ *             the frame is off, so a mask cut by the frame edge has its boundary there (the inner boundary of the boundary-IoU code,
+ *             not a half-pixel map)
+ *   tol2      int32 [T] in DEVICE memory: squared tolerances q, any order; a pixel is within tolerance when d2 <= q.  Values above
+ *             2 x 63^2 act as "any distance", negative ones as "none"
+ *   counts    int32 [n][4 + 4 T]: pred_px, truth_px (boundary pixels), hd2_pred (the largest squared distance from a predicted boundary
+ *             pixel to the truth boundary), hd2_truth (the other way round; both -1 when either boundary is empty), then per tolerance
+ *             k at 4 + 4 k: hit_pred (predicted boundary pixels with d2_truth <= q), hit_truth, band_inter = #(P_q & G_q), band_union =
+ *             #(P_q | G_q) with P_q the on pixels of pred with d2_pred <= q and G_q the same for the truth.  An empty boundary gives
+ *             that side's band as empty and the other side no hits
+ *   dist2     int32 [n][2][h][w] or NULL: the squared distance of every pixel to the predicted (plane 0) and the truth boundary
+ *             (plane 1); -1 throughout a plane whose boundary is empty
+ * Runs on `stream` without synchronising, allocates nothing, can be captured in a graph.  pred, truth, tol2, counts not NULL, n, h, w
+ * >= 1, a valid pred_kind, 1 <= T <= CGS_BOUNDARY_MAX_TOL, fp32 pred / tol2 / counts / dist2 4-byte aligned, else CGS_ERR_BADARG
+ * (nothing is launched); then h, w <= 64, else CGS_ERR_UNSUPPORTED.                                                                    */
+enum { CGS_BOUNDARY_MAX_TOL = 16, CGS_BOUNDARY_MAX_TOL_PX = 128 };
+int cgs_boundary_score(const void* pred, int32_t pred_kind, float thresh, const uint8_t* truth, int32_t n, int32_t h, int32_t w,
+                       const int32_t* tol2, int32_t T, int32_t* counts, int32_t* dist2, cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
