@@ -10,14 +10,20 @@ __device__ __forceinline__ void unpack12(uint32_t d0, uint32_t d1, uint32_t d2, 
     v[8] = (d2 & 255) * s; v[9] = ((d2 >> 8) & 255) * s; v[10] = ((d2 >> 16) & 255) * s; v[11] = (d2 >> 24) * s;
 }
 
-// one thread = 4 pixels (12 bytes of A and of B, one float4 of Z, 3 float4 of each mix); grid-stride.
-// Each workgroup writes its partial (sum |Z|, sum Z^2) to zpart[2*block .. 2*block+1]: no float atomics.
-__global__ void __launch_bounds__(256) mix_fwd_kernel(int groups, int rep_groups, const uint32_t* __restrict__ a,
-                                                      const uint32_t* __restrict__ b, const float4* __restrict__ z,
-                                                      int inject, float4* __restrict__ mixed, float* __restrict__ zpart) {
+// one thread = 4 pixels (12 bytes of A and of B, one float4 of Z, 3 float4 of each mix).  A workgroup belongs to ONE image: image i has
+// wg_per_img workgroups (i * wg_per_img ...), each striding over its contiguous share of `share` pixel groups of that image.
+// Each workgroup writes its partial (sum |Z|, sum Z^2) to zpart[2*block .. 2*block+1]: no float atomics, and partial p covers only pixels
+// of image p / wg_per_img at every n -- phase2_losses_kernel / phase2_loss_values weight it by that image's 1 - pred (flag bit 8).
+__global__ void __launch_bounds__(256) mix_fwd_kernel(int groups_per_img, int wg_per_img, int share, int rep_groups,
+                                                      const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                      const float4* __restrict__ z, int inject, float4* __restrict__ mixed,
+                                                      float* __restrict__ zpart) {
     __shared__ float red[2][4];
     float s1 = 0.f, s2 = 0.f;
-    for (int g = blockIdx.x * 256 + threadIdx.x; g < groups; g += gridDim.x * 256) {
+    const int img = blockIdx.x / wg_per_img, lo = (blockIdx.x % wg_per_img) * share;
+    const int hi = min(lo + share, groups_per_img);
+    for (int gi = lo + threadIdx.x; gi < hi; gi += 256) {
+        const int g = img * groups_per_img + gi;
         float4 zz = z[g];
         float zv[4] = {zz.x, zz.y, zz.z, zz.w};
         if (!mixed) {       // partial sums only: the consumers form the mixes themselves (cgs_bf16_enc0_fwd_mix / cgs_bf16_hwgrad_pooled_mix)
@@ -287,19 +293,25 @@ __global__ void __launch_bounds__(256) dropout_mask_kernel(long count4, cgs_drop
 }
 
 // ------------------------------------------------------------------------------------------------
-static int mix_blocks(int groups) { int b = (groups + 255) / 256; return b < 1024 ? b : 1024; }
+// workgroups per image: one per 256 pixel groups, fewer once n of them would pass 1024 workgroups in all (never less than one:
+// the partial sums stay per image).  Up to 256 images of 64x64 (64 of 128x128) that is one group per thread.
+static int mix_wg_per_img(int n, int groups_per_img) {
+    int k = (groups_per_img + 255) / 256, cap = n > 0 ? 1024 / n : 1024;
+    if (cap < 1) cap = 1;
+    return k < cap ? k : cap;
+}
 
 extern "C" int cgs_mix_fwd_partials(int32_t n, int32_t hw) {
     if (n < 0 || hw <= 0 || (hw & 3)) return CGS_ERR_BADARG;
-    return mix_blocks(n * (hw / 4));
+    return n * mix_wg_per_img(n, hw / 4);
 }
 
 extern "C" int cgs_mix_fwd(int32_t n, int32_t hw, const uint8_t* a, const uint8_t* b, const float* z, int32_t inject,
                            float* mixed, float* zpart, cgs_stream_t stream) {
     if (n < 0 || hw <= 0 || (hw & 3) || !z || !zpart || (mixed && (!a || !b))) return CGS_ERR_BADARG;      // mixed = NULL: only the partial sums of |Z|, Z^2
-    int groups = n * (hw / 4);
-    if (groups == 0) return CGS_OK;
-    hipLaunchKernelGGL(mix_fwd_kernel, dim3(mix_blocks(groups)), dim3(256), 0, (hipStream_t)stream, groups, groups,
+    if (n == 0) return CGS_OK;
+    const int gpi = hw / 4, k = mix_wg_per_img(n, gpi), share = (gpi + k - 1) / k;
+    hipLaunchKernelGGL(mix_fwd_kernel, dim3(n * k), dim3(256), 0, (hipStream_t)stream, gpi, k, share, n * gpi,
                        (const uint32_t*)a, (const uint32_t*)b, (const float4*)z, inject, (float4*)mixed, zpart);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
@@ -574,6 +586,7 @@ __global__ void __launch_bounds__(COLS * SL) reduce_adam_kernel(const cgs_reduce
             float g = 0.f;
 #pragma unroll
             for (int k = 0; k < SL; ++k) g += red[k][col];
+            if (j.accumulate) g = j.dst[i] + g;                    // (as reduce_slabs_kernel; uniform per workgroup)
             j.dst[i] = g;                                          // the gradient stays observable (tests, DP)
             if (A.param) {      // (NULL: data parallel -- the all-reduce of the gradient comes first, Adam is a launch of its own)
                 const size_t e = (size_t)(j.dst + i - A.grad_base);      // element of the flat buffers

@@ -499,7 +499,8 @@ int cgs_pointwise_bwd(int32_t n, int32_t ci, int32_t co, const float* x, const f
  *   rep = A(1-Z) + Z B,  inj = B(1-Z) + Z A  with A,B uint8 NHWC (/255 fused), Z [n,64,64].
  *   mixed : [2n,h,w,3] fp32 (rep images then inj images; inj skipped when inject == 0)
  *   zpart : device float[2 * cgs_mix_fwd_partials(n,hw)]: per-workgroup partial (sum |Z|, sum Z^2),
- *           summed by cgs_phase2_losses (fixed order: no float atomics).                    */
+ *           summed by cgs_phase2_losses (fixed order: no float atomics).  The count is a multiple of n and
+ *           partial i covers only pixels of image i / (count / n), at every n (flag bit 8 relies on it). */
 int cgs_mix_fwd_partials(int32_t n, int32_t hw);
 int cgs_mix_fwd(int32_t n, int32_t hw, const uint8_t* a, const uint8_t* b, const float* z,
                 int32_t inject, float* mixed, float* zpart, cgs_stream_t stream);
