@@ -381,7 +381,7 @@ extern "C" int cgs_tail_enc_fwd(int32_t n, const cgs_tail_enc_weights* w, const 
 }
 
 // cgs_tail_enc_fwd in eval mode with fp16 OPERANDS in features.6 / features.10 (fp32 accumulation, fp32 tensors in and out; BASELINE config 4:
-// the -process path with fp16 conv kernels, nets.py:176-194 in eval mode).  Dropout is not supported here: CGS_ERR_UNSUPPORTED when any p > 0.
+// the -process path with fp16 conv kernels, nets.py:176-194 in eval mode).  Eval mode only: the entry point takes no dropout descriptors.
 extern "C" int cgs_tail_enc_fwd_h16(int32_t n, const cgs_tail_enc_weights* w, const float* e1, float* e2, uint32_t* am2, float* e3,
                                     uint32_t* am3, float* e4, float* h1, float* pred, float* o4, cgs_stream_t stream) {
     if (n < 0 || !w || !e1 || !e2 || !am2 || !e3 || !am3 || !e4 || !h1 || !pred) return CGS_ERR_BADARG;
