@@ -66,6 +66,7 @@ OBJ_MATCH_MAX_OBJECTS, OBJ_MATCH_MAX_IOU = 64, 16                               
 OBJ_TRACK_FIELDS, OBJ_TRACK_MAX_FRAMES = 8, 1 << 17                             # cgs_objects_track (include/cgs_hip.h)
 SALIENCY_SIDE, SALIENCY_MAX_T = 64, 1024                                        # cgs_saliency_sweep (include/cgs_hip.h)
 BOUNDARY_MAX_TOL, BOUNDARY_MAX_TOL_PX = 16, 128                                 # cgs_boundary_score (include/cgs_hip.h)
+FIT_SIDE, FIT_MAX_SIDE, FIT_RADIUS, FIT_MAP_F32, FIT_MAP_U8 = 64, 4096, 2, 0, 1 # cgs_fit_down_u8 / cgs_fit_up_joint (include/cgs_hip.h)
 
 
 class ReduceJob(C.Structure):
@@ -220,6 +221,8 @@ SIGNATURES = {
     "cgs_objects_track_switches": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "cgs_saliency_sweep": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "cgs_boundary_score": (i32, [vp, i32, f32, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
+    "cgs_fit_down_u8": (i32, [vp, i32, i32, i32, vp, vp]),
+    "cgs_fit_up_joint": (i32, [vp, i32, vp, vp, i32, i32, i32, f32, f32, f32, i32, vp, vp, vp, vp]),
     "cgs_build_arch": (C.c_char_p, []),
     "cgs_abi_version": (i32, []),
 }

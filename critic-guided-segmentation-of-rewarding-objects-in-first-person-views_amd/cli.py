@@ -2,6 +2,7 @@
 
     python main.py -train --model DIR
     python main.py -process [-concatenated] [--binarymaskthreshold t] --model DIR --source-imgs S --mask-output-imgs R
+    python main.py -process -fit [--fit-spatial s] [--fit-range r] ...      (this build's own: frames of any one size, 64..4096 a side)
     python main.py -test --model DIR --output-video V       (evaluation sweep + the evaluation video V/iou=....mp4)
     python main.py -train -critic '' -masker '' -vismasker --model DIR      (DIR/curves.mp4, -pred-sorted.mp4, -GT-sorted.mp4)
 
@@ -44,6 +45,12 @@ def build_parser():
     # these tolerances in pixels -- boundary F, boundary IoU and the Hausdorff distance -- on the GPU (boundary.score); leaves
     # {model}/eval_boundary.json
     p.add_argument("--boundary-tol", type=str, default="")
+    # (this build's own flags) -process -fit: frames of any one size from 64 to 4096 pixels a side, shrunk to the network's 64 x 64 grid
+    # on the GPU and the masks brought back to the frame's size by joint bilateral upsampling along the frame's edges (fit.py).
+    # --fit-spatial (cells) and --fit-range (colour units of 0..255) default to 1 and 16, filled in by check_fit_flags
+    p.add_argument("-fit", action="store_true")
+    p.add_argument("--fit-spatial", type=float, default=None)
+    p.add_argument("--fit-range", type=float, default=None)
     for flag in ("-masker", "-critic", "-cload", "-mload", "-staticnorm", "-visbesteval", "-salglobal"):
         p.add_argument(flag, type=bool, default=True)
     p.add_argument("--salience-thresh", type=float, default="1.5")
@@ -99,6 +106,7 @@ def parse_args(argv=None):
         args.salience = True
     check_sweep_flags(args)
     check_objects_flags(args)
+    check_fit_flags(args)
     return args
 
 
@@ -164,6 +172,26 @@ def check_objects_flags(args):
     if args.objects and args.process and not args.binarymaskthreshold and not args.crf:
         raise ValueError("-process -objects labels the thresholded mask (or with -crf the CRF mask): --binarymaskthreshold 0 without "
                          "-crf leaves no binary mask")
+
+
+def check_fit_flags(args):
+    """-fit / --fit-spatial / --fit-range: combinations that could not run and sigmas outside the filter's range are refused here, before
+    any GPU work; the defaults (--fit-spatial 1, --fit-range 16) are filled in."""
+    given = [f for f, v in (("--fit-spatial", args.fit_spatial), ("--fit-range", args.fit_range)) if v is not None]
+    if not args.fit:
+        if given:
+            raise ValueError(f"{' / '.join(given)} belong to -fit: give -fit")
+        return
+    if not args.process:
+        raise ValueError("-fit resizes the frames of -process: give -process")
+    if args.eval:
+        raise ValueError("-fit is for -process; the data of -eval and -test is 64 x 64 .npy")
+    if args.salience or args.process_salience:
+        raise ValueError("-fit with -salience / -process_salience: upsampled saliency maps are outside this build")
+    from .fit import SIGMA_RANGE, SIGMA_SPATIAL, check_sigmas
+    args.fit_spatial, args.fit_range = check_sigmas(SIGMA_SPATIAL if args.fit_spatial is None else args.fit_spatial,
+                                                    SIGMA_RANGE if args.fit_range is None else args.fit_range,
+                                                    names=("--fit-spatial", "--fit-range"))
 
 
 def main(argv=None):

@@ -456,6 +456,8 @@ class Handler:
             raise NotImplementedError("-noevalmode together with -salience (Dropout inside the saliency backward) is not implemented")
         if args.process_salience and not args.salience:
             raise ValueError("-process_salience needs -salience (the reference collects the maps only then, main.py:1136-1147)")
+        if getattr(args, "fit", False):                 # (this build's flag) frames of any one size; everything below stays as it is
+            return self._segment_fit(folder)
         files = os.listdir(folder)
         frames = np.stack([np.array(Image.open(os.path.join(folder, f)))[..., :3] for f in files]) / 255.0     # NHWC float64 in [0,1]
         stems = [f.rsplit(".", 1)[0] for f in files if "." in f]
@@ -495,6 +497,89 @@ class Handler:
             else:
                 for kind, g in zip(kinds, grey_rgb):
                     Image.fromarray(to_u8(g[i])).save(f"{out_dir}/{stem}-{kind}.png")
+        return M
+
+    FIT_CHUNK_FRAMES, FIT_CHUNK_BYTES = 128, 256 << 20      # a chunk of -process -fit: at most so many frames and frame bytes
+
+    def _segment_fit(self, folder):
+        """-process -fit: a folder of frames of one size, 64 to 4096 pixels a side.  Per chunk of at most 128 frames and about 256 MB the
+        uint8 frames are uploaded, shrunk to 64 x 64 on the GPU (fit.down), run through the network as -process runs 64 x 64 frames (and
+        through -crf on the shrunk frames), and every column is brought back to the frame's size along the frame's edges (fit.up): the
+        mask as grey, thresholded at --binarymaskthreshold (inclusive, main.py:1164), the CRF labels thresholded at 0.5.  The files keep
+        their names and the by-position rule, at H x W; -objects and --track-iou work on the 64 x 64 masks, in the 64 x 64 grid's
+        coordinates.  Rank 0 leaves {R}/fit.json.  Returns the 64 x 64 masks [n,1,64,64] as segment does."""
+        from PIL import Image
+        from . import fit
+        args = self.args
+        files = os.listdir(folder)
+        stems = [f.rsplit(".", 1)[0] for f in files if "." in f]
+        if not files:
+            raise ValueError(f"-fit: {folder!r} holds no files")
+        size = None
+        for f in files:
+            with Image.open(os.path.join(folder, f)) as im:
+                wh = im.size
+            if size is None:
+                try:
+                    fit.check_size(wh[1], wh[0])
+                except ValueError as e:
+                    raise ValueError(f"-fit: {f}: {e}") from None
+                size = wh
+            elif wh != size:
+                raise ValueError(f"-fit: {f} is {wh[1]}x{wh[0]}, the files before it are {size[1]}x{size[0]}: a folder holds one size")
+        W, H = size
+        fp16 = bool(getattr(args, "fp16", False))
+        thr = args.binarymaskthreshold
+        self.critic.eval()
+        self.masker.eval()
+        eng = self._engine(2 * 32)
+        out_dir = args.mask_output_imgs
+        os.makedirs(out_dir, exist_ok=True)
+        kinds = ("raw-mask", "thresholded-mask", "crf-mask")
+        sig = dict(sigma_s=args.fit_spatial, sigma_r=args.fit_range)
+        step = max(1, min(self.FIT_CHUNK_FRAMES, self.FIT_CHUNK_BYTES // (3 * H * W)))
+        rgb = lambda a: np.repeat(a[:, :, None], 3, axis=2)
+        masks, crf_masks = [], []
+        # float32(k / 255.0) for the 256 byte values, rounded on the host as the plain path rounds its frames: the device's own fp32
+        # division is not correctly rounded, so low.float() / 255 would differ from it in the last bit for some k
+        unit = torch.from_numpy((np.arange(256) / 255.0).astype(np.float32)).to(self.device)
+        for lo in range(0, len(files), step):
+            print("segmentation in progress", round(lo / len(files), 2), end="%\r")
+            host = np.stack([np.array(Image.open(os.path.join(folder, f)))[..., :3] for f in files[lo:lo + step]])    # NHWC uint8
+            guide = torch.from_numpy(np.ascontiguousarray(host, dtype=np.uint8)).to(self.device)
+            low = fit.down(guide)
+            if fp16:
+                _pred, Z = eng.infer(low, fp16=True)
+            else:
+                _pred, Z = eng.infer(unit[low.long()], train_mode=bool(args.noevalmode))
+            M = Z.cpu().numpy()[:, None]
+            masks.append(M)
+            up = fit.up(Z.contiguous(), guide, low, thresh=thr if thr else None, want=("grey", "hard") if thr else ("grey",), **sig)
+            cols = [up.grey.cpu().numpy()]
+            if thr:
+                cols.append(up.hard.cpu().numpy() * np.uint8(255))
+            if args.crf:
+                labels = self.crf(low.cpu().numpy() / 255.0, M, None)
+                crf_masks.append(labels)
+                dev_labels = torch.from_numpy(np.ascontiguousarray(labels[:, 0]).view(np.uint8)).to(self.device)
+                cols.append(fit.up(dev_labels, guide, low, thresh=0.5, want=("hard",), **sig).hard.cpu().numpy() * np.uint8(255))
+            for i, stem in enumerate(stems[lo:lo + len(host)]):
+                if args.concatenated:
+                    Image.fromarray(np.concatenate([host[i]] + [rgb(c[i]) for c in cols], axis=1)).save(f"{out_dir}/{stem}_with_mask.png")
+                else:
+                    for kind, c in zip(kinds, cols):
+                        Image.fromarray(rgb(c[i])).save(f"{out_dir}/{stem}-{kind}.png")
+        print()
+        M = np.concatenate(masks, axis=0)
+        crf_mask = np.concatenate(crf_masks, axis=0) if args.crf else None
+        if getattr(args, "objects", False):
+            self._process_objects(M, crf_mask, stems[:len(files)])
+            if getattr(args, "track_iou", ""):
+                self._process_tracks(M, crf_mask, stems[:len(files)])
+        if self.rank == 0:
+            with open(f"{out_dir}/fit.json", "w") as fp:
+                json.dump({"frame_size": [H, W], "net_size": [fit.SIDE, fit.SIDE], "sigma_spatial": args.fit_spatial,
+                           "sigma_range": args.fit_range, "radius": fit.RADIUS, "frames": len(files)}, fp, indent=1)
         return M
 
     PROCESS_MAX_OBJECTS = 256       # rows of the object table of -process -objects

@@ -978,6 +978,45 @@ enum { CGS_BOUNDARY_MAX_TOL = 16, CGS_BOUNDARY_MAX_TOL_PX = 128 };
 int cgs_boundary_score(const void* pred, int32_t pred_kind, float thresh, const uint8_t* truth, int32_t n, int32_t h, int32_t w,
                        const int32_t* tol2, int32_t T, int32_t* counts, int32_t* dist2, cgs_stream_t stream);
 
+/* ---- frames of any size: the way in and the way out (csrc/fit.hip; this build's own -process -fit) ------------------------------------------
+ * The reference's loader stacks the files of a folder and so demands one size, which its network fixes at 64 x 64 (main.py:1126-1127);
+ * its writer saves every column at the network's size (main.py:1212-1223).  These two entries stand beside those lines: the first shrinks
+ * uint8 frames of any size from 64 to CGS_FIT_MAX_SIDE pixels a side to the network's grid, the second brings a 64 x 64 map back to the
+ * frame's size along the frame's own edges.  Both run on `stream` without synchronising, allocate nothing, use no atomics, are
+ * deterministic and can be captured in a graph.
+ *
+ * cgs_fit_down_u8: the exact box average, in integers (a stretch, not a letterbox).
+ *   frames  uint8 [n][h][w][3]
+ *   out     uint8 [n][64][64][3]
+ * On an axis of length L source pixel s covers [64 s, 64 s + 64), output cell o covers [L o, L o + L) and w_L(o, s) is the length of their
+ * overlap (0..64; it sums to L over s).  Per channel S = sum_y sum_x w_h(oy, y) w_w(ox, x) v[y][x] and out = (2 S + h w) / (2 h w) in
+ * integer division: the box average rounded half up.  For h and w multiples of 64 that is the plain block mean, at h = w = 64 a copy.
+ * The rows are read with 16-, 4- or 1-byte loads: the widest for which `frames` and 3 w are both aligned.
+ * frames, out not NULL, n, h, w >= 1, else CGS_ERR_BADARG; then 64 <= h, w <= CGS_FIT_MAX_SIDE, else CGS_ERR_UNSUPPORTED.
+ *
+ * cgs_fit_up_joint: joint bilateral upsampling (Kopf et al. 2007) of a 64 x 64 map to h x w, guided by the frame.
+ *   map       [n][64][64]: fp32 (map_kind CGS_FIT_MAP_F32, values in [0, 1]) or uint8 labels (CGS_FIT_MAP_U8: non-zero = 1.0)
+ *   guide     uint8 [n][h][w][3]: the frames
+ *   low       uint8 [n][64][64][3]: cgs_fit_down_u8 of `guide`
+ *   sigma_s   in cells, >= 0.5; sigma_r in colour units of 0..255, > 0
+ *   soft      fp32 [n][h][w] or NULL
+ *   grey      uint8 [n][h][w] or NULL: (uint8) (soft * 255.0f), the fp32 product truncated
+ *   hard      uint8 [n][h][w] or NULL, 0 / 1: soft >= thresh, or soft > thresh when `inclusive` is 0, compared in fp32
+ * Pixel (y, x) has the home cell qy0 = ((2 y + 1) 32) / h, qx0 = ((2 x + 1) 32) / w and the taps (qy0 + dy, qx0 + dx), dy, dx in
+ * -CGS_FIT_RADIUS .. CGS_FIT_RADIUS, that lie inside the grid; taps outside it are skipped, not clamped.  With fy = ((2 y + 1) 64 -
+ * h (2 qy + 1)) / (2 h), fx likewise, ds = fy^2 + fx^2, d2 = |guide[y][x] - low[qy][qx]|^2 (an integer) and d2_min the smallest d2 over
+ * the pixel's taps,  w = exp(-(ds / (2 sigma_s^2) + (d2 - d2_min) / (2 sigma_r^2)))  and  soft = sum w m / sum w,  both sums in fp32 in
+ * the same tap order.  The difference d2 - d2_min is taken in integers, so no exponent is rounded before it; the tap of d2_min keeps a
+ * weight of at least exp(-6.25 / sigma_s^2), so the denominator is never zero.  0 <= soft <= 1 for a map in [0, 1].
+ * map, guide, low not NULL, 1 <= n <= 65535, h, w >= 1, a valid map_kind, sigma_s >= 0.5 and sigma_r > 0 and both finite, thresh not a NaN
+ * when hard is given, fp32 map / soft 4-byte aligned, else CGS_ERR_BADARG (nothing is launched); then 64 <= h, w <= CGS_FIT_MAX_SIDE,
+ * else CGS_ERR_UNSUPPORTED.  With all three outputs NULL nothing is launched.                                                            */
+enum { CGS_FIT_SIDE = 64, CGS_FIT_MAX_SIDE = 4096, CGS_FIT_RADIUS = 2, CGS_FIT_MAP_F32 = 0, CGS_FIT_MAP_U8 = 1 };
+int cgs_fit_down_u8(const uint8_t* frames, int32_t n, int32_t h, int32_t w, uint8_t* out, cgs_stream_t stream);
+int cgs_fit_up_joint(const void* map, int32_t map_kind, const uint8_t* guide, const uint8_t* low, int32_t n, int32_t h, int32_t w,
+                     float sigma_s, float sigma_r, float thresh, int32_t inclusive, float* soft, uint8_t* grey, uint8_t* hard,
+                     cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
