@@ -3,6 +3,8 @@
     python main.py -train --model DIR
     python main.py -process [-concatenated] [--binarymaskthreshold t] --model DIR --source-imgs S --mask-output-imgs R
     python main.py -process -fit [--fit-spatial s] [--fit-range r] ...      (this build's own: frames of any one size, 64..4096 a side)
+    python main.py -process --source-video IN.mp4 --overlay-video OUT.mp4 [--smooth R] ...      (this build's own: a video in, masks
+                                                            smoothed along time, a GPU-composed overlay video out)
     python main.py -test --model DIR --output-video V       (evaluation sweep + the evaluation video V/iou=....mp4)
     python main.py -train -critic '' -masker '' -vismasker --model DIR      (DIR/curves.mp4, -pred-sorted.mp4, -GT-sorted.mp4)
 
@@ -51,6 +53,18 @@ def build_parser():
     p.add_argument("-fit", action="store_true")
     p.add_argument("--fit-spatial", type=float, default=None)
     p.add_argument("--fit-range", type=float, default=None)
+    # (this build's own flags) -process --source-video IN --overlay-video OUT: the frames of a video file (decoded by ffmpeg) instead of a
+    # folder of stills, through the -fit machinery, and the masks drawn on the frames at the frames' size as a video (overlay.py).
+    # --smooth R filters the masks along time over +-R frames first (temporal.py; 0 = off), --smooth-range is its colour sigma.  The
+    # defaults (0, 16, overlay, 0,255,0, 0.5, 1) are filled in by check_video_flags, which has to see what was given
+    p.add_argument("--source-video", type=str, default="")
+    p.add_argument("--overlay-video", type=str, default="")
+    p.add_argument("--smooth", type=int, default=None)
+    p.add_argument("--smooth-range", type=float, default=None)
+    p.add_argument("--overlay-layout", type=str, default=None)
+    p.add_argument("--overlay-color", type=str, default=None)
+    p.add_argument("--overlay-alpha", type=float, default=None)
+    p.add_argument("--overlay-outline", type=int, default=None)
     for flag in ("-masker", "-critic", "-cload", "-mload", "-staticnorm", "-visbesteval", "-salglobal"):
         p.add_argument(flag, type=bool, default=True)
     p.add_argument("--salience-thresh", type=float, default="1.5")
@@ -106,6 +120,7 @@ def parse_args(argv=None):
         args.salience = True
     check_sweep_flags(args)
     check_objects_flags(args)
+    check_video_flags(args)
     check_fit_flags(args)
     return args
 
@@ -194,12 +209,71 @@ def check_fit_flags(args):
                                                     names=("--fit-spatial", "--fit-range"))
 
 
+def check_video_flags(args):
+    """--source-video / --overlay-video and the --smooth* / --overlay-* options: combinations that could not run and values out of range
+    are refused here, before any GPU work; the defaults (--smooth 0, --smooth-range 16, --overlay-layout overlay, --overlay-color
+    0,255,0, --overlay-alpha 0.5, --overlay-outline 1) are filled in, --overlay-color becomes (r, g, b), args.overlay_alpha256 is
+    round(256 alpha), and -fit is switched on: a video goes through the -fit machinery.  The frame size is checked after the probe
+    (check_video_size)."""
+    given = [f for f, v in (("--overlay-video", args.overlay_video or None), ("--smooth", args.smooth), ("--smooth-range", args.smooth_range),
+                            ("--overlay-layout", args.overlay_layout), ("--overlay-color", args.overlay_color),
+                            ("--overlay-alpha", args.overlay_alpha), ("--overlay-outline", args.overlay_outline)) if v is not None]
+    if not args.source_video:
+        if given:
+            raise ValueError(f"{' / '.join(given)} belong to --source-video: give --source-video")
+        return
+    if not args.process:
+        raise ValueError("--source-video is the source of -process: give -process")
+    if not args.overlay_video:
+        raise ValueError("--source-video writes its masks as an overlay video: give --overlay-video")
+    for on, what in ((args.eval, "-eval / -test"), (args.crf, "-crf"), (args.objects, "-objects"),
+                     (args.salience or args.process_salience, "-salience / -process_salience"), (args.concatenated, "-concatenated")):
+        if on:
+            raise ValueError(f"--source-video with {what}: outside this build (a video source gives the masks and the overlay video only)")
+    from . import overlay, parallel, temporal
+    from .fit import check_sigmas
+    if parallel.env_world()[2] > 1:
+        raise ValueError(f"--source-video with {parallel.env_world()[2]} ranks: a video is one stream, run one process")
+    args.smooth = temporal.check_radius(0 if args.smooth is None else args.smooth, least=0, name="--smooth")
+    _, args.smooth_range = check_sigmas(1.0, temporal.SIGMA_RANGE if args.smooth_range is None else args.smooth_range,
+                                        names=("", "--smooth-range"))
+    def named(flag, fn, value):
+        try:
+            return fn(value)
+        except ValueError as e:
+            raise ValueError(f"{flag}: {e}") from None
+    args.overlay_layout = overlay.LAYOUT if args.overlay_layout is None else args.overlay_layout
+    args.overlay_panels = named("--overlay-layout", overlay.panels, args.overlay_layout)
+    args.overlay_color = named("--overlay-color", overlay.parse_color, overlay.COLOR if args.overlay_color is None else args.overlay_color)
+    args.overlay_alpha = overlay.ALPHA if args.overlay_alpha is None else args.overlay_alpha
+    args.overlay_alpha256 = named("--overlay-alpha", overlay.to_alpha256, args.overlay_alpha)
+    args.overlay_outline = named("--overlay-outline", overlay.check_outline,
+                                 overlay.OUTLINE if args.overlay_outline is None else args.overlay_outline)
+    args.fit = True
+
+
+def check_video_size(w, h, panels):
+    """The probed frame size of --source-video: 64..4096 a side (fit.check_size), and an even height and an even width of the finished
+    frame, which yuv420p needs.  Called after the probe and before the first frame is decoded."""
+    from .fit import check_size
+    try:
+        check_size(h, w)
+    except ValueError as e:
+        raise ValueError(f"--source-video: {e}") from None
+    if h % 2 or (panels * w) % 2:
+        raise ValueError(f"--source-video: frames of {w}x{h} give a video of {panels * w}x{h}; yuv420p needs an even width and height "
+                         "(odd sizes are outside this build)")
+
+
 def main(argv=None):
     from . import vis
     from .handler import Handler
     args = parse_args(argv)
     if (args.viscritic or args.vismasker) and not args.trainasvis:
         vis.refuse_unbuilt(args)            # before any GPU work
+    if args.source_video:
+        from . import video_in
+        video_in.find_ffmpeg(), video_in.find_ffprobe()     # FileNotFoundError before any GPU work
     H = Handler(args)
     if args.train:
         H.load_data()

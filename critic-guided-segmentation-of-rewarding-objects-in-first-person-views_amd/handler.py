@@ -456,6 +456,8 @@ class Handler:
             raise NotImplementedError("-noevalmode together with -salience (Dropout inside the saliency backward) is not implemented")
         if args.process_salience and not args.salience:
             raise ValueError("-process_salience needs -salience (the reference collects the maps only then, main.py:1136-1147)")
+        if getattr(args, "source_video", ""):           # (this build's flag) a video file in, an overlay video out; `folder` is not read
+            return self._segment_video(args.source_video)
         if getattr(args, "fit", False):                 # (this build's flag) frames of any one size; everything below stays as it is
             return self._segment_fit(folder)
         files = os.listdir(folder)
@@ -580,6 +582,120 @@ class Handler:
             with open(f"{out_dir}/fit.json", "w") as fp:
                 json.dump({"frame_size": [H, W], "net_size": [fit.SIDE, fit.SIDE], "sigma_spatial": args.fit_spatial,
                            "sigma_range": args.fit_range, "radius": fit.RADIUS, "frames": len(files)}, fp, indent=1)
+        return M
+
+    VIDEO_CHUNK_FRAMES, VIDEO_CHUNK_BYTES = 128, 256 << 20    # a chunk of -process --source-video: at most so many frames and frame bytes
+
+    def _segment_video(self, path):
+        """-process --source-video IN --overlay-video OUT: the frames of a video file, 64 to 4096 pixels a side, decoded by ffmpeg a chunk
+        of at most 128 frames and about 256 MB at a time (video_in.read_chunks).  Two stages, so that the smoother has its lookahead:
+          A  upload, fit.down, the network exactly as _segment_fit feeds it;
+          B  --smooth R > 0: temporal.smooth over a rolling device stack -- the last R frames before the chunk, the chunk, the first R
+             after it, with their shrunk frames -- then fit.up (the grey byte, and the hard mask at --binarymaskthreshold, inclusive; no
+             hard mask and so no outline at threshold 0), overlay.compose, an asynchronous copy into a pinned double buffer and the
+             encoder (video.ffmpeg_argv with the probed rate).
+        Stage A of chunk c + 1 runs before stage B of chunk c (a chunk waits until R frames after it are there, or the stream has ended).
+        No PNG is written.  Rank 0 leaves {R}/{stem of OUT}.json.  Returns the 64 x 64 masks [n,1,64,64], the smoothed ones with --smooth."""
+        from collections import deque
+        import subprocess
+        from . import cli, fit, overlay, temporal, video_in
+        args = self.args
+        ffmpeg, ffprobe = video_in.find_ffmpeg(), video_in.find_ffprobe()
+        W, H, rate = video_in.probe(path, ffprobe)
+        k = args.overlay_panels
+        cli.check_video_size(W, H, k)                  # before the first frame is decoded
+        fp16 = bool(getattr(args, "fp16", False))
+        thr, R = args.binarymaskthreshold, args.smooth
+        self.critic.eval()
+        self.masker.eval()
+        eng = self._engine(2 * 32)
+        out_dir, out_path = args.mask_output_imgs, args.overlay_video
+        os.makedirs(out_dir, exist_ok=True)
+        if os.path.dirname(out_path):
+            os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        sig = dict(sigma_s=args.fit_spatial, sigma_r=args.fit_range)
+        step = max(1, min(self.VIDEO_CHUNK_FRAMES, self.VIDEO_CHUNK_BYTES // (3 * H * W)))
+        unit = torch.from_numpy((np.arange(256) / 255.0).astype(np.float32)).to(self.device)      # as _segment_fit: float32(k / 255.0)
+        masks = []
+        proc = subprocess.Popen(video.ffmpeg_argv(ffmpeg, out_path, k * W, H, framerate=rate), stdin=subprocess.PIPE)
+        writer = video.FrameWriter(proc.stdin, (H, k * W, 3), step)
+        pending = deque()                              # chunks through stage A, waiting for stage B: (guide, low, Z)
+        tail = None                                    # (Z, low) of the last R frames before the first pending chunk, unsmoothed
+
+        def stage_a(host):
+            guide = torch.from_numpy(host).to(self.device)        # (a blocking copy: the reader may refill the buffer afterwards)
+            low = fit.down(guide)
+            if fp16:
+                _pred, Z = eng.infer(low, fp16=True)
+            else:
+                _pred, Z = eng.infer(unit[low.long()], train_mode=bool(args.noevalmode))
+            return guide, low, Z.contiguous().clone()
+
+        def stage_b():
+            nonlocal tail
+            guide, low, Z = pending.popleft()
+            if R:
+                zs, ls = [Z], [low]
+                need = R
+                for _g, l2, z2 in pending:             # the head of what follows, R frames of it
+                    if need <= 0:
+                        break
+                    zs.append(z2[:need])
+                    ls.append(l2[:need])
+                    need -= len(zs[-1])
+                f0 = 0
+                if tail is not None:
+                    zs.insert(0, tail[0])
+                    ls.insert(0, tail[1])
+                    f0 = len(tail[0])
+                Zs = temporal.smooth(torch.cat(zs), torch.cat(ls), R, args.smooth_range, f0, f0 + len(Z))
+                before = (torch.cat((tail[0], Z)), torch.cat((tail[1], low))) if tail is not None else (Z, low)
+                tail = (before[0][-R:], before[1][-R:])
+            else:
+                Zs = Z
+            masks.append(Zs.cpu().numpy()[:, None])
+            up = fit.up(Zs, guide, low, thresh=thr if thr else None, want=("grey", "hard") if thr else ("grey",), **sig)
+            frames = overlay.compose(guide, up.grey, up.hard, color=args.overlay_color, alpha256=args.overlay_alpha256,
+                                     outline=args.overlay_outline, layout=args.overlay_layout)
+            writer.submit(frames)
+
+        failure, done = None, 0
+        try:
+            for host in video_in.read_chunks(path, step, size=(W, H), ffmpeg=ffmpeg):
+                print("segmentation in progress, frame", done, end="\r")
+                done += len(host)
+                pending.append(stage_a(host))
+                while pending and sum(len(c[2]) for c in list(pending)[1:]) >= max(R, 1):
+                    stage_b()
+            while pending:
+                stage_b()
+            writer.close()
+        except BrokenPipeError as e:
+            failure = e
+        finally:
+            try:
+                writer.close()
+            except BaseException as e:               # (the first failure is the one reported)
+                failure = failure or e
+            try:
+                proc.stdin.close()
+            except BrokenPipeError:
+                pass
+            rc = proc.wait()
+        if rc != 0 or isinstance(failure, BrokenPipeError):
+            raise RuntimeError(f"ffmpeg exited with status {rc} while writing {out_path}" + (f" ({failure})" if failure else ""))
+        if failure is not None:
+            raise failure
+        print()
+        M = np.concatenate(masks, axis=0)
+        if self.rank == 0:
+            stem = os.path.basename(out_path).rsplit(".", 1)[0]
+            with open(f"{out_dir}/{stem}.json", "w") as fp:
+                json.dump({"frame_size": [H, W], "frames": len(M), "rate": rate, "layout": args.overlay_layout,
+                           "color": list(args.overlay_color), "alpha256": args.overlay_alpha256, "outline": args.overlay_outline,
+                           "threshold": thr,
+                           "smooth": {"radius": R, "sigma_t": temporal.sigma_t(R), "sigma_range": args.smooth_range} if R else None,
+                           "sigma_spatial": args.fit_spatial, "sigma_range": args.fit_range}, fp, indent=1)
         return M
 
     PROCESS_MAX_OBJECTS = 256       # rows of the object table of -process -objects

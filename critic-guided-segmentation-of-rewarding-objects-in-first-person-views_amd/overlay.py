@@ -1,0 +1,101 @@
+"""The frames of the overlay video of ``-process --source-video`` (csrc/overlay.hip): ``compose`` tints every frame by its upsampled mask
+(``fit.up``'s grey byte), draws the outline of the thresholded mask in the tint colour and lays the panels side by side -- the overlay
+alone, frame | overlay, or frame | overlay | grey.  Integers throughout, so a result is reproducible bit for bit.  Runs on the GPU only;
+``parse_color`` / ``to_alpha256`` / ``panels`` / ``check_outline`` are the pure host helpers.
+
+The outline is the set of on pixels within Manhattan distance t - 1 of an off pixel, where a pixel OUTSIDE the frame counts as on: a
+mask that the frame cuts draws no line along the frame's edge.  boundary.py scores with the opposite convention (there the frame's edge
+belongs to an object's outline); a drawn line along the border of the picture would only be noise."""
+import numpy as np
+import torch
+
+from . import _lib
+from .fit import _frames, _need_gpu
+
+LAYOUTS = {"overlay": _lib.OVERLAY_ONLY, "side": _lib.OVERLAY_SIDE, "triple": _lib.OVERLAY_TRIPLE}
+MAX_OUTLINE = _lib.OVERLAY_MAX_OUTLINE
+COLOR, ALPHA, OUTLINE, LAYOUT = (0, 255, 0), 0.5, 1, "overlay"
+NONTEMPORAL = True
+
+
+def panels(layout):
+    """The number of panels of a layout name; ValueError for an unknown one."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout {layout!r}: one of {', '.join(LAYOUTS)}")
+    return LAYOUTS[layout]
+
+
+def parse_color(text):
+    """"R,G,B" (or three numbers) -> (r, g, b), whole numbers 0..255; ValueError otherwise."""
+    parts = text.split(",") if isinstance(text, str) else list(text) if isinstance(text, (tuple, list)) else None
+    if parts is None or len(parts) != 3:
+        raise ValueError(f"colour {text!r}: three integers R,G,B")
+    out = []
+    for p in parts:
+        try:
+            v = int(p.strip(), 10) if isinstance(p, str) else p
+        except ValueError:
+            raise ValueError(f"colour {text!r}: three integers R,G,B") from None
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 255:
+            raise ValueError(f"colour {text!r}: each of R,G,B is an integer 0..255")
+        out.append(int(v))
+    return tuple(out)
+
+
+def to_alpha256(alpha):
+    """An opacity in [0, 1] as the integer round(alpha * 256) in 0..256; ValueError outside the range."""
+    try:
+        a = float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"alpha must be a number, got {alpha!r}") from None
+    if not 0.0 <= a <= 1.0:                      # (a NaN fails both comparisons)
+        raise ValueError(f"alpha = {alpha!r}: an opacity is between 0 and 1")
+    return int(round(a * 256))
+
+
+def check_outline(t, name="outline"):
+    if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t <= MAX_OUTLINE:
+        raise ValueError(f"{name} = {t!r}: a thickness is an integer 0..{MAX_OUTLINE} pixels")
+    return int(t)
+
+
+def compose(guide, grey, hard=None, color=COLOR, alpha256=128, outline=OUTLINE, layout=LAYOUT, out=None, nontemporal=NONTEMPORAL):
+    """guide: device tensor uint8 [n,H,W,3], the frames, 64 <= H, W <= 4096.  grey: uint8 [n,H,W] (fit.up's grey).  hard: uint8 / bool
+    [n,H,W], zero / non-zero, or None (no outline).  color (r, g, b); alpha256: the opacity as an integer 0..256; outline: thickness 0..4;
+    layout "overlay", "side" or "triple" (k = 1, 2, 3 panels).  Returns uint8 [n,H,k W,3] (`out` when given) on the inputs' device:
+    overlay_c = (frame_c (65280 - q) + color_c q + 32640) // 65280 with q = alpha256 grey, outline pixels the colour itself; "side" puts
+    the frame to its left, "triple" also the grey byte as RGB to its right.  No CPU path: raises CgsError without a GPU."""
+    n, h, w = _frames("guide", guide)
+    k = panels(layout)
+    r, g, b = parse_color(color)
+    outline = check_outline(outline)
+    if isinstance(alpha256, bool) or not isinstance(alpha256, (int, np.integer)) or not 0 <= alpha256 <= 256:
+        raise ValueError(f"alpha256 = {alpha256!r}: an integer 0..256 (overlay.to_alpha256 maps an opacity to it)")
+    if not isinstance(grey, torch.Tensor) or grey.dtype != torch.uint8 or tuple(grey.shape) != (n, h, w):
+        raise ValueError(f"grey must be a uint8 tensor [{n},{h},{w}], got "
+                         + (f"{grey.dtype} {tuple(grey.shape)}" if isinstance(grey, torch.Tensor) else type(grey).__name__))
+    if hard is not None and (not isinstance(hard, torch.Tensor) or hard.dtype not in (torch.uint8, torch.bool) or tuple(hard.shape) != (n, h, w)):
+        raise ValueError(f"hard must be a uint8 or bool tensor [{n},{h},{w}] or None, got "
+                         + (f"{hard.dtype} {tuple(hard.shape)}" if isinstance(hard, torch.Tensor) else type(hard).__name__))
+    if n > 65535:
+        raise ValueError(f"guide: at most 65535 frames a call, got {n}")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous()
+                            or tuple(out.shape) != (n, h, k * w, 3)):
+        raise ValueError(f"out must be a contiguous uint8 tensor [{n},{h},{k * w},3]")
+    tensors = (guide, grey) + ((hard,) if hard is not None else ()) + ((out,) if out is not None else ())
+    _need_gpu("overlay.compose (cgs_overlay_compose)", *tensors)
+    if not guide.is_contiguous():
+        guide = guide.contiguous()
+    if not grey.is_contiguous():
+        grey = grey.contiguous()
+    if hard is not None:
+        hard = hard.contiguous()
+        if hard.dtype == torch.bool:
+            hard = hard.view(torch.uint8)
+    if out is None:
+        out = torch.empty((n, h, k * w, 3), dtype=torch.uint8, device=guide.device)
+    with torch.cuda.device(guide.device):
+        _lib.call("cgs_overlay_compose", guide.data_ptr(), grey.data_ptr(), hard.data_ptr() if hard is not None else None, n, h, w, r, g, b,
+                  int(alpha256), outline, k, _lib.OVERLAY_NONTEMPORAL if nontemporal else 0, out.data_ptr(),
+                  torch.cuda.current_stream().cuda_stream)
+    return out

@@ -239,6 +239,62 @@ def stream_frames(comp, sink, chunk=CHUNK):
     return written[0]
 
 
+class FrameWriter:
+    """Finished frames from the device to a byte sink (an encoder's stdin), a chunk at a time: ``submit`` copies a device chunk into one of
+    two pinned host buffers without waiting, and a writer thread hands the buffer to sink.write once its copy has landed -- the
+    double buffer of stream_frames for a caller that composes its chunks itself.  ``close`` drains and re-raises a failed write."""
+
+    def __init__(self, sink, frame_shape, chunk):
+        self.sink, self.frame_shape, self.written = sink, tuple(frame_shape), 0
+        self._hosts = [torch.empty((chunk,) + self.frame_shape, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        self._free = [threading.Semaphore(1) for _ in range(2)]
+        self._todo, self._err, self._i = queue.Queue(), [], 0
+        self._thread = threading.Thread(target=self._run, name="video-writer", daemon=True)
+        self._thread.start()
+
+    def _run(self):
+        while True:
+            item = self._todo.get()
+            if item is None:
+                return
+            k, cnt, ev = item
+            try:
+                if not self._err:
+                    ev.synchronize()
+                    buf = self._hosts[k].numpy()[:cnt].reshape(-1)
+                    self.sink.write(memoryview(buf))
+                    self.written += buf.nbytes
+            except BaseException as e:      # (a closed pipe: reported by close after the thread has stopped)
+                self._err.append(e)
+            finally:
+                self._free[k].release()
+
+    def submit(self, frames):
+        """frames: device uint8 [m, *frame_shape], m at most the chunk; copied on the current stream."""
+        cnt = len(frames)
+        if tuple(frames.shape[1:]) != self.frame_shape or frames.dtype != torch.uint8 or not 1 <= cnt <= len(self._hosts[0]):
+            raise ValueError(f"a chunk is uint8 [1..{len(self._hosts[0])}, {self.frame_shape}], got {frames.dtype} {tuple(frames.shape)}")
+        k = self._i % 2
+        self._i += 1
+        self._free[k].acquire()                  # the writer is done with this buffer
+        if self._err:
+            self._free[k].release()
+            raise self._err[0]
+        self._hosts[k][:cnt].copy_(frames, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._todo.put((k, cnt, ev))
+
+    def close(self):
+        if self._thread is not None:
+            self._todo.put(None)
+            self._thread.join()
+            self._thread = None
+        if self._err:
+            raise self._err[0]
+        return self.written
+
+
 def write_video(path, layout, sources, device="cuda", ffmpeg=None, chunk=CHUNK, font=None):
     """Encodes the video of main.py:1027-1087 to `path` with ffmpeg (ffmpeg_argv); raises if ffmpeg fails.  Returns the frame count."""
     exe = ffmpeg or find_ffmpeg()

@@ -1017,6 +1017,56 @@ int cgs_fit_up_joint(const void* map, int32_t map_kind, const uint8_t* guide, co
                      float sigma_s, float sigma_r, float thresh, int32_t inclusive, float* soft, uint8_t* grey, uint8_t* hard,
                      cgs_stream_t stream);
 
+/* ---- a video as the source: masks smoothed along time, the overlay composed (csrc/temporal.hip, csrc/overlay.hip; this build's own
+ * -process --source-video) ---------------------------------------------------------------------------------------------------------------
+ * The reference reads a folder of stills and writes a PNG per column (main.py:1126-1127, 1212-1223); it has no notion of frame order.
+ * These two entries stand beside cgs_fit_*: the first filters the 64 x 64 masks of consecutive frames along time, the second draws a mask
+ * on its frame at the frame's own size.  Both run on `stream` without synchronising, allocate nothing, use no atomics, are deterministic
+ * and can be captured in a graph.
+ *
+ * cgs_temporal_smooth: spatio-temporal joint bilateral smoothing of a stack of masks, guided by the shrunk frames.
+ *   z       fp32 [n][64][64], values in [0, 1]
+ *   low     uint8 [n][64][64][3]: cgs_fit_down_u8 of the frames
+ *   out     fp32 [f1 - f0][64][64]: frames f0 <= f < f1 of the smoothed stack
+ *   radius  frames each way, 1 .. CGS_TEMPORAL_MAX_RADIUS; sigma_t = radius / 2 (the window is +-2 sigma); sigma_r in colour units, > 0
+ * For frame f and cell p the taps are, IN THIS ORDER (the order of both fp32 sums): the centre tap (f, p), weight exactly 1; then k = -radius
+ * .. -1, 1 .. radius ascending, and for each k with 0 <= g = f + k < n, dy = -1, 0, 1 (outer) and dx = -1, 0, 1 (inner), the cell p + (dy,
+ * dx) of frame g when it lies inside the grid.  A frame outside [0, n) and a cell outside the grid are skipped, not clamped.
+ *   w = exp(-(k^2 / (2 sigma_t^2) + (dy^2 + dx^2) / 2 + d2 / (2 sigma_r^2))),  d2 = |low[g][p + (dy, dx)] - low[f][p]|^2 (an integer),
+ *   num = fma(w, z[g][p + (dy, dx)], num),  den = den + w,  out = num / den (the IEEE division).
+ * The spatial sigma is one cell; one hardware exp2 per tap with the constants folded to base 2.  den >= 1, 0 <= out <= 1, and a stack that
+ * is 1.0 wherever a weight is non-zero gives exactly 1.0f.  Motion is not compensated.  The sub-range lets a caller that works in chunks
+ * hand over a window (the tail of the chunk before, the chunk, the head of the next) and receive the chunk's frames: with `radius` frames
+ * of halo on each side (or the stack's end) the result equals the one-call result bit for bit.
+ * z, low, out not NULL, n >= 1, 0 <= f0 < f1 <= n, radius >= 1, sigma_r > 0 and finite, z / out 4-byte aligned, else CGS_ERR_BADARG
+ * (nothing is launched); then radius <= CGS_TEMPORAL_MAX_RADIUS, else CGS_ERR_UNSUPPORTED.
+ *
+ * cgs_overlay_compose: the frames of the overlay video, in integers.
+ *   guide     uint8 [n][h][w][3]: the frames
+ *   grey      uint8 [n][h][w]: the grey byte of cgs_fit_up_joint
+ *   hard      uint8 [n][h][w], zero / non-zero, or NULL: the thresholded mask, for the outline
+ *   r, g, b   the tint colour, 0..255 each; alpha256 0..256; thickness 0..CGS_OVERLAY_MAX_OUTLINE
+ *   layout    the number of panels k: CGS_OVERLAY_ONLY (overlay), CGS_OVERLAY_SIDE (frame | overlay), CGS_OVERLAY_TRIPLE (frame | overlay |
+ *             grey as RGB)
+ *   flags     CGS_OVERLAY_NONTEMPORAL = non-temporal stores
+ *   out       uint8 [n][h][k w][3]
+ * Overlay panel: q = alpha256 grey, out_c = (frame_c (65280 - q) + tint_c q + 32640) / 65280 in integer division.  Outline: E_0 = hard,
+ * E_{i+1}[p] = E_i[p] and the E_i of its four neighbours, a neighbour OUTSIDE the frame counting as on; pixel p is on the outline when
+ * hard[p] and not E_thickness[p] -- the on pixels within Manhattan distance thickness - 1 of an off pixel -- and is then the tint colour,
+ * opaque.  Because the frame's edge counts as on, a mask cut by the frame draws no line along the frame's edge: the opposite of
+ * cgs_boundary_score's convention, on purpose (there the edge of the frame is part of an object's outline, here it is not drawn).
+ * With hard NULL or thickness 0 there is no outline.  Rows are read and written 16, 4 or 1 bytes at a time: the widest for which guide,
+ * grey, out and w are all aligned.
+ * guide, grey, out not NULL, 1 <= n <= 65535, h, w >= 1, colour, alpha256, thickness, layout in range, no unknown flag, else CGS_ERR_BADARG
+ * (nothing is launched); then 64 <= h, w <= CGS_FIT_MAX_SIDE, else CGS_ERR_UNSUPPORTED.                                                  */
+enum { CGS_TEMPORAL_SIDE = 64, CGS_TEMPORAL_MAX_RADIUS = 8 };
+enum { CGS_OVERLAY_ONLY = 1, CGS_OVERLAY_SIDE = 2, CGS_OVERLAY_TRIPLE = 3, CGS_OVERLAY_MAX_OUTLINE = 4, CGS_OVERLAY_NONTEMPORAL = 1 };
+int cgs_temporal_smooth(const float* z, const uint8_t* low, int32_t n, int32_t f0, int32_t f1, int32_t radius, float sigma_r, float* out,
+                        cgs_stream_t stream);
+int cgs_overlay_compose(const uint8_t* guide, const uint8_t* grey, const uint8_t* hard, int32_t n, int32_t h, int32_t w, int32_t r,
+                        int32_t g, int32_t b, int32_t alpha256, int32_t thickness, int32_t layout, int32_t flags, uint8_t* out,
+                        cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
