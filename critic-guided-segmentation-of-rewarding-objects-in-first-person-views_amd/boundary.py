@@ -2,7 +2,7 @@
 exact squared Euclidean distance of every pixel to each, and from them the counts of the boundary F-measure (the video-segmentation
 benchmarks' contour accuracy), of boundary IoU (Cheng et al., CVPR 2021) and of the Hausdorff distance.  Everything is integer and
 stays on the device; ``tol_squared`` / ``parse_boundary_tol`` / ``boundary_report`` are the pure host helpers of ``-eval
---boundary-tol`` (handler.py, eval_boundary.json).
+--boundary-tol`` (evaluate.py, eval_boundary.json).
 
 Two conventions differ from other tools: everything outside the frame counts as off, so a mask cut by the frame edge has its boundary
 there; and the boundary is the inner boundary (on pixels with an off 4-neighbour), not a ``seg2bmap`` half-pixel map."""

@@ -1,0 +1,208 @@
+"""The reports of ``-eval`` (handler.Handler.eval): the threshold, saliency and CRF-grid sweeps of eval_sweep.json, and
+eval_objects.json, eval_match.json, eval_tracks.json, eval_boundary.json.  ``Stacks`` holds the stacks of one run on the device: each
+is uploaded when a report first reads it, labelled (objects.label) once per source and matched (objects.match) once per source and
+threshold list.  A report function takes (args, stacks) and returns (the dict of its file, its summary line); everything is scored on
+the GPU and only counts come back.  ``write_json`` is the one writer of every report, here and in process.py."""
+import json
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import boundary, metrics, objects, saliency
+
+MATCH_MAX_OBJECTS = 64          # objects per frame and side that --match-iou matches and --track-iou follows
+
+
+def _json_safe(obj):
+    """NaN (an empty union or denominator) has no JSON spelling: it is written as null."""
+    if isinstance(obj, dict):
+        return {k: _json_safe(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return [_json_safe(v) for v in obj]
+    return None if isinstance(obj, float) and math.isnan(obj) else obj
+
+
+def write_json(path, obj, rank=0):
+    """Rank 0 (data parallel: one writer) leaves `obj` at `path`, NaN as null, its directory made if need be."""
+    if rank == 0:
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        with open(path, "w") as fp:
+            json.dump(_json_safe(obj), fp, indent=1)
+
+
+def fmt(v):
+    return "nan" if v is None else f"{v:.6f}"
+
+
+class Stacks:
+    """The stacks of one -eval run by name, host arrays in `host`: "truth" (bool), "mask" (the probabilities, float32, read with the
+    strict compare of --eval-thresh, main.py:964), the hard stacks "crf", "saliency", "saliency_crf" where the run has them, and the
+    saliency sweep's inputs "sal" and "preds" (float32).  dev uploads a stack when it is first read; labelled and matched likewise."""
+
+    def __init__(self, args, device, **host):
+        self.args, self.device, self.host, self._made = args, device, host, {}
+
+    def _once(self, key, make):
+        if key not in self._made:
+            self._made[key] = make()
+        return self._made[key]
+
+    def names(self, among=("mask", "crf", "saliency", "saliency_crf")):
+        """The hard stacks this run has, in the reports' order; among=("mask", "crf"): the ones the object reports describe."""
+        return [name for name in among if name in self.host]
+
+    def dev(self, name):
+        dtype = np.float32 if name in ("mask", "sal", "preds") else None
+        return self._once(name, lambda: torch.from_numpy(np.ascontiguousarray(self.host[name], dtype=dtype)).to(self.device))
+
+    def thresh(self, name):
+        return float(self.args.eval_thresh) if name == "mask" else None
+
+    def labelled(self, name):
+        """objects.label's result for a stack, labels and kept-pixel mask: a prediction with --connectivity and --min-area (the
+        objects eval_objects.json counts), the truth unfiltered.  One call serves every report: labels, mask, found and kept do not
+        depend on max_objects, and no report reads the table."""
+        a = self.args
+        return self._once(("label", name), lambda: objects.label(
+            self.dev(name), thresh=self.thresh(name), connectivity=a.connectivity, min_area=1 if name == "truth" else a.min_area,
+            max_objects=MATCH_MAX_OBJECTS, want_labels=True, want_mask=name != "truth"))
+
+    def matched(self, name, iou):
+        """objects.match of a labelled prediction against the labelled truth at the thresholds `iou`."""
+        return self._once(("match", name, tuple(iou)), lambda: objects.match(
+            self.labelled(name).labels, self.labelled("truth").labels, iou=iou, max_objects=MATCH_MAX_OBJECTS))
+
+
+def _head(args, **more):
+    return {"connectivity": args.connectivity, "min_area": args.min_area, "threshold": float(args.eval_thresh), **more}
+
+
+def _blocks(st, report):
+    """(prefix of the summary line, block) of every object source."""
+    return [("" if name == "mask" else name + " ", report[name]) for name in st.names(("mask", "crf"))]
+
+
+# ---------------------------------------------------------------------------------------------------------------- eval_sweep.json
+def thresh_sweep(args, st):
+    """--thresh-grid: the mask threshold only; the saliency threshold, which is also _saliency_post's normaliser, has a sweep of its
+    own that renormalises per threshold (saliency_sweep)."""
+    thr = metrics.parse_thresh_grid(args.thresh_grid)
+    inter, union = metrics.iou_curve(st.dev("mask"), st.dev("truth"), thr)                              # strict >, main.py:964
+    rep = metrics.curve_report(thr, inter.cpu().numpy(), union.cpu().numpy(), np.count_nonzero(st.host["truth"]))
+    b = rep["best"]
+    return rep, f"\nTHRESH SWEEP {len(thr)} thresholds, best {b['thresh']:.6g} (index {b['index']}) iou {b['iou']:.6f}"
+
+
+def saliency_sweep(args, st):
+    """--salience-grid: _saliency_post's hard mask at every threshold (float64), each with its own normaliser, scored against the truth
+    on the GPU (saliency.sweep): the maps, the predictions and the truth are uploaded once and 2 T counts come back.  The global mode's
+    mean is numpy's, of the host copy, so every row is what _saliency_post and get_iou's counts give at that threshold."""
+    thr, glob, salM = saliency.parse_salience_grid(args.salience_grid), bool(args.salglobal), st.host["sal"]
+    mean = np.where(salM >= 0, salM, 0.0).mean() if glob else None
+    inter, union, _scale = saliency.sweep(st.dev("sal"), st.dev("preds"), st.dev("truth"), thr, glob, mean=mean)
+    rep = saliency.sweep_report(thr, inter.cpu().numpy(), union.cpu().numpy(), np.count_nonzero(st.host["truth"]), salglobal=glob)
+    rep = {"mode": "global" if glob else "frame", **rep}
+    b = rep["best"]
+    return rep, (f"\nSALIENCY SWEEP {len(rep['rows'])} thresholds ({rep['mode']}), best {b['thresh']:.6g} (index {b['index']}) "
+                 f"iou {b['iou']:.6f}")
+
+
+def crf_grid(args, st, tables):
+    """--crf-grid: the tables Handler.crf left behind in this run, the mask's and then the saliency map's."""
+    rep = dict(zip(("mask", "saliency"), tables))
+    return rep, "\nCRF GRID " + "; ".join(f"{k}: {len(r['rows'])} points, best {r['best']['params']} iou {r['best']['iou']:.6f}"
+                                          for k, r in rep.items())
+
+
+# ---------------------------------------------------------------------------------------------------------------- the objects
+def _objects_block(st, name):
+    """One block of eval_objects.json: the kept pixels of a labelled stack and the unfiltered stack scored against the truth with
+    metrics.iou_counts / iou_curve.  Only the counts come back."""
+    res, src, truth, thresh = st.labelled(name), st.dev(name), st.dev("truth"), st.thresh(name)
+    inter, union = metrics.iou_counts(res.mask, truth).tolist()
+    if thresh is None:
+        inter0, union0 = metrics.iou_counts(src, truth).tolist()
+    else:
+        inter0, union0 = (int(c[0]) for c in metrics.iou_curve(src, truth, [thresh]))
+    kept, found = res.kept.cpu().numpy(), res.found.cpu().numpy()
+    return {"inter": inter, "union": union, "iou": metrics.ratio(inter, union),
+            "unfiltered": {"inter": inter0, "union": union0, "iou": metrics.ratio(inter0, union0)},
+            "found": int(found.sum()), "kept": int(kept.sum()), "frames_without_objects": int(np.count_nonzero(kept == 0))}
+
+
+def objects_report(args, st):
+    """-objects: the masks as objects, labelled, filtered and scored on the GPU."""
+    report = _head(args)
+    for name in st.names(("mask", "crf")):
+        report[name] = _objects_block(st, name)
+    report = _json_safe(report)
+    return report, f"\nOBJECTS conn={args.connectivity} min_area={args.min_area}: " + "; ".join(
+        f"{pre}iou {fmt(b['iou'])} (unfiltered {fmt(b['unfiltered']['iou'])}), kept {b['kept']}/found {b['found']} objects"
+        for pre, b in _blocks(st, report))
+
+
+def match_report(args, st):
+    """--match-iou: those objects matched on the GPU to the truth's objects (objects.match).  Only the counts and the T sums of IoU
+    come back."""
+    iou = objects.parse_match_iou(args.match_iou)
+    report = _head(args, max_objects=MATCH_MAX_OBJECTS, iou=iou)
+    for name in st.names(("mask", "crf")):
+        m = st.matched(name, iou)
+        report[name] = objects.match_report(m.pred_max, m.truth_max, m.matched_pred, m.matched_truth, objects.sum_iou(m.best, iou), iou,
+                                            max_objects=MATCH_MAX_OBJECTS)
+    report = _json_safe(report)
+    first = lambda b: b["per_iou"][0]
+    return report, f"\nMATCH conn={args.connectivity} min_area={args.min_area} iou>={iou[0]:g} ({len(iou)} thresholds): " + "; ".join(
+        f"{pre}matched {first(b)['matched_pred']}/{b['pred_objects']} predicted, {first(b)['matched_truth']}/"
+        f"{b['truth_objects']} truth objects, f1 {fmt(first(b)['f1'])}, pq {fmt(first(b)['pq'])}" for pre, b in _blocks(st, report))
+
+
+def _tracked(labelled, iou):
+    """(Tracks, one side of eval_tracks.json) of a labelled stack: tracked on the GPU, the length histogram and the link sums formed
+    there; only the totals, 7 counts and 3 sums come back."""
+    K = MATCH_MAX_OBJECTS
+    tr = objects.track(labelled.labels, iou=iou, max_objects=K)
+    totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
+    return tr, objects.track_report(totals, tr.table[:, 2], tr.table[:, 6].sum(dtype=torch.int64), tr.table[:, 7].sum(dtype=torch.int64),
+                                    (labelled.kept - K).clamp(min=0).sum())
+
+
+def tracks_report(args, st):
+    """--track-iou: the same objects followed from frame to frame on the GPU; with --match-iou the identity switches at its thresholds,
+    from the matches eval_match.json reports."""
+    t_iou = objects.parse_track_iou(args.track_iou)
+    m_iou = objects.parse_match_iou(args.match_iou) if getattr(args, "match_iou", "") else None
+    truth_tr, truth_side = _tracked(st.labelled("truth"), t_iou)
+    report = _head(args, max_objects=MATCH_MAX_OBJECTS, track_iou=t_iou, truth=truth_side)
+    for name in st.names(("mask", "crf")):
+        pred_tr, side = _tracked(st.labelled(name), t_iou)
+        report[name] = {"pred": side}
+        if m_iou is not None:
+            counts = objects.switches(truth_tr.prev, pred_tr.track, st.matched(name, m_iou).best, m_iou).cpu().numpy()
+            report[name]["switches"] = [{"iou": t, "covered": int(c[0]), "continued": int(c[1]), "switches": int(c[2]),
+                                         "switch_rate": int(c[2]) / int(c[1]) if c[1] else None} for t, c in zip(m_iou, counts)]
+    report = _json_safe(report)
+    p = report["mask"]["pred"]
+    return report, (f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g}: {p['tracks']} tracks over {p['objects']} "
+                    f"objects, mean length {fmt(p['mean_length'])}, longest {p['max_length']}; truth {truth_side['tracks']} tracks over "
+                    f"{truth_side['objects']} objects")
+
+
+# ---------------------------------------------------------------------------------------------------------------- the outlines
+def boundary_report(args, st):
+    """--boundary-tol: the outline of every hard stack, and with -objects of the mask eval_objects.json scores (small objects removed),
+    against the truth's outline on the GPU (boundary.score); only the per-frame counts come back."""
+    tol = boundary.parse_boundary_tol(args.boundary_tol)
+    stacks = [(name, st.dev(name), st.thresh(name)) for name in st.names()]
+    if getattr(args, "objects", False):
+        stacks.append(("mask_objects", st.labelled("mask").mask, None))
+    report = {"tol": tol, "tol2": boundary.tol_squared(tol), "threshold": float(args.eval_thresh)}
+    for name, src, thr in stacks:
+        b = boundary.score(src, st.dev("truth"), tol=tol, thresh=thr)
+        report[name] = boundary.boundary_report(*(t.cpu().numpy() for t in b[:8]), tol)
+    report = _json_safe(report)
+    return report, f"\nBOUNDARY tol={tol[0]:g} ({len(tol)} tolerances): " + "; ".join(
+        f"{name} f {fmt(report[name]['per_tol'][0]['f'])} boundary_iou {fmt(report[name]['per_tol'][0]['boundary_iou'])}"
+        for name, _src, _thr in stacks)

@@ -12,7 +12,6 @@ the evaluation video of ``-test`` / ``--output-video`` (video.py: frames compose
 through vis.py (frames composed on the GPU).
 """
 import gzip
-import json
 import math
 import os
 import pickle
@@ -20,9 +19,10 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, boundary, dataformat, metrics, objects, parallel, saliency, sheets, video, vis
+from . import _lib, dataformat, evaluate, metrics, parallel, process, sheets, video, vis
 from .crf import GRID_KEYS, dense_crf, grid_points, parse_crf_grid
 from .engine import HourglassEngine
+from .evaluate import _json_safe, write_json    # noqa: F401  (_json_safe: tests read it from here)
 from .generic_engine import GenericEngine
 from .nets import NewCritic, UnetDecoder
 
@@ -42,13 +42,15 @@ def checkpoint_names(args):
     return critic_args, masker_args
 
 
-def _json_safe(obj):
-    """NaN (an empty union or denominator) has no JSON spelling: it is written as null."""
-    if isinstance(obj, dict):
-        return {k: _json_safe(v) for k, v in obj.items()}
-    if isinstance(obj, (list, tuple)):
-        return [_json_safe(v) for v in obj]
-    return None if isinstance(obj, float) and math.isnan(obj) else obj
+def pyplot():
+    """matplotlib's pyplot on the Agg backend, or None where matplotlib cannot be imported: the plots are then left out."""
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        from matplotlib import pyplot as plt
+    except Exception:
+        return None
+    return plt
 
 
 class Handler:
@@ -460,9 +462,8 @@ class Handler:
             return self._segment_video(args.source_video)
         if getattr(args, "fit", False):                 # (this build's flag) frames of any one size; everything below stays as it is
             return self._segment_fit(folder)
-        files = os.listdir(folder)
+        files, stems = process.list_folder(folder)
         frames = np.stack([np.array(Image.open(os.path.join(folder, f)))[..., :3] for f in files]) / 255.0     # NHWC float64 in [0,1]
-        stems = [f.rsplit(".", 1)[0] for f in files if "." in f]
         fp16 = bool(getattr(args, "fp16", False))      # (this build's switch) BASELINE config 4: fp16 layers on the uint8 frames
 
         def to_device(chunk):
@@ -472,33 +473,22 @@ class Handler:
         preds, M, sal = self._sweep_masks(frames, to_device, "segmentation in progress", want_saliency=bool(args.salience), fp16=fp16)
         print()
         print("postprocessing...")
-        # one column per output kind, in the reference's order; the file name of a column is its POSITION in `kinds` (main.py:1212-1223)
-        cols = [M]
+        cols = [M]                      # one column per output kind, in the order of process.KINDS
         if args.binarymaskthreshold:
             cols.append(M >= args.binarymaskthreshold)
         if args.crf:                    # main.py:1169-1172 (with --binarymaskthreshold 0 this column lands in position 2)
             cols.append(self.crf(frames, M, None))
         if getattr(args, "objects", False):     # (this build's flag) not a column: the by-position naming and the strip stay as they are
-            self._process_objects(M, cols[-1] if args.crf else None, stems[:len(frames)])
-            if getattr(args, "track_iou", ""):
-                self._process_tracks(M, cols[-1] if args.crf else None, stems[:len(frames)])
+            process.objects_and_tracks(args, M, cols[-1] if args.crf else None, stems[:len(frames)], self.device, self.rank)
         if args.process_salience:       # main.py:1176-1197
             sal_maps, sal_hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
             cols += [sal_maps, sal_hard]
             if args.crf:                # main.py:1200-1203
                 cols.append(self.crf(frames, sal_maps, None))
-        kinds = ("raw-mask", "thresholded-mask", "crf-mask", "saliency-map", "thresholded-saliency", "crf-saliency")
         out_dir = args.mask_output_imgs
         os.makedirs(out_dir, exist_ok=True)
         to_u8 = lambda a: (a * 255).astype(np.uint8)
-        grey_rgb = [np.repeat(c, 3, axis=1).transpose(0, 2, 3, 1) for c in cols]          # [n,1,64,64] -> [n,64,64,3]
-        for i, stem in enumerate(stems[:len(frames)]):
-            if args.concatenated:       # frame | column 1 | column 2 ... side by side
-                strip = np.concatenate([to_u8(frames[i])] + [to_u8(g[i]) for g in grey_rgb], axis=1)
-                Image.fromarray(strip).save(f"{out_dir}/{stem}_with_mask.png")
-            else:
-                for kind, g in zip(kinds, grey_rgb):
-                    Image.fromarray(to_u8(g[i])).save(f"{out_dir}/{stem}-{kind}.png")
+        process.write_columns(out_dir, stems[:len(frames)], to_u8(frames), [to_u8(c[:, 0]) for c in cols], args.concatenated)
         return M
 
     FIT_CHUNK_FRAMES, FIT_CHUNK_BYTES = 128, 256 << 20      # a chunk of -process -fit: at most so many frames and frame bytes
@@ -513,8 +503,7 @@ class Handler:
         from PIL import Image
         from . import fit
         args = self.args
-        files = os.listdir(folder)
-        stems = [f.rsplit(".", 1)[0] for f in files if "." in f]
+        files, stems = process.list_folder(folder)
         if not files:
             raise ValueError(f"-fit: {folder!r} holds no files")
         size = None
@@ -537,23 +526,16 @@ class Handler:
         eng = self._engine(2 * 32)
         out_dir = args.mask_output_imgs
         os.makedirs(out_dir, exist_ok=True)
-        kinds = ("raw-mask", "thresholded-mask", "crf-mask")
         sig = dict(sigma_s=args.fit_spatial, sigma_r=args.fit_range)
-        step = max(1, min(self.FIT_CHUNK_FRAMES, self.FIT_CHUNK_BYTES // (3 * H * W)))
-        rgb = lambda a: np.repeat(a[:, :, None], 3, axis=2)
+        step = process.chunk_frames(self.FIT_CHUNK_FRAMES, self.FIT_CHUNK_BYTES, H, W)
         masks, crf_masks = [], []
-        # float32(k / 255.0) for the 256 byte values, rounded on the host as the plain path rounds its frames: the device's own fp32
-        # division is not correctly rounded, so low.float() / 255 would differ from it in the last bit for some k
-        unit = torch.from_numpy((np.arange(256) / 255.0).astype(np.float32)).to(self.device)
+        unit = process.unit_table(self.device)
         for lo in range(0, len(files), step):
             print("segmentation in progress", round(lo / len(files), 2), end="%\r")
             host = np.stack([np.array(Image.open(os.path.join(folder, f)))[..., :3] for f in files[lo:lo + step]])    # NHWC uint8
             guide = torch.from_numpy(np.ascontiguousarray(host, dtype=np.uint8)).to(self.device)
             low = fit.down(guide)
-            if fp16:
-                _pred, Z = eng.infer(low, fp16=True)
-            else:
-                _pred, Z = eng.infer(unit[low.long()], train_mode=bool(args.noevalmode))
+            Z = process.fit_infer(eng, low, unit, fp16, bool(args.noevalmode))
             M = Z.cpu().numpy()[:, None]
             masks.append(M)
             up = fit.up(Z.contiguous(), guide, low, thresh=thr if thr else None, want=("grey", "hard") if thr else ("grey",), **sig)
@@ -565,23 +547,14 @@ class Handler:
                 crf_masks.append(labels)
                 dev_labels = torch.from_numpy(np.ascontiguousarray(labels[:, 0]).view(np.uint8)).to(self.device)
                 cols.append(fit.up(dev_labels, guide, low, thresh=0.5, want=("hard",), **sig).hard.cpu().numpy() * np.uint8(255))
-            for i, stem in enumerate(stems[lo:lo + len(host)]):
-                if args.concatenated:
-                    Image.fromarray(np.concatenate([host[i]] + [rgb(c[i]) for c in cols], axis=1)).save(f"{out_dir}/{stem}_with_mask.png")
-                else:
-                    for kind, c in zip(kinds, cols):
-                        Image.fromarray(rgb(c[i])).save(f"{out_dir}/{stem}-{kind}.png")
+            process.write_columns(out_dir, stems[lo:lo + len(host)], host, cols, args.concatenated)
         print()
         M = np.concatenate(masks, axis=0)
         crf_mask = np.concatenate(crf_masks, axis=0) if args.crf else None
         if getattr(args, "objects", False):
-            self._process_objects(M, crf_mask, stems[:len(files)])
-            if getattr(args, "track_iou", ""):
-                self._process_tracks(M, crf_mask, stems[:len(files)])
-        if self.rank == 0:
-            with open(f"{out_dir}/fit.json", "w") as fp:
-                json.dump({"frame_size": [H, W], "net_size": [fit.SIDE, fit.SIDE], "sigma_spatial": args.fit_spatial,
-                           "sigma_range": args.fit_range, "radius": fit.RADIUS, "frames": len(files)}, fp, indent=1)
+            process.objects_and_tracks(args, M, crf_mask, stems[:len(files)], self.device, self.rank)
+        write_json(f"{out_dir}/fit.json", {"frame_size": [H, W], "net_size": [fit.SIDE, fit.SIDE], "sigma_spatial": args.fit_spatial,
+                                           "sigma_range": args.fit_range, "radius": fit.RADIUS, "frames": len(files)}, self.rank)
         return M
 
     VIDEO_CHUNK_FRAMES, VIDEO_CHUNK_BYTES = 128, 256 << 20    # a chunk of -process --source-video: at most so many frames and frame bytes
@@ -614,8 +587,8 @@ class Handler:
         if os.path.dirname(out_path):
             os.makedirs(os.path.dirname(out_path), exist_ok=True)
         sig = dict(sigma_s=args.fit_spatial, sigma_r=args.fit_range)
-        step = max(1, min(self.VIDEO_CHUNK_FRAMES, self.VIDEO_CHUNK_BYTES // (3 * H * W)))
-        unit = torch.from_numpy((np.arange(256) / 255.0).astype(np.float32)).to(self.device)      # as _segment_fit: float32(k / 255.0)
+        step = process.chunk_frames(self.VIDEO_CHUNK_FRAMES, self.VIDEO_CHUNK_BYTES, H, W)
+        unit = process.unit_table(self.device)
         masks = []
         proc = subprocess.Popen(video.ffmpeg_argv(ffmpeg, out_path, k * W, H, framerate=rate), stdin=subprocess.PIPE)
         writer = video.FrameWriter(proc.stdin, (H, k * W, 3), step)
@@ -625,11 +598,7 @@ class Handler:
         def stage_a(host):
             guide = torch.from_numpy(host).to(self.device)        # (a blocking copy: the reader may refill the buffer afterwards)
             low = fit.down(guide)
-            if fp16:
-                _pred, Z = eng.infer(low, fp16=True)
-            else:
-                _pred, Z = eng.infer(unit[low.long()], train_mode=bool(args.noevalmode))
-            return guide, low, Z.contiguous().clone()
+            return guide, low, process.fit_infer(eng, low, unit, fp16, bool(args.noevalmode)).contiguous().clone()
 
         def stage_b():
             nonlocal tail
@@ -688,130 +657,13 @@ class Handler:
             raise failure
         print()
         M = np.concatenate(masks, axis=0)
-        if self.rank == 0:
-            stem = os.path.basename(out_path).rsplit(".", 1)[0]
-            with open(f"{out_dir}/{stem}.json", "w") as fp:
-                json.dump({"frame_size": [H, W], "frames": len(M), "rate": rate, "layout": args.overlay_layout,
-                           "color": list(args.overlay_color), "alpha256": args.overlay_alpha256, "outline": args.overlay_outline,
-                           "threshold": thr,
-                           "smooth": {"radius": R, "sigma_t": temporal.sigma_t(R), "sigma_range": args.smooth_range} if R else None,
-                           "sigma_spatial": args.fit_spatial, "sigma_range": args.fit_range}, fp, indent=1)
+        stem = os.path.basename(out_path).rsplit(".", 1)[0]
+        write_json(f"{out_dir}/{stem}.json", {
+            "frame_size": [H, W], "frames": len(M), "rate": rate, "layout": args.overlay_layout, "color": list(args.overlay_color),
+            "alpha256": args.overlay_alpha256, "outline": args.overlay_outline, "threshold": thr,
+            "smooth": {"radius": R, "sigma_t": temporal.sigma_t(R), "sigma_range": args.smooth_range} if R else None,
+            "sigma_spatial": args.fit_spatial, "sigma_range": args.fit_range}, self.rank)
         return M
-
-    PROCESS_MAX_OBJECTS = 256       # rows of the object table of -process -objects
-
-    def _process_objects(self, M, crf_mask, stems):
-        """-process -objects: the thresholded masks (M >= --binarymaskthreshold, the comparison of the thresholded column), or with -crf
-        the CRF masks, labelled on the GPU (objects.py).  Rank 0 writes {R}/objects.json and per frame {R}/{stem}-objects-mask.png,
-        the pixels of the kept objects as 0 / 255 grey RGB."""
-        from PIL import Image
-        args = self.args
-        kw = dict(connectivity=args.connectivity, min_area=args.min_area, max_objects=self.PROCESS_MAX_OBJECTS, want_labels=False,
-                  want_mask=True)
-        if crf_mask is not None:
-            source, thresh = "crf-mask", None
-            res = objects.label(torch.from_numpy(np.ascontiguousarray(crf_mask[:, 0])).to(self.device), **kw)
-        else:
-            source, thresh = "thresholded-mask", float(args.binarymaskthreshold)
-            res = objects.label(torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device), thresh=thresh,
-                                inclusive=True, **kw)
-        if self.rank != 0:
-            return
-        kept, found, mask = res.kept.cpu().numpy(), res.found.cpu().numpy(), res.mask.cpu().numpy()
-        rows = objects.table_rows(res.table, kept, width=M.shape[-1])
-        report = {"source": source, "threshold": thresh, "connectivity": args.connectivity, "min_area": args.min_area,
-                  "max_objects": self.PROCESS_MAX_OBJECTS,
-                  "frames": {stem: {"found": int(found[i]), "kept": int(kept[i]), "objects": rows[i]} for i, stem in enumerate(stems)}}
-        out_dir = args.mask_output_imgs
-        os.makedirs(out_dir, exist_ok=True)
-        with open(f"{out_dir}/objects.json", "w") as fp:
-            json.dump(report, fp, indent=1)
-        for i, stem in enumerate(stems):
-            Image.fromarray(np.repeat((mask[i] * np.uint8(255))[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-objects-mask.png")
-
-    def _process_tracks(self, M, crf_mask, stems):
-        """-process -objects --track-iou: the objects objects.json describes (the same source, --connectivity and --min-area), followed
-        through the frames in natural order of their names on the GPU (objects.track); labels above 64 are untracked.  Rank 0 writes
-        {R}/tracks.json and per frame {R}/{stem}-tracks-mask.png, a colour per track."""
-        from PIL import Image
-        args = self.args
-        K, iou = self.MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou)
-        kw = dict(connectivity=args.connectivity, min_area=args.min_area, max_objects=K)
-        if crf_mask is not None:
-            source, thresh = "crf-mask", None
-            res = objects.label(torch.from_numpy(np.ascontiguousarray(crf_mask[:, 0])).to(self.device), **kw)
-        else:
-            source, thresh = "thresholded-mask", float(args.binarymaskthreshold)
-            res = objects.label(torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device), thresh=thresh,
-                                inclusive=True, **kw)
-        order = objects.natural_order(stems)                             # os.listdir's order is arbitrary; only the label stack is reordered
-        pick = torch.tensor(order, dtype=torch.int64, device=res.labels.device)
-        tr = objects.track(res.labels[pick], iou=iou, max_objects=K, want_rgb=True)
-        if self.rank != 0:
-            return
-        totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
-        side = objects.track_report(totals, tr.table[:, 2], tr.table[:, 6].sum(dtype=torch.int64), tr.table[:, 7].sum(dtype=torch.int64),
-                                    (res.kept[pick] - K).clamp(min=0).sum())
-        rows = objects.track_rows(tr.table, side["tracks"])
-        names = [stems[i] for i in order]
-        prev, trk, rgb = tr.prev.cpu().numpy(), tr.track.cpu().numpy(), tr.rgb.cpu().numpy()
-        report = {"source": source, "threshold": thresh, "connectivity": args.connectivity, "min_area": args.min_area, "max_objects": K,
-                  "track_iou": iou, "summary": side, "order": names,
-                  "frames": {stem: [{"label": int(l) + 1, "track": int(trk[j, l]), "prev": int(prev[j, l])} for l in np.flatnonzero(trk[j])]
-                             for j, stem in enumerate(names)},
-                  "tracks": [{"track": r["track"], "first": names[r["first_frame"]], "last": names[r["first_frame"] + r["length"] - 1],
-                              "length": r["length"], "area_sum": r["area_sum"], "area_min": r["area_min"], "area_max": r["area_max"],
-                              "link_iou": r["link_iou"]} for r in rows]}
-        out_dir = args.mask_output_imgs
-        os.makedirs(out_dir, exist_ok=True)
-        with open(f"{out_dir}/tracks.json", "w") as fp:
-            json.dump(_json_safe(report), fp, indent=1)
-        for j, stem in enumerate(names):
-            Image.fromarray(rgb[j]).save(f"{out_dir}/{stem}-tracks-mask.png")
-
-    def _eval_tracks(self, labelled, iou):
-        """(Tracks, one side of eval_tracks.json) of a labelled stack (objects.label's result with max_objects = 64): tracked on the
-        GPU, the length histogram and the link sums formed there; only the totals, 7 counts and 3 sums come back."""
-        K = self.MATCH_MAX_OBJECTS
-        tr = objects.track(labelled.labels, iou=iou, max_objects=K)
-        totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
-        return tr, objects.track_report(totals, tr.table[:, 2], tr.table[:, 6].sum(dtype=torch.int64), tr.table[:, 7].sum(dtype=torch.int64),
-                                        (labelled.kept - K).clamp(min=0).sum())
-
-    def _eval_objects(self, src, truth, thresh=None):
-        """One block of eval_objects.json: the stack `src` (device; float32 with the strict compare of -eval, or bool labels) labelled
-        and filtered on the GPU, the kept pixels and the unfiltered stack scored against `truth` (device bool) with metrics.iou_counts
-        / iou_curve.  Only the counts come back."""
-        args = self.args
-        res = objects.label(src, thresh=thresh, connectivity=args.connectivity, min_area=args.min_area, max_objects=1, want_labels=False,
-                            want_mask=True)
-        inter, union = metrics.iou_counts(res.mask, truth).tolist()
-        if thresh is None:
-            inter0, union0 = metrics.iou_counts(src, truth).tolist()
-        else:
-            inter0, union0 = (int(c[0]) for c in metrics.iou_curve(src, truth, [thresh]))
-        kept, found = res.kept.cpu().numpy(), res.found.cpu().numpy()
-        return {"inter": inter, "union": union, "iou": metrics.ratio(inter, union),
-                "unfiltered": {"inter": inter0, "union": union0, "iou": metrics.ratio(inter0, union0)},
-                "found": int(found.sum()), "kept": int(kept.sum()), "frames_without_objects": int(np.count_nonzero(kept == 0))}
-
-    MATCH_MAX_OBJECTS = 64          # objects per frame and side that -eval -objects --match-iou matches
-
-    def _eval_match(self, src, truth_labels, iou, thresh=None):
-        """One block of eval_match.json: the stack `src` (as _eval_objects takes it) labelled with --connectivity and --min-area -- the
-        objects eval_objects.json counts -- and matched on the GPU against the labelled truth (objects.match).  Only the counts and
-        the T sums of IoU come back."""
-        args = self.args
-        pred = objects.label(src, thresh=thresh, connectivity=args.connectivity, min_area=args.min_area, max_objects=self.MATCH_MAX_OBJECTS)
-        m = objects.match(pred.labels, truth_labels, iou=iou, max_objects=self.MATCH_MAX_OBJECTS)
-        return objects.match_report(m.pred_max, m.truth_max, m.matched_pred, m.matched_truth, objects.sum_iou(m.best, iou), iou,
-                                    max_objects=self.MATCH_MAX_OBJECTS)
-
-    def _eval_boundary(self, src, truth, tol, thresh=None):
-        """One block of eval_boundary.json: the stack `src` (as _eval_objects takes it) scored against the truth's outline on the GPU
-        (boundary.score); only the per-frame counts come back."""
-        b = boundary.score(src, truth, tol=tol, thresh=thresh)
-        return boundary.boundary_report(*(t.cpu().numpy() for t in b[:8]), tol)
 
     def _sweep_masks(self, X, to_device, progress, want_saliency=False, fp16=False, batchsize=128, train_mode=None):
         """The inference loop shared by -process and -eval (main.py:1130-1151, 900-953): eval-mode critic + masker over X in batches
@@ -850,17 +702,6 @@ class Handler:
             scale = np.sort(salM.reshape(n, 1, hw), axis=-1)[:, :, int(hw * thresh), None, None]
         out = np.minimum(salM / (scale + tiny) * preds.reshape(-1, 1, 1, 1), 1.0)
         return out, (out > thresh).astype(np.uint8)
-
-    def _saliency_sweep(self, salM, preds, truth, thr):
-        """--salience-grid: _saliency_post's hard mask at every threshold of thr (float64), each with its own normaliser, scored against
-        truth on the GPU (saliency.sweep): the maps, the predictions and the truth are uploaded once and 2 T counts come back.  The global
-        mode's mean is numpy's, of the host copy, so every row is what _saliency_post and get_iou's counts give at that threshold."""
-        glob = bool(self.args.salglobal)
-        to_dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
-        mean = np.where(salM >= 0, salM, 0.0).mean() if glob else None
-        inter, union, _scale = saliency.sweep(to_dev(salM[:, 0], np.float32), to_dev(preds, np.float32), to_dev(truth, bool), thr, glob, mean=mean)
-        rep = saliency.sweep_report(thr, inter.cpu().numpy(), union.cpu().numpy(), np.count_nonzero(truth), salglobal=glob)
-        return {"mode": "global" if glob else "frame", **rep}
 
     # ------------------------------------------------------------------ -crf: dense-CRF refinement of mask stacks
     def crf(self, imgs, mask, Y, skip=1):
@@ -902,11 +743,8 @@ class Handler:
         return mask >= 1
 
     def _crf_debug_pngs(self, imgs, prob, labels):
-        try:
-            import matplotlib
-            matplotlib.use("Agg")
-            from matplotlib import pyplot as plt
-        except Exception:
+        plt = pyplot()
+        if plt is None:
             return
         out = self.path + "crf/"
         os.makedirs(out, exist_ok=True)
@@ -949,131 +787,44 @@ class Handler:
         preds, M, sal = self._sweep_masks(frames, to_device, "eval at", want_saliency=want_sal)
         hard_m = M[:, 0] > args.eval_thresh
         ious = [self.get_iou(hard_m, truth)]
-        thresh_grid, crf_grid = getattr(args, "thresh_grid", ""), getattr(args, "crf_grid", "")
+        st = evaluate.Stacks(args, self.device, truth=truth, mask=M[:, 0])
+
+        def report(fn, name=None, *more):         # a report's file (the sweeps share one, written below), then its summary line
+            rep, line = fn(args, st, *more)
+            if name:
+                write_json(self.path + name, rep, self.rank)
+            print(line)
+            return rep
         sweep, n_reports = {}, len(self.crf_reports)
-        if thresh_grid:       # (this build's flag) the mask threshold only; the saliency threshold, which is also _saliency_post's
-            # normaliser, has a sweep of its own that renormalises per threshold: --salience-grid below
-            thr = metrics.parse_thresh_grid(thresh_grid)
-            inter, union = metrics.iou_curve(torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device),
-                                             torch.from_numpy(np.ascontiguousarray(truth)).to(self.device), thr)    # strict >, main.py:964
-            sweep["thresholds"] = metrics.curve_report(thr, inter.cpu().numpy(), union.cpu().numpy(), np.count_nonzero(truth))
-            b = sweep["thresholds"]["best"]
-            print(f"\nTHRESH SWEEP {len(thr)} thresholds, best {b['thresh']:.6g} (index {b['index']}) iou {b['iou']:.6f}")
+        if getattr(args, "thresh_grid", ""):    # (this build's flags) the sweeps of eval_sweep.json
+            sweep["thresholds"] = report(evaluate.thresh_sweep)
         crf_m = maps = sal_hard = sal_crf = None
         if args.crf:                                                      # main.py:969-972
-            crf_m = self.crf(frames, M, truth)[:, 0]
+            crf_m = st.host["crf"] = self.crf(frames, M, truth)[:, 0]
             ious.append(self.get_iou(crf_m, truth))
         if want_sal:
             maps, sal_hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
+            st.host["saliency"] = sal_hard[:, 0]
             ious.append(self.get_iou(sal_hard[:, 0], truth))
-            if getattr(args, "salience_grid", ""):      # (this build's flag) the baseline at every threshold, renormalised, on the GPU
-                sweep["saliency"] = self._saliency_sweep(sal, preds, truth, saliency.parse_salience_grid(args.salience_grid))
-                b = sweep["saliency"]["best"]
-                print(f"\nSALIENCY SWEEP {len(sweep['saliency']['rows'])} thresholds ({sweep['saliency']['mode']}), best {b['thresh']:.6g} "
-                      f"(index {b['index']}) iou {b['iou']:.6f}")
+            if getattr(args, "salience_grid", ""):
+                st.host.update(sal=sal[:, 0], preds=preds)
+                sweep["saliency"] = report(evaluate.saliency_sweep)
             if args.crf:                                                  # main.py:1000-1003
-                sal_crf = self.crf(frames, maps, truth)[:, 0]
+                sal_crf = st.host["saliency_crf"] = self.crf(frames, maps, truth)[:, 0]
                 ious.append(self.get_iou(sal_crf, truth))
-        if crf_grid and args.crf:
-            sweep["crf"] = dict(zip(("mask", "saliency"), self.crf_reports[n_reports:]))
-            print("\nCRF GRID " + "; ".join(f"{k}: {len(r['rows'])} points, best {r['best']['params']} iou {r['best']['iou']:.6f}"
-                                            for k, r in sweep["crf"].items()))
+        if getattr(args, "crf_grid", "") and args.crf:
+            sweep["crf"] = report(evaluate.crf_grid, None, self.crf_reports[n_reports:])
         if sweep:
             self.sweep = sweep
-            if self.rank == 0:
-                os.makedirs(self.path, exist_ok=True)
-                with open(self.path + "eval_sweep.json", "w") as fp:
-                    json.dump(_json_safe(sweep), fp, indent=1)
-        if getattr(args, "objects", False):     # (this build's flag) the masks as objects: labelled, filtered and scored on the GPU
-            dev_truth = torch.from_numpy(np.ascontiguousarray(truth)).to(self.device)
-            report = {"connectivity": args.connectivity, "min_area": args.min_area, "threshold": float(args.eval_thresh)}
-            report["mask"] = self._eval_objects(torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device),
-                                                dev_truth, thresh=float(args.eval_thresh))            # strict >, main.py:964
-            if args.crf:
-                report["crf"] = self._eval_objects(torch.from_numpy(np.ascontiguousarray(crf_m)).to(self.device), dev_truth)
-            self.objects = report = _json_safe(report)
-            if self.rank == 0:
-                os.makedirs(self.path, exist_ok=True)
-                with open(self.path + "eval_objects.json", "w") as fp:
-                    json.dump(report, fp, indent=1)
-            fmt = lambda v: "nan" if v is None else f"{v:.6f}"
-            print(f"\nOBJECTS conn={args.connectivity} min_area={args.min_area}: " + "; ".join(
-                f"{name}iou {fmt(b['iou'])} (unfiltered {fmt(b['unfiltered']['iou'])}), kept {b['kept']}/found {b['found']} objects"
-                for name, b in (("", report["mask"]),) + ((("crf ", report["crf"]),) if args.crf else ())))
-            if getattr(args, "match_iou", ""):  # (this build's flag) those objects matched to the truth's objects, on the GPU
-                iou = objects.parse_match_iou(args.match_iou)
-                truth_labels = objects.label(dev_truth, connectivity=args.connectivity, min_area=1,      # the truth is not filtered
-                                             max_objects=self.MATCH_MAX_OBJECTS).labels
-                matched = {"connectivity": args.connectivity, "min_area": args.min_area, "threshold": float(args.eval_thresh),
-                           "max_objects": self.MATCH_MAX_OBJECTS, "iou": iou}
-                matched["mask"] = self._eval_match(torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device),
-                                                    truth_labels, iou, thresh=float(args.eval_thresh))    # strict >, main.py:964
-                if args.crf:
-                    matched["crf"] = self._eval_match(torch.from_numpy(np.ascontiguousarray(crf_m)).to(self.device), truth_labels, iou)
-                self.matches = matched = _json_safe(matched)
-                if self.rank == 0:
-                    with open(self.path + "eval_match.json", "w") as fp:
-                        json.dump(matched, fp, indent=1)
-                first = lambda b: b["per_iou"][0]
-                print(f"\nMATCH conn={args.connectivity} min_area={args.min_area} iou>={iou[0]:g} ({len(iou)} thresholds): " + "; ".join(
-                    f"{name}matched {first(b)['matched_pred']}/{b['pred_objects']} predicted, {first(b)['matched_truth']}/"
-                    f"{b['truth_objects']} truth objects, f1 {fmt(first(b)['f1'])}, pq {fmt(first(b)['pq'])}"
-                    for name, b in (("", matched["mask"]),) + ((("crf ", matched["crf"]),) if args.crf else ())))
-            if getattr(args, "track_iou", ""):  # (this build's flag) the same objects followed from frame to frame, on the GPU
-                K, t_iou = self.MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou)
-                m_iou = objects.parse_match_iou(args.match_iou) if getattr(args, "match_iou", "") else None
-                truth_obj = objects.label(dev_truth, connectivity=args.connectivity, min_area=1, max_objects=K)   # not filtered
-                truth_tr, truth_side = self._eval_tracks(truth_obj, t_iou)
-                tracked = {"connectivity": args.connectivity, "min_area": args.min_area, "threshold": float(args.eval_thresh),
-                           "max_objects": K, "track_iou": t_iou, "truth": truth_side}
-                sources = [("mask", torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(self.device), float(args.eval_thresh))]
-                if args.crf:
-                    sources.append(("crf", torch.from_numpy(np.ascontiguousarray(crf_m)).to(self.device), None))
-                for name, src, thr in sources:
-                    pred = objects.label(src, thresh=thr, connectivity=args.connectivity, min_area=args.min_area, max_objects=K)
-                    pred_tr, side = self._eval_tracks(pred, t_iou)
-                    tracked[name] = {"pred": side}
-                    if m_iou is not None:                                 # identity switches at the thresholds of --match-iou
-                        best = objects.match(pred.labels, truth_obj.labels, iou=m_iou, max_objects=K).best
-                        counts = objects.switches(truth_tr.prev, pred_tr.track, best, m_iou).cpu().numpy()
-                        tracked[name]["switches"] = [{"iou": t, "covered": int(c[0]), "continued": int(c[1]), "switches": int(c[2]),
-                                                      "switch_rate": int(c[2]) / int(c[1]) if c[1] else None}
-                                                     for t, c in zip(m_iou, counts)]
-                self.tracks = tracked = _json_safe(tracked)
-                if self.rank == 0:
-                    with open(self.path + "eval_tracks.json", "w") as fp:
-                        json.dump(tracked, fp, indent=1)
-                p = tracked["mask"]["pred"]
-                print(f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g}: {p['tracks']} tracks over {p['objects']} "
-                      f"objects, mean length {fmt(p['mean_length'])}, longest {p['max_length']}; truth {truth_side['tracks']} tracks over "
-                      f"{truth_side['objects']} objects")
-        if getattr(args, "boundary_tol", ""):   # (this build's flag) the outlines against the truth's outline, scored on the GPU
-            tol = boundary.parse_boundary_tol(args.boundary_tol)
-            dev_truth = torch.from_numpy(np.ascontiguousarray(truth)).to(self.device)
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
-            stacks = [("mask", up(M[:, 0].astype(np.float32, copy=False)), float(args.eval_thresh))]      # strict >, main.py:964
-            if args.crf:
-                stacks.append(("crf", up(crf_m), None))
-            if want_sal:
-                stacks.append(("saliency", up(sal_hard[:, 0]), None))
-                if args.crf:
-                    stacks.append(("saliency_crf", up(sal_crf), None))
-            if getattr(args, "objects", False):                           # the mask eval_objects.json scores: small objects removed
-                kept = objects.label(stacks[0][1], thresh=stacks[0][2], connectivity=args.connectivity, min_area=args.min_area,
-                                     want_labels=False, want_mask=True).mask
-                stacks.append(("mask_objects", kept, None))
-            outlines = {"tol": tol, "tol2": boundary.tol_squared(tol), "threshold": float(args.eval_thresh)}
-            for name, src, thr in stacks:
-                outlines[name] = self._eval_boundary(src, dev_truth, tol, thresh=thr)
-            self.boundary = outlines = _json_safe(outlines)
-            if self.rank == 0:
-                os.makedirs(self.path, exist_ok=True)
-                with open(self.path + "eval_boundary.json", "w") as fp:
-                    json.dump(outlines, fp, indent=1)
-            fmt = lambda v: "nan" if v is None else f"{v:.6f}"
-            print(f"\nBOUNDARY tol={tol[0]:g} ({len(tol)} tolerances): " + "; ".join(
-                f"{name} f {fmt(outlines[name]['per_tol'][0]['f'])} boundary_iou {fmt(outlines[name]['per_tol'][0]['boundary_iou'])}"
-                for name, _src, _thr in stacks))
+            write_json(self.path + "eval_sweep.json", sweep, self.rank)
+        if getattr(args, "objects", False):     # (this build's flags) the masks as objects, matched to the truth's, followed through the frames
+            self.objects = report(evaluate.objects_report, "eval_objects.json")
+            if getattr(args, "match_iou", ""):
+                self.matches = report(evaluate.match_report, "eval_match.json")
+            if getattr(args, "track_iou", ""):
+                self.tracks = report(evaluate.tracks_report, "eval_tracks.json")
+        if getattr(args, "boundary_tol", ""):   # (this build's flag) the outlines against the truth's outline
+            self.boundary = report(evaluate.boundary_report, "eval_boundary.json")
         print("\nRESULTS", ious)
         if vid is not None and self.rank == 0 and ious[0] > self.ious[0]:          # main.py:1027
             layout, exe = vid
@@ -1109,11 +860,8 @@ class Handler:
     # ------------------------------------------------------------------ helpers
     @staticmethod
     def _plot(path, series):
-        try:
-            import matplotlib
-            matplotlib.use("Agg")
-            from matplotlib import pyplot as plt
-        except Exception:
+        plt = pyplot()
+        if plt is None:
             return
         plt.clf()
         for name, vals in series.items():
@@ -1129,11 +877,8 @@ class Handler:
     @staticmethod
     def _hist(path, values):
         """plt.clf(); plt.hist(values); plt.savefig(path) of main.py:257-264."""
-        try:
-            import matplotlib
-            matplotlib.use("Agg")
-            from matplotlib import pyplot as plt
-        except Exception:
+        plt = pyplot()
+        if plt is None:
             return
         plt.clf()
         plt.hist(np.asarray(values))

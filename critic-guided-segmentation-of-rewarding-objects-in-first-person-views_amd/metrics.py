@@ -1,7 +1,7 @@
 """Evaluation scoring on the GPU (csrc/metrics.hip): intersection / union counts of a mask stack against the truth for a whole grid of
 thresholds (``iou_curve``, the grid main.py:974-975 left commented out) or of K label stacks (``iou_counts``, the score of the
 reference's CRF parameter search, main.py:1253).  The stacks are scored where they are; only the counts (int64) come back.
-``parse_thresh_grid`` and ``curve_report`` are pure host helpers for ``-eval --thresh-grid`` (handler.py)."""
+``parse_thresh_grid`` and ``curve_report`` are pure host helpers for ``-eval --thresh-grid`` (evaluate.py)."""
 import math
 
 import numpy as np

@@ -1,7 +1,7 @@
 """From masks to objects on the GPU (csrc/objects.hip): connected-component labelling of a mask stack where it is, an area filter, the
 numbering of ``scipy.ndimage.label`` and a table of the objects (area, bounding box, coordinate sums, first pixel).  Everything is
 integer and stays on the device; ``table_rows`` is the host helper that turns a table into the dicts of ``objects.json``
-(handler.py: ``-process -objects`` / ``-eval -objects``).
+(process.py: ``-process -objects``, evaluate.py: ``-eval -objects``).
 
 ``match`` (csrc/objects_match.hip) matches the objects of two label stacks frame by frame at a list of IoU thresholds; ``sum_iou`` adds
 up the matched pairs' IoU on the device, and ``parse_match_iou`` / ``match_report`` are the pure host helpers of

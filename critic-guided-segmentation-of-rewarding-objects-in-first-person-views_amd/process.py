@@ -1,0 +1,118 @@
+"""What the three ``-process`` paths of handler.Handler share (segment, _segment_fit, _segment_video): the folder listing, the chunk
+size, how a shrunk uint8 frame is fed to the network, the PNG columns with their by-position names, and ``-objects`` /
+``--track-iou`` on the 64 x 64 masks (objects.json, tracks.json and their PNGs).  Under data parallelism every rank makes the GPU
+calls and rank 0 writes."""
+import os
+
+import numpy as np
+import torch
+
+from . import objects
+from .evaluate import MATCH_MAX_OBJECTS, write_json
+
+PROCESS_MAX_OBJECTS = 256       # rows of the object table of -process -objects
+# one column per output kind, in the reference's order; the file name of a column is its POSITION here (main.py:1212-1223)
+KINDS = ("raw-mask", "thresholded-mask", "crf-mask", "saliency-map", "thresholded-saliency", "crf-saliency")
+
+
+def list_folder(folder):
+    """(files, stems) of a folder of frames in os.listdir's order; a name without a dot has no stem."""
+    files = os.listdir(folder)
+    return files, [f.rsplit(".", 1)[0] for f in files if "." in f]
+
+
+def chunk_frames(max_frames, max_bytes, H, W):
+    """Frames per chunk of H x W RGB frames: at most max_frames and about max_bytes, at least one."""
+    return max(1, min(max_frames, max_bytes // (3 * H * W)))
+
+
+def unit_table(device):
+    """float32(k / 255.0) for the 256 byte values, rounded on the host as the plain path rounds its frames: the device's own fp32
+    division is not correctly rounded, so low.float() / 255 would differ from it in the last bit for some k."""
+    return torch.from_numpy((np.arange(256) / 255.0).astype(np.float32)).to(device)
+
+
+def fit_infer(eng, low, unit, fp16, train_mode):
+    """The masks Z [n,64,64] of the shrunk uint8 frames `low`, as -process runs 64 x 64 frames: the fp16 layers take the bytes, the
+    fp32 ones the unit_table values (train_mode: -noevalmode, Dropout stays on)."""
+    if fp16:
+        return eng.infer(low, fp16=True)[1]
+    return eng.infer(unit[low.long()], train_mode=train_mode)[1]
+
+
+def write_columns(out_dir, stems, frames, cols, concatenated):
+    """The PNGs of a run of frames: frames uint8 [n,H,W,3], cols a list of grey uint8 stacks [n,H,W] in KINDS' order.  -concatenated:
+    frame | column 1 | column 2 ... side by side as {stem}_with_mask.png, else one {stem}-{kind}.png per column."""
+    from PIL import Image
+    rgb = lambda a: np.repeat(a[:, :, None], 3, axis=2)
+    for i, stem in enumerate(stems):
+        if concatenated:
+            Image.fromarray(np.concatenate([frames[i]] + [rgb(c[i]) for c in cols], axis=1)).save(f"{out_dir}/{stem}_with_mask.png")
+        else:
+            for kind, c in zip(KINDS, cols):
+                Image.fromarray(rgb(c[i])).save(f"{out_dir}/{stem}-{kind}.png")
+
+
+def binary_source(args, M, crf_mask, device):
+    """The stack -objects and --track-iou describe: (source name, threshold, device stack, objects.label's keywords) -- with -crf the
+    CRF masks, else M >= --binarymaskthreshold (the comparison of the thresholded column)."""
+    kw = dict(connectivity=args.connectivity, min_area=args.min_area)
+    if crf_mask is not None:
+        return "crf-mask", None, torch.from_numpy(np.ascontiguousarray(crf_mask[:, 0])).to(device), kw
+    thresh = float(args.binarymaskthreshold)
+    return ("thresholded-mask", thresh, torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(device),
+            dict(kw, thresh=thresh, inclusive=True))
+
+
+def objects_and_tracks(args, M, crf_mask, stems, device, rank):
+    """-process -objects [--track-iou]: the stack of binary_source labelled on the GPU once (objects.py; labels, mask and counts do not
+    depend on the table's rows), then reported as objects and, if asked for, as tracks."""
+    want_tracks = bool(getattr(args, "track_iou", ""))
+    source, thresh, stack, kw = binary_source(args, M, crf_mask, device)
+    res = objects.label(stack, max_objects=PROCESS_MAX_OBJECTS, want_labels=want_tracks, want_mask=True, **kw)
+    head = {"source": source, "threshold": thresh, "connectivity": args.connectivity, "min_area": args.min_area}
+    _objects(args, res, head, stems, M.shape[-1], rank)
+    if want_tracks:
+        _tracks(args, res, head, stems, rank)
+
+
+def _objects(args, res, head, stems, width, rank):
+    """Rank 0 writes {R}/objects.json and per frame {R}/{stem}-objects-mask.png, the pixels of the kept objects as 0 / 255 grey RGB."""
+    from PIL import Image
+    if rank != 0:
+        return
+    kept, found, mask = res.kept.cpu().numpy(), res.found.cpu().numpy(), res.mask.cpu().numpy()
+    rows = objects.table_rows(res.table, kept, width=width)
+    out_dir = args.mask_output_imgs
+    write_json(f"{out_dir}/objects.json", {**head, "max_objects": PROCESS_MAX_OBJECTS, "frames": {
+        stem: {"found": int(found[i]), "kept": int(kept[i]), "objects": rows[i]} for i, stem in enumerate(stems)}})
+    for i, stem in enumerate(stems):
+        Image.fromarray(np.repeat((mask[i] * np.uint8(255))[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-objects-mask.png")
+
+
+def _tracks(args, res, head, stems, rank):
+    """The objects objects.json describes followed through the frames in natural order of their names on the GPU (objects.track);
+    labels above 64 are untracked.  Rank 0 writes {R}/tracks.json and per frame {R}/{stem}-tracks-mask.png, a colour per track."""
+    from PIL import Image
+    K, iou = MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou)
+    order = objects.natural_order(stems)                             # os.listdir's order is arbitrary; only the label stack is reordered
+    pick = torch.tensor(order, dtype=torch.int64, device=res.labels.device)
+    tr = objects.track(res.labels[pick], iou=iou, max_objects=K, want_rgb=True)
+    if rank != 0:
+        return
+    totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
+    side = objects.track_report(totals, tr.table[:, 2], tr.table[:, 6].sum(dtype=torch.int64), tr.table[:, 7].sum(dtype=torch.int64),
+                                (res.kept[pick] - K).clamp(min=0).sum())
+    rows = objects.track_rows(tr.table, side["tracks"])
+    names = [stems[i] for i in order]
+    prev, trk, rgb = tr.prev.cpu().numpy(), tr.track.cpu().numpy(), tr.rgb.cpu().numpy()
+    report = {**head, "max_objects": K, "track_iou": iou, "summary": side, "order": names,
+              "frames": {stem: [{"label": int(l) + 1, "track": int(trk[j, l]), "prev": int(prev[j, l])} for l in np.flatnonzero(trk[j])]
+                         for j, stem in enumerate(names)},
+              "tracks": [{"track": r["track"], "first": names[r["first_frame"]], "last": names[r["first_frame"] + r["length"] - 1],
+                          "length": r["length"], "area_sum": r["area_sum"], "area_min": r["area_min"], "area_max": r["area_max"],
+                          "link_iou": r["link_iou"]} for r in rows]}
+    out_dir = args.mask_output_imgs
+    write_json(f"{out_dir}/tracks.json", report)
+    for j, stem in enumerate(names):
+        Image.fromarray(rgb[j]).save(f"{out_dir}/{stem}-tracks-mask.png")

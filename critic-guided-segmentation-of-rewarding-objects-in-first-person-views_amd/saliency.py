@@ -2,7 +2,7 @@
 the |gradient| maps, weight them by the critic's prediction, clip at 1, threshold (main.py:976-1003) -- for a whole grid of thresholds
 in one launch, every threshold with its own normaliser, scored against the truth where the maps are.  The on/off decision is
 ``_saliency_post``'s bit for bit (float64, as numpy 2 evaluates it), so every count is exact.
-``parse_salience_grid`` and ``sweep_report`` are pure host helpers for ``-eval -salience --salience-grid`` (handler.py)."""
+``parse_salience_grid`` and ``sweep_report`` are pure host helpers for ``-eval -salience --salience-grid`` (evaluate.py)."""
 import numpy as np
 import torch
 
