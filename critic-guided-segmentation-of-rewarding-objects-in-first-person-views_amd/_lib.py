@@ -117,6 +117,7 @@ SIGNATURES = {
     "cgs_tail_enc_fwd": (i32, [i32, C.POINTER(TailEncWeights), vp, vp, vp, vp, vp, vp, vp, vp, vp, Dropout, Dropout, Dropout, vp]),
     "cgs_enc1_tail_fwd": (i32, [i32, C.POINTER(TailEncWeights), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, Dropout, Dropout, Dropout, vp]),
     "cgs_critic_fwd_fused": (i32, [i32, C.POINTER(TailEncWeights), vp, i32] + [vp] * 16 + [Dropout, Dropout, Dropout, vp]),
+    "cgs_critic_fwd_fused_pack": (i32, [i32, C.POINTER(TailEncWeights), vp, i32] + [vp] * 16 + [Dropout, Dropout, Dropout, vp, vp, vp]),
     "cgs_tail_dec_fwd": (i32, [i32, C.POINTER(TailDecWeights), vp, vp, vp, vp, vp, vp, vp, vp]),
     "cgs_tail_enc_fwd_h16": (i32, [i32, C.POINTER(TailEncWeights), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "cgs_tail_dec_fwd_h16": (i32, [i32, C.POINTER(TailDecWeights), vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -141,6 +142,7 @@ SIGNATURES = {
     "cgs_dec3_wgrad_rider_slabs": (i32, [i32]),
     "cgs_enc0_wgrad_u8_with_head_riders": (i32, [i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "cgs_tail_dec_fwd_dec0": (i32, [i32, C.POINTER(TailDecWeights)] + [vp] * 13 + [vp]),
+    "cgs_dec_mask_fwd": (i32, [i32, C.POINTER(TailDecWeights)] + [vp] * 11 + [i32] + [vp] * 8 + [vp]),
     "cgs_conv3x3_bwd_weight_slabs": (i32, [C.POINTER(ConvDesc)]),
     "cgs_conv3x3_bwd_weight": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp]),
     "cgs_conv3x3_bwd_both_slabs": (i32, [C.POINTER(ConvDesc)]),

@@ -646,7 +646,7 @@ __global__ void __launch_bounds__(C::THREADS * C::CW) conv3x3_kernel(ConvParams 
 }
 
 template <class C>
-static size_t conv_lds_bytes() {
+static constexpr size_t conv_lds_bytes() {
     using G = Geo<C::H, C::W, C::THREADS, C::CW>;
     constexpr int PA = (C::SRC == SRC_SCALAR) ? 1 : (C::CA + 3) / 4;
     constexpr int PB = C::CB / 4;

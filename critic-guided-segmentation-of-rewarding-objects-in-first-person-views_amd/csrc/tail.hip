@@ -22,6 +22,7 @@
 #include "wgrad_dec0.h"
 #include "conv_body.h"
 #include "wgrad_sparse.h"
+#include "mask_fwd_body.h"
 
 namespace {
 
@@ -103,7 +104,9 @@ struct TailEncFwdParams {
     int n;
     int nblocks;
     unsigned long long* dbg;
+    const float* m0_w; float* m0_pack;      // rider (optional, uint8 frames): masker.0's weight registers for the mask head forward, packed once (mask0_pack_weights)
 };
+__device__ __forceinline__ void mask0_pack_weights(const float* __restrict__ w0, float* __restrict__ pack, int lane);
 
 // (round 3) features.6 and features.10 on v_mfma_f32_4x4x1 with lane = pixel (tail4.h): 216 instead of 90 x 4 MFMA-cycles-worth
 // of instructions per wave and image, 36 16-byte LDS reads instead of ~360 dword reads.
@@ -129,6 +132,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(H16 ? 
     __shared__ float es[32], hs[32];                                    // hs: the 32 Dropout multipliers of h1 (stage 3 -> stage 10)
     if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailEncFwdParams) + 2 * sizeof(ConvParams)>();
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (FUSED && ENC0 == 1) {
+        if ((int)blockIdx.x == P.nblocks) {          // the rider workgroup (launched only when m0_pack is given): see tail_dec_fwd_kernel
+            if (wave == 0) mask0_pack_weights(P.m0_w, P.m0_pack, lane);
+            return;
+        }
+    }
     if (CGS_STAMP_PTR(P.dbg) && tid == 0) CGS_STAMP_PTR(P.dbg)[(size_t)blockIdx.x * 16] = __builtin_amdgcn_s_memtime();
     const int o = tid & 31, kg = tid >> 5;
     // the first image's loads and the Dropout step counters are requested before anything else: they fly during the set-up below
@@ -416,15 +425,16 @@ extern "C" int cgs_enc1_tail_fwd(int32_t n, const cgs_tail_enc_weights* w, const
 // The WHOLE critic forward of an image in one workgroup: features.0 (cgs_conv3x3_fwd of the 3 -> 8 layer at 64x64 on uint8 frames, or -- x_is_mix --
 // on the virtual replaced | injected mixes of a cgs_mix_src) -> e0 + am0, then everything cgs_enc1_tail_fwd does.  w0 / b0: features.0's
 // HWIO weights and bias.
-extern "C" int cgs_critic_fwd_fused(int32_t n, const cgs_tail_enc_weights* w, const void* x, int32_t x_is_mix, const float* w0, const float* b0,
+extern "C" int cgs_critic_fwd_fused_pack(int32_t n, const cgs_tail_enc_weights* w, const void* x, int32_t x_is_mix, const float* w0, const float* b0,
                                     float* e0, uint32_t* am0, const float* w3, const float* b3, float* e1, uint32_t* am1, float* e2, uint32_t* am2,
                                     float* e3, uint32_t* am3, float* e4, float* h1, float* pred, float* o4, cgs_dropout drop_e2,
-                                    cgs_dropout drop_e3, cgs_dropout drop_h1, cgs_stream_t stream) {
+                                    cgs_dropout drop_e3, cgs_dropout drop_h1, const float* w_m0, float* m0_pack, cgs_stream_t stream) {
     if (n < 0 || !w || !x || !w0 || !b0 || !e0 || !am0 || !w3 || !b3 || !e1 || !am1 || !e2 || !am2 || !e3 || !am3 || !e4 || !h1 || !pred) return CGS_ERR_BADARG;
     if (!w->w6 || !w->b6 || !w->w10 || !w->b10 || !w->w14 || !w->b14 || !w->wl1 || !w->bl1 || !w->wl2 || !w->bl2) return CGS_ERR_BADARG;
     if (o4 && (!w->wpw || !w->bpw)) return CGS_ERR_BADARG;
+    if (m0_pack && (!w_m0 || x_is_mix)) return CGS_ERR_BADARG;      // (the rider exists in the uint8-frame form: the pass over [B | A])
     if (n == 0) return CGS_OK;
-    TailEncFwdParams P{*w, e1, e2, am2, e3, am3, e4, h1, pred, o4, drop_e2, drop_e3, drop_h1, n, n, g_tail_stamps ? g_tail_stamps + 0 * 2048 * 16 : nullptr};
+    TailEncFwdParams P{*w, e1, e2, am2, e3, am3, e4, h1, pred, o4, drop_e2, drop_e3, drop_h1, n, n, g_tail_stamps ? g_tail_stamps + 0 * 2048 * 16 : nullptr, w_m0, m0_pack};
     ConvParams PC{}, PC0{};
     PC.src_a = e0; PC.w = w3; PC.bias = b3; PC.out = e1; PC.amask_out = am1; PC.n = n;
     PC0.w = w0; PC0.bias = b0; PC0.out = e0; PC0.amask_out = am0; PC0.n = n;
@@ -438,10 +448,18 @@ extern "C" int cgs_critic_fwd_fused(int32_t n, const cgs_tail_enc_weights* w, co
     } else {
         PC0.src_a = x;
         if (conv_lds_bytes<FEnc0U8P>() > lds) lds = conv_lds_bytes<FEnc0U8P>();
-        hipLaunchKernelGGL((tail_enc_fwd_kernel<true, 1>), dim3(n), dim3(256), lds, (hipStream_t)stream, P, PC, PC0);
+        hipLaunchKernelGGL((tail_enc_fwd_kernel<true, 1>), dim3(n + (m0_pack ? 1 : 0)), dim3(256), lds, (hipStream_t)stream, P, PC, PC0);
     }
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
+}
+
+extern "C" int cgs_critic_fwd_fused(int32_t n, const cgs_tail_enc_weights* w, const void* x, int32_t x_is_mix, const float* w0, const float* b0,
+                                    float* e0, uint32_t* am0, const float* w3, const float* b3, float* e1, uint32_t* am1, float* e2, uint32_t* am2,
+                                    float* e3, uint32_t* am3, float* e4, float* h1, float* pred, float* o4, cgs_dropout drop_e2,
+                                    cgs_dropout drop_e3, cgs_dropout drop_h1, cgs_stream_t stream) {
+    return cgs_critic_fwd_fused_pack(n, w, x, x_is_mix, w0, b0, e0, am0, w3, b3, e1, am1, e2, am2, e3, am3, e4, h1, pred, o4, drop_e2, drop_e3, drop_h1,
+                                     nullptr, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -498,23 +516,24 @@ using T1F = TileP<16, 16, 16, 16, 292>;     // cat(e1, up(o2)) of the forward de
 // FUSED (round 4): one workgroup per image; after the tail stages (o1 written) the same workgroup runs dec_model.0 of ITS image
 // (conv3x3_body_pipe<FDec0P>: cat(e0, up(o1)) -> o0), every other co-resident workgroup ~4 us late (cgs_stagger).
 // H16 (round 6, config 4, stand-alone form only): the three layers with fp16 operands on v_mfma_f32_16x16x16_f16 (tail_h16.h)
-template <bool FUSED, bool H16 = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) tail_dec_fwd_kernel(TailDecFwdParams P, ConvParams PC) {
-    static_assert(!H16 || !FUSED, "fp16 operands: the stand-alone inference form");
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailDecFwdParams) + sizeof(ConvParams)>();
-    extern __shared__ __attribute__((aligned(16))) float4 dec_conv_smem[];     // FUSED: dec_model.0's tiles + weights
-    __shared__ __attribute__((aligned(16))) float t1[T1F::FLOATS];
-    __shared__ __attribute__((aligned(16))) float t2[T8x24::FLOATS];
-    __shared__ __attribute__((aligned(16))) float t3[T4x48::FLOATS];
-    __shared__ __attribute__((aligned(16))) float w2s[14 * 64 * 2];       // dec_model.2's weights [216][8] (H16: the fp16 operand table [14][64] x 8 bytes)
-    static_assert(14 * 64 * 2 >= 216 * 8, "either form fits");
-    __shared__ float part[4][16][16];       // dec_model.3: the waves split K, partial [pixel][co]
+// The LDS of the decoder tail forward, handed to its body by the kernel that runs it (tail_dec_fwd_kernel: static arrays + the dynamic block;
+// dec_mask_fwd_kernel: slices of the one block it shares with the mask head forward).
+struct DecFwdLds {
+    float4* conv;               // FUSED: dec_model.0's tiles + weights (conv_lds_bytes<FDec0P>())
+    float* t1; float* t2; float* t3;
+    float* w2s;                 // dec_model.2's weights [216][8] (H16: the fp16 operand table [14][64] x 8 bytes)
+    float (*part)[16][16];      // dec_model.3: the waves split K, partial [pixel][co]
+};
+constexpr int kDecW2sFloats = 14 * 64 * 2;
+static_assert(kDecW2sFloats >= 216 * 8, "either form fits");
+
+// The body of tail_dec_fwd_kernel (and phase D of dec_mask_fwd_kernel): everything after the rider check and the stagger.
+template <bool FUSED, bool H16>
+__device__ __forceinline__ void tail_dec_fwd_body(const TailDecFwdParams& P, const ConvParams& PC, const DecFwdLds S) {
+    float4* const dec_conv_smem = S.conv;
+    float* const t1 = S.t1; float* const t2 = S.t2; float* const t3 = S.t3; float* const w2s = S.w2s;
+    float (*const part)[16][16] = S.part;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if ((int)blockIdx.x == P.nblocks) {          // the rider workgroup (launched only when m0_pack is given)
-        if (wave == 0) mask0_pack_weights(P.m0_w, P.m0_pack, lane);
-        return;
-    }
-    if constexpr (FUSED) cgs_stagger<8, CGS_STAGGER_DEC_FWD>();
     if (CGS_STAMP_PTR(P.dbg) && tid == 0) CGS_STAMP_PTR(P.dbg)[(size_t)blockIdx.x * 16] = __builtin_amdgcn_s_memtime();
     const int l15 = lane & 15, kq = lane >> 4;
     // the first image's loads are requested before the set-up (and the next image's as soon as the tiles are filled)
@@ -686,6 +705,25 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
         conv3x3_body_pipe<FDec0P>(PC, 2 * (int)blockIdx.x, dec_conv_smem);
     }
     if (CGS_STAMP_PTR(P.dbg) && tid == 0) CGS_STAMP_PTR(P.dbg)[(size_t)blockIdx.x * 16 + 15] = __builtin_amdgcn_s_memtime();
+#undef DEC_FWD_FETCH
+}
+
+template <bool FUSED, bool H16 = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) tail_dec_fwd_kernel(TailDecFwdParams P, ConvParams PC) {
+    static_assert(!H16 || !FUSED, "fp16 operands: the stand-alone inference form");
+    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailDecFwdParams) + sizeof(ConvParams)>();
+    extern __shared__ __attribute__((aligned(16))) float4 dec_conv_smem[];     // FUSED: dec_model.0's tiles + weights
+    __shared__ __attribute__((aligned(16))) float t1[T1F::FLOATS];
+    __shared__ __attribute__((aligned(16))) float t2[T8x24::FLOATS];
+    __shared__ __attribute__((aligned(16))) float t3[T4x48::FLOATS];
+    __shared__ __attribute__((aligned(16))) float w2s[kDecW2sFloats];
+    __shared__ float part[4][16][16];
+    if ((int)blockIdx.x == P.nblocks) {          // the rider workgroup (launched only when m0_pack is given)
+        if (threadIdx.x < 64) mask0_pack_weights(P.m0_w, P.m0_pack, threadIdx.x);
+        return;
+    }
+    if constexpr (FUSED) cgs_stagger<8, CGS_STAGGER_DEC_FWD>();
+    tail_dec_fwd_body<FUSED, H16>(P, PC, DecFwdLds{dec_conv_smem, t1, t2, t3, w2s, part});
 }
 
 extern "C" int cgs_tail_dec_fwd_pack(int32_t n, const cgs_tail_dec_weights* w, const float* e1, const float* e2, const float* e3,
@@ -719,6 +757,79 @@ extern "C" int cgs_tail_dec_fwd_dec0(int32_t n, const cgs_tail_dec_weights* w, c
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(conv_lds_bytes<FDec0P>()));
     if (attr != hipSuccess) return (int)attr;
     hipLaunchKernelGGL(tail_dec_fwd_kernel<true>, dim3(n + (m0_pack ? 1 : 0)), dim3(256), lds, (hipStream_t)stream, P, PC);
+    CGS_HIP_CHECK_LAUNCH();
+    return CGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// decoder forward AND mask head forward of an image in one workgroup (round 7; nets.py:503-521, 488-491; uint8 frames):
+//   phase D = tail_dec_fwd_kernel<true>'s body (dec_model.3 / .2 / .1 / .0; o3, o2, o1, o0 to memory as before: the backward reads them),
+//   phase M = mask_fwd_kernel<SRC_U8C3>'s body (mask_fwd_body.h; h, Z, zpart), reading o0 back from THIS workgroup's stores behind a barrier
+//             (__syncthreads waits for the stores: the same hand-over as o1 -> dec_model.0 inside phase D).
+// Both phases are one workgroup per image at two per CU, so neither loses occupancy; their LDS is ONE block, aliased.  Same operands in the same
+// order as the two kernels: bit-identical outputs (tests/test_gpu_dec_mask_fused.py).
+// CGS_DEC_MASK_HOIST: phase M's prologue that does not depend on o0 (40 weight registers, w2, the first strip's frame fetch) is requested BEFORE
+// phase D.  CGS_STAGGER_DEC_MASK: s_sleep units of the phase stagger (cgs_stagger; 0 = none).
+// ------------------------------------------------------------------------------------------------
+#ifndef CGS_DEC_MASK_HOIST
+#define CGS_DEC_MASK_HOIST 1
+#endif
+#ifndef CGS_STAGGER_DEC_MASK
+#define CGS_STAGGER_DEC_MASK 0
+#endif
+namespace {
+constexpr int kDmConvF4 = (int)(conv_lds_bytes<FDec0P>() / sizeof(float4));
+static_assert(T1F::FLOATS % 4 == 0 && T8x24::FLOATS % 4 == 0 && T4x48::FLOATS % 4 == 0, "16-byte aligned slices");
+constexpr int kDmDecFloats = 4 * kDmConvF4 + T1F::FLOATS + T8x24::FLOATS + T4x48::FLOATS + kDecW2sFloats + 4 * 16 * 16;
+constexpr int kDmMaskFloats = 4 * kMaskStageF4 + kMaskWinFloats + 8;
+constexpr int kDmF4 = ((kDmDecFloats > kDmMaskFloats ? kDmDecFloats : kDmMaskFloats) + 3) / 4;
+unsigned long long* g_dec_mask_stamps = nullptr;     // debug: phase M's stamps of the fused kernel (tools/maskfwd_stamps.py --fused); phase D's go to g_tail_stamps
+}
+#ifdef CGS_DEBUG_STAMPS
+extern "C" int dbg_dec_mask_stamps(unsigned long long* stamps) { g_dec_mask_stamps = stamps; return CGS_OK; }
+#endif
+
+__global__ void __launch_bounds__(256, 2) dec_mask_fwd_kernel(TailDecFwdParams P, ConvParams PC, MaskFwdParams M) {
+    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailDecFwdParams) + sizeof(ConvParams) + sizeof(MaskFwdParams)>();
+    __shared__ __attribute__((aligned(16))) float4 lds[kDmF4];
+    float* const f = (float*)lds;
+    float* const t1 = f + 4 * kDmConvF4;
+    float* const t2 = t1 + T1F::FLOATS;
+    float* const t3 = t2 + T8x24::FLOATS;
+    float* const w2s = t3 + T4x48::FLOATS;
+    const DecFwdLds S{lds, t1, t2, t3, w2s, (float (*)[16][16])(w2s + kDecW2sFloats)};
+    float* const win = f + 4 * kMaskStageF4;
+    cgs_stagger<8, CGS_STAGGER_DEC_MASK>();
+    auto phase_d = [&] {
+        tail_dec_fwd_body<true, false>(P, PC, S);
+        __syncthreads();        // o0 of this image is in memory, and phase D's LDS is free
+    };
+    if constexpr (CGS_DEC_MASK_HOIST) {
+        mask_fwd_body<SRC_U8C3, true, true>(M, lds, win, win + kMaskWinFloats, phase_d);
+    } else {
+        phase_d();
+        mask_fwd_body<SRC_U8C3, false, true>(M, lds, win, win + kMaskWinFloats, [] {});
+    }
+}
+
+// cgs_tail_dec_fwd_dec0 + cgs_mask_train_fwd_packed in ONE launch (uint8 frames; fp32 frames and n > 1024: CGS_ERR_UNSUPPORTED, the caller keeps the two
+// launches).  m0_pack [40 * 64] must already hold masker.0's weight registers (cgs_critic_fwd_fused_pack's rider, or cgs_tail_dec_fwd_pack's).
+extern "C" int cgs_dec_mask_fwd(int32_t n, const cgs_tail_dec_weights* w, const float* e0, const float* e1, const float* e2, const float* e3,
+                                const float* o4, float* o3, float* o2, float* o1, const float* w0, const float* b0, float* o0, int32_t src_a,
+                                const void* x, const float* b_m0, const float* w_m2, const float* b_m2, float* h, float* z, float* zpart,
+                                const float* m0_pack, cgs_stream_t stream) {
+    if (n < 0 || !w || !e0 || !e1 || !e2 || !e3 || !o4 || !o3 || !o2 || !o1 || !w0 || !b0 || !o0) return CGS_ERR_BADARG;
+    if (!x || !b_m0 || !w_m2 || !b_m2 || !h || !z || !zpart || !m0_pack) return CGS_ERR_BADARG;
+    if (!w->w3 || !w->b3 || !w->w2 || !w->b2 || !w->w1 || !w->b1) return CGS_ERR_BADARG;
+    if (src_a != CGS_SRC_U8 && src_a != CGS_SRC_F32) return CGS_ERR_BADARG;
+    if (src_a != CGS_SRC_U8) return CGS_ERR_UNSUPPORTED;
+    if (n == 0) return CGS_OK;
+    if (n > tail_fwd_cap()) return CGS_ERR_UNSUPPORTED;
+    TailDecFwdParams P{*w, e1, e2, e3, o4, o3, o2, o1, n, n, g_tail_stamps ? g_tail_stamps + 1 * 2048 * 16 : nullptr, nullptr, nullptr};
+    ConvParams PC{};
+    PC.src_a = e0; PC.src_b = o1; PC.w = w0; PC.bias = b0; PC.out = o0; PC.n = n;
+    MaskFwdParams M{x, o0, nullptr, b_m0, w_m2, b_m2, h, z, zpart, n, g_dec_mask_stamps, m0_pack};
+    hipLaunchKernelGGL(dec_mask_fwd_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, P, PC, M);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
 }

@@ -231,8 +231,14 @@ class HourglassEngine:
         fm_ptr = self.fm.data_ptr()
         pw = (C.c_void_p(fm_ptr + 4 * self.lm.off("dec_model.4.weight")), C.c_void_p(fm_ptr + 4 * self.lm.off("dec_model.4.bias")),
               self._o4_full)
+        # (where the decoder and the mask head run as one launch below, the mask head's packed weights are built by a spare workgroup here)
+        m0 = None
+        if hg.ENC0_MIX_FUSED and hg.dec_mask_fwd_fused(n, self.ab.dtype == torch.uint8) and hg.critic_fwd_whole(False, True):
+            if self.mbuf.get("m0pack") is None:
+                self.mbuf["m0pack"] = torch.empty(40 * 64, device=self.dev, dtype=torch.float32)
+            m0 = (C.c_void_p(fm_ptr + 4 * self.lm.off("masker.0.weight")), self.mbuf["m0pack"])
         hg.critic_forward(self.fc, self.lc, self.ab, 2 * n, drop.shifted(0), out=self._cview(0, 2 * n),
-                          pw=None if self.separate else pw)
+                          pw=None if self.separate else pw, m0=m0)
         sa = self._cview(n, 2 * n)
         if self.separate:     # main.py:389-390: the masker's inputs come from the second critic's pass over A
             pws = (pw[0], pw[1], self.mbuf["o4"])
@@ -241,7 +247,7 @@ class HourglassEngine:
         else:
             embeds = [sa[f"e{i}"] for i in range(5)]
         hg.masker_forward(self.fm, self.lm, A, embeds, n, out=self.mbuf, o4_done=True,
-                          zpart=self.zsum if hg.ENC0_MIX_FUSED else None)
+                          zpart=self.zsum if hg.ENC0_MIX_FUSED else None, m0pack_done=m0 is not None)
         if hg.ENC0_MIX_FUSED:
             # the mixes are virtual: features.0 computes them in its tile loaders (forward here, weight gradient below); the
             # mask layer left the (sum |z|, sum z^2) partials in self.zsum

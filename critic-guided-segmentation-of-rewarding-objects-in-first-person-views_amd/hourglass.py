@@ -49,10 +49,24 @@ DEC_TAIL_DEC0_FUSED = True
 ENC1_TAIL_BWD_FUSED = os.environ.get("CGS_ENC1_TAIL_BWD_FUSED", "1") != "0"      # (A/B switch for tools/; the product default is on)
 # ... for passes of this many images or more (same measurement: N = 64: -11 us, 128: -5, 192: -3, 256: +1 without it)
 ENC1_TAIL_BWD_FUSED_MIN_N = int(os.environ.get("CGS_ENC1_TAIL_BWD_FUSED_MIN_N", "224"))
+# the decoder forward (tail + dec_model.0) and the training mask head forward of an image as ONE launch (tail.hip: dec_mask_fwd_kernel, round 7): taken
+# where DEC_TAIL_DEC0_FUSED and mask_train_fused(n) hold and the frames are uint8; the mask head's packed weights then come from a spare workgroup of
+# the critic's forward over [B | A], the launch before.  (A/B switch for tools/ like CGS_ENC1_TAIL_BWD_FUSED)
+DEC_MASK_FWD_FUSED = os.environ.get("CGS_DEC_MASK_FWD_FUSED", "1") != "0"
 
 
 def mask_train_fused(n: int) -> bool:
     return MASK_TRAIN_FUSED and n >= MASK_TRAIN_FUSED_MIN_N
+
+
+def critic_fwd_whole(mixin: bool, u8: bool) -> bool:
+    """Does critic_forward run the whole forward as one launch (cgs_critic_fwd_fused)?  Not for fp32 frames."""
+    return TAIL_FWD and ENC1_TAIL_FUSED and CRITIC_FWD_FUSED and (mixin or u8)
+
+
+def dec_mask_fwd_fused(n: int, u8: bool) -> bool:
+    """Does the training masker forward of n images take the one-launch decoder + mask head form (given the packed weights, see masker_forward)?"""
+    return DEC_MASK_FWD_FUSED and TAIL_FWD and DEC_TAIL_DEC0_FUSED and mask_train_fused(n) and u8
 
 
 def enc1_tail_bwd_fused(n: int) -> bool:
@@ -241,10 +255,12 @@ class SlabPlan:
 # critic
 # ------------------------------------------------------------------------------------------------
 def critic_forward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, drop: DropState = NO_DROP,
-                   out: Optional[Dict[str, torch.Tensor]] = None, pw=None) -> Dict[str, torch.Tensor]:
+                   out: Optional[Dict[str, torch.Tensor]] = None, pw=None, m0=None) -> Dict[str, torch.Tensor]:
     """x: NHWC uint8 or NHWC fp32 [n,64,64,3].  Returns pooled embeds e0..e3 (pre-dropout), their argmax
     masks am0..am3, e4 [n,32], h1 [n,32], pred [n].  ``out`` may hold preallocated views to fill.
-    pw = (w_ptr, b_ptr, o4[n,32]): also emit the decoder's bottleneck 1x1 conv of e4 (dec_model.4) from the head kernel."""
+    pw = (w_ptr, b_ptr, o4[n,32]): also emit the decoder's bottleneck 1x1 conv of e4 (dec_model.4) from the head kernel.
+    m0 = (masker.0 weight ptr, m0pack [40 * 64]): a spare workgroup of the launch also packs the mask head forward's weight registers
+    (uint8 frames in the one-launch form only, critic_fwd_whole: the caller asks for it only there)."""
     mixin = isinstance(x, MixInput)
     u8 = (not mixin) and x.dtype == torch.uint8
     if not mixin:
@@ -253,7 +269,9 @@ def critic_forward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, dro
     dev = x.device
     o = out if out is not None else {}
     src = x
-    whole = TAIL_FWD and ENC1_TAIL_FUSED and CRITIC_FWD_FUSED and (mixin or u8)      # the whole forward in one launch (not for fp32 frames)
+    whole = critic_fwd_whole(mixin, u8)      # the whole forward in one launch (not for fp32 frames)
+    if m0 is not None and (mixin or not whole):
+        raise _lib.CgsError("critic_forward: m0 (the mask head's packed weights) rides only in the one-launch form on uint8 frames")
     for i, (key, hw, ca, cb, co, ups, act, pool, site) in enumerate(ENC_LAYERS):
         e = o.get(f"e{i}")
         if e is None:
@@ -280,10 +298,14 @@ def critic_forward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, dro
         if whole:
             k0, k3 = ENC_LAYERS[0][0], ENC_LAYERS[1][0]
             wp_ = lambda k: C.c_void_p(flat.data_ptr() + 4 * lay.off(k))
-            _lib.call("cgs_critic_fwd_fused", n, C.byref(tw), x.ptr() if mixin else _p(x), int(mixin), wp_(k0 + ".weight"), wp_(k0 + ".bias"),
-                      _p(o["e0"]), _p(o["am0"]), wp_(k3 + ".weight"), wp_(k3 + ".bias"), _p(o["e1"]), _p(o["am1"]), _p(o["e2"]), _p(o["am2"]),
-                      _p(o["e3"]), _p(o["am3"]), _p(o["e4"]), _p(o["h1"]), _p(o["pred"]), _p(pw[2]) if pw else None,
-                      drop.desc(DROP_SITE_E2, True, 128), drop.desc(DROP_SITE_E3, True, 64), drop.desc(DROP_SITE_H1, True, 8), _stream())
+            args = (n, C.byref(tw), x.ptr() if mixin else _p(x), int(mixin), wp_(k0 + ".weight"), wp_(k0 + ".bias"),
+                    _p(o["e0"]), _p(o["am0"]), wp_(k3 + ".weight"), wp_(k3 + ".bias"), _p(o["e1"]), _p(o["am1"]), _p(o["e2"]), _p(o["am2"]),
+                    _p(o["e3"]), _p(o["am3"]), _p(o["e4"]), _p(o["h1"]), _p(o["pred"]), _p(pw[2]) if pw else None,
+                    drop.desc(DROP_SITE_E2, True, 128), drop.desc(DROP_SITE_E3, True, 64), drop.desc(DROP_SITE_H1, True, 8))
+            if m0 is not None:
+                _lib.call("cgs_critic_fwd_fused_pack", *args, m0[0], _p(m0[1]), _stream())
+            else:
+                _lib.call("cgs_critic_fwd_fused", *args, _stream())
             return o
         if ENC1_TAIL_FUSED:
             k3 = ENC_LAYERS[1][0]
@@ -559,13 +581,15 @@ def critic_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, sa
 def masker_forward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, embeds: List[torch.Tensor], n: int,
                    out: Optional[Dict[str, torch.Tensor]] = None, o4_done: bool = False,
                    keep_hm: bool = True, fp16_mask_head: bool = False,
-                   zpart: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                   zpart: Optional[torch.Tensor] = None, m0pack_done: bool = False) -> Dict[str, torch.Tensor]:
     """x: NHWC uint8/fp32 image [n,64,64,3]; embeds = [e0,e1,e2,e3 (NHWC), e4 [n,32]].
     Returns o4 [n,32], o3..o0, hm [n,64,64,16], Z [n,64,64].  o4_done: out['o4'] was already produced by the critic's
     head kernel (critic_forward(..., pw=...)), skip the stand-alone 1x1 conv.  keep_hm=False (inference): the 16-channel
     masker.0 output is not needed afterwards -- masker.0 and masker.2 run as one kernel and 'hm' is never stored;
     fp16_mask_head (with keep_hm=False only, opt-in): that kernel's masker.0 GEMM takes fp16 operands (~1e-3 abs in Z).
-    zpart [zpart_count(n), 2] (training): the mask layer also leaves its per-tile (sum |z|, sum z^2) there for the L1/L2 losses."""
+    zpart [zpart_count(n), 2] (training): the mask layer also leaves its per-tile (sum |z|, sum z^2) there for the L1/L2 losses.
+    m0pack_done: out['m0pack'] was already built by an earlier launch (critic_forward(..., m0=...)); where dec_mask_fwd_fused(n, u8) holds the
+    decoder and the mask head then run as ONE launch (cgs_dec_mask_fwd), bit-identical to the two."""
     u8 = x.dtype == torch.uint8
     _chk(x, torch.uint8 if u8 else torch.float32, "masker image input")
     _chk_img(x, n, "masker image input")
@@ -596,6 +620,21 @@ def masker_forward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, embeds: Lis
             m0pack = o.get("m0pack")
             if m0pack is None:
                 m0pack = o["m0pack"] = torch.empty(40 * 64, device=dev, dtype=torch.float32)
+        if m0pack_done and keep_hm and zpart is not None and dec_mask_fwd_fused(n, u8):
+            assert o.get("m0pack") is not None, "m0pack_done: the caller's critic launch already built out['m0pack']"
+            for k, shp in (("o0", (n, 32, 32, 8)), ("hm", (n, 64, 64, 16)), ("Z", (n, 64, 64))):
+                if o.get(k) is None:
+                    o[k] = torch.empty(shp, device=dev, dtype=torch.float32)
+            wp_ = lambda k: C.c_void_p(fp + 4 * lay.off(k))
+            rc = _lib.load().cgs_dec_mask_fwd(n, C.byref(tw), _p(embeds[0]), _p(embeds[1]), _p(embeds[2]), _p(embeds[3]), _p(o["o4"]),
+                                              _p(o["o3"]), _p(o["o2"]), _p(o["o1"]), wp_("dec_model.0.weight"), wp_("dec_model.0.bias"), _p(o["o0"]),
+                                              _lib.SRC_U8, _p(x), wp_("masker.0.bias"), wp_("masker.2.weight"), wp_("masker.2.bias"),
+                                              _p(o["hm"]), _p(o["Z"]), _p(zpart), _p(o["m0pack"]), _stream())
+            if rc == 0:
+                return o
+            if rc != _lib.ERR_UNSUPPORTED:
+                _lib.check(rc, "cgs_dec_mask_fwd")
+            # beyond the library's cap: the two launches below
         dec0_done = False
         if DEC_TAIL_DEC0_FUSED:
             # one workgroup per image up to the library's own cap (tail_fwd_cap in csrc/tail.hip): beyond it the entry point answers

@@ -265,6 +265,13 @@ int cgs_critic_fwd_fused(int32_t n, const cgs_tail_enc_weights* w, const void* x
                          float* e0, uint32_t* am0, const float* w3, const float* b3, float* e1, uint32_t* am1, float* e2, uint32_t* am2,
                          float* e3, uint32_t* am3, float* e4, float* h1, float* pred, float* o4, cgs_dropout drop_e2, cgs_dropout drop_e3,
                          cgs_dropout drop_h1, cgs_stream_t stream);
+/* The same + (m0_pack != NULL; uint8 frames only, else CGS_ERR_BADARG) one extra workgroup that packs masker.0's HWIO weights w_m0 [9][11][16] into
+ * the mask head forward's weight registers m0_pack [40 * 64], as cgs_tail_dec_fwd_pack's spare workgroup does (byte for byte): the launch in front
+ * of cgs_dec_mask_fwd on the training path.                                                                                              */
+int cgs_critic_fwd_fused_pack(int32_t n, const cgs_tail_enc_weights* w, const void* x, int32_t x_is_mix, const float* w0, const float* b0,
+                              float* e0, uint32_t* am0, const float* w3, const float* b3, float* e1, uint32_t* am1, float* e2, uint32_t* am2,
+                              float* e3, uint32_t* am3, float* e4, float* h1, float* pred, float* o4, cgs_dropout drop_e2, cgs_dropout drop_e3,
+                              cgs_dropout drop_h1, const float* w_m0, float* m0_pack, cgs_stream_t stream);
 int cgs_tail_dec_fwd(int32_t n, const cgs_tail_dec_weights* w, const float* e1, const float* e2, const float* e3,
                      const float* o4, float* o3, float* o2, float* o1, cgs_stream_t stream);
 /* (round 6, BASELINE config 4: main.py:1130-1151 with fp16 conv kernels) cgs_tail_enc_fwd in eval mode / cgs_tail_dec_fwd with fp16 OPERANDS in
@@ -392,6 +399,15 @@ int cgs_dec0_tail_dec_bwd_do3(int32_t n, const cgs_tail_dec_weights* w, const fl
 int cgs_tail_dec_fwd_dec0(int32_t n, const cgs_tail_dec_weights* w, const float* e0, const float* e1, const float* e2, const float* e3,
                           const float* o4, float* o3, float* o2, float* o1, const float* w0_hwio, const float* b0, float* o0,
                           const float* w_m0, float* m0_pack, cgs_stream_t stream);
+/* cgs_tail_dec_fwd_dec0 and cgs_mask_train_fwd_packed in ONE launch, one workgroup per image (round 7; nets.py:503-521, 488-491): the decoder
+ * (dec_model.3 / .2 / .1 / .0 -> o3, o2, o1, o0, all stored) and then the mask head (masker.0 + LeakyReLU + masker.2 + sigmoid -> h [n,64,64,16],
+ * z [n,64,64], zpart [n][2]) of the same image, bit-identical to the two launches.  x: uint8 frames [n,64,64,3] (src_a = CGS_SRC_U8); for
+ * CGS_SRC_F32 and for n > 1024 the answer is CGS_ERR_UNSUPPORTED and the caller keeps the two launches.  m0_pack [40 * 64] (required) holds
+ * masker.0's weight registers, built by an EARLIER launch (cgs_critic_fwd_fused_pack / cgs_tail_dec_fwd_pack).                              */
+int cgs_dec_mask_fwd(int32_t n, const cgs_tail_dec_weights* w, const float* e0, const float* e1, const float* e2, const float* e3,
+                     const float* o4, float* o3, float* o2, float* o1, const float* w0_hwio, const float* b0, float* o0, int32_t src_a,
+                     const void* x, const float* b_m0, const float* w_m2, const float* b_m2, float* h, float* z, float* zpart,
+                     const float* m0_pack, cgs_stream_t stream);
 
 /* ---- convolution backward, weights --------------------------------------------------
  * Replaces convolution_backward(weight, bias).  Each workgroup writes one partial "slab"
