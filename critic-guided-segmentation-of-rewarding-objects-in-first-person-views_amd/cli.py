@@ -55,12 +55,14 @@ def build_parser():
     p.add_argument("--fit-range", type=float, default=None)
     # (this build's own flags) -process --source-video IN --overlay-video OUT: the frames of a video file (decoded by ffmpeg) instead of a
     # folder of stills, through the -fit machinery, and the masks drawn on the frames at the frames' size as a video (overlay.py).
-    # --smooth R filters the masks along time over +-R frames first (temporal.py; 0 = off), --smooth-range is its colour sigma.  The
-    # defaults (0, 16, overlay, 0,255,0, 0.5, 1) are filled in by check_video_flags, which has to see what was given
+    # --smooth R filters the masks along time over +-R frames first (temporal.py; 0 = off), --smooth-range is its colour sigma,
+    # --smooth-motion S lets its taps follow block-matched motion of up to S cells a frame (0 = off).  The defaults (0, 16, 0, overlay,
+    # 0,255,0, 0.5, 1) are filled in by check_video_flags, which has to see what was given
     p.add_argument("--source-video", type=str, default="")
     p.add_argument("--overlay-video", type=str, default="")
     p.add_argument("--smooth", type=int, default=None)
     p.add_argument("--smooth-range", type=float, default=None)
+    p.add_argument("--smooth-motion", type=int, default=None)
     p.add_argument("--overlay-layout", type=str, default=None)
     p.add_argument("--overlay-color", type=str, default=None)
     p.add_argument("--overlay-alpha", type=float, default=None)
@@ -211,11 +213,12 @@ def check_fit_flags(args):
 
 def check_video_flags(args):
     """--source-video / --overlay-video and the --smooth* / --overlay-* options: combinations that could not run and values out of range
-    are refused here, before any GPU work; the defaults (--smooth 0, --smooth-range 16, --overlay-layout overlay, --overlay-color
-    0,255,0, --overlay-alpha 0.5, --overlay-outline 1) are filled in, --overlay-color becomes (r, g, b), args.overlay_alpha256 is
+    are refused here, before any GPU work; the defaults (--smooth 0, --smooth-range 16, --smooth-motion 0, --overlay-layout overlay,
+    --overlay-color 0,255,0, --overlay-alpha 0.5, --overlay-outline 1) are filled in, --overlay-color becomes (r, g, b), args.overlay_alpha256 is
     round(256 alpha), and -fit is switched on: a video goes through the -fit machinery.  The frame size is checked after the probe
     (check_video_size)."""
     given = [f for f, v in (("--overlay-video", args.overlay_video or None), ("--smooth", args.smooth), ("--smooth-range", args.smooth_range),
+                            ("--smooth-motion", args.smooth_motion),
                             ("--overlay-layout", args.overlay_layout), ("--overlay-color", args.overlay_color),
                             ("--overlay-alpha", args.overlay_alpha), ("--overlay-outline", args.overlay_outline)) if v is not None]
     if not args.source_video:
@@ -237,6 +240,9 @@ def check_video_flags(args):
     args.smooth = temporal.check_radius(0 if args.smooth is None else args.smooth, least=0, name="--smooth")
     _, args.smooth_range = check_sigmas(1.0, temporal.SIGMA_RANGE if args.smooth_range is None else args.smooth_range,
                                         names=("", "--smooth-range"))
+    args.smooth_motion = temporal.check_search(0 if args.smooth_motion is None else args.smooth_motion, least=0, name="--smooth-motion")
+    if args.smooth_motion and not args.smooth:
+        raise ValueError("--smooth-motion steers the taps of --smooth: give --smooth R")
     def named(flag, fn, value):
         try:
             return fn(value)

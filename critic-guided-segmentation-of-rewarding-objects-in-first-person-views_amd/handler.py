@@ -564,9 +564,9 @@ class Handler:
         of at most 128 frames and about 256 MB at a time (video_in.read_chunks).  Two stages, so that the smoother has its lookahead:
           A  upload, fit.down, the network exactly as _segment_fit feeds it;
           B  --smooth R > 0: temporal.smooth over a rolling device stack -- the last R frames before the chunk, the chunk, the first R
-             after it, with their shrunk frames -- then fit.up (the grey byte, and the hard mask at --binarymaskthreshold, inclusive; no
-             hard mask and so no outline at threshold 0), overlay.compose, an asynchronous copy into a pinned double buffer and the
-             encoder (video.ffmpeg_argv with the probed rate).
+             after it, with their shrunk frames, with --smooth-motion S > 0 along temporal.flow of that same window -- then fit.up (the
+             grey byte, and the hard mask at --binarymaskthreshold, inclusive; no hard mask and so no outline at threshold 0),
+             overlay.compose, an asynchronous copy into a pinned double buffer and the encoder (video.ffmpeg_argv with the probed rate).
         Stage A of chunk c + 1 runs before stage B of chunk c (a chunk waits until R frames after it are there, or the stream has ended).
         No PNG is written.  Rank 0 leaves {R}/{stem of OUT}.json.  Returns the 64 x 64 masks [n,1,64,64], the smoothed ones with --smooth."""
         from collections import deque
@@ -578,7 +578,7 @@ class Handler:
         k = args.overlay_panels
         cli.check_video_size(W, H, k)                  # before the first frame is decoded
         fp16 = bool(getattr(args, "fp16", False))
-        thr, R = args.binarymaskthreshold, args.smooth
+        thr, R, S = args.binarymaskthreshold, args.smooth, getattr(args, "smooth_motion", 0)
         self.critic.eval()
         self.masker.eval()
         eng = self._engine(2 * 32)
@@ -594,6 +594,8 @@ class Handler:
         writer = video.FrameWriter(proc.stdin, (H, k * W, 3), step)
         pending = deque()                              # chunks through stage A, waiting for stage B: (guide, low, Z)
         tail = None                                    # (Z, low) of the last R frames before the first pending chunk, unsmoothed
+        # --smooth-motion: the forward vectors' summed length and the number of saturated ones, on the device; the number of vectors
+        moved, vectors = torch.zeros(2, dtype=torch.float64, device=self.device) if S else None, 0
 
         def stage_a(host):
             guide = torch.from_numpy(host).to(self.device)        # (a blocking copy: the reader may refill the buffer afterwards)
@@ -601,7 +603,7 @@ class Handler:
             return guide, low, process.fit_infer(eng, low, unit, fp16, bool(args.noevalmode)).contiguous().clone()
 
         def stage_b():
-            nonlocal tail
+            nonlocal tail, moved, vectors
             guide, low, Z = pending.popleft()
             if R:
                 zs, ls = [Z], [low]
@@ -617,7 +619,13 @@ class Handler:
                     zs.insert(0, tail[0])
                     ls.insert(0, tail[1])
                     f0 = len(tail[0])
-                Zs = temporal.smooth(torch.cat(zs), torch.cat(ls), R, args.smooth_range, f0, f0 + len(Z))
+                zw, lw, motion = torch.cat(zs), torch.cat(ls), None
+                if S:
+                    motion = temporal.flow(lw, S)
+                    own = motion[0][max(f0 - 1, 0):f0 + len(Z) - 1].to(torch.float64)      # the pairs that end in this chunk: each pair once
+                    moved = moved + torch.stack((own.pow(2).sum(dim=-1).sqrt().sum(), (own.abs().amax(dim=-1) >= S).sum().to(torch.float64)))
+                    vectors += own.shape[0] * own.shape[1] * own.shape[2]
+                Zs = temporal.smooth(zw, lw, R, args.smooth_range, f0, f0 + len(Z), motion=motion)
                 before = (torch.cat((tail[0], Z)), torch.cat((tail[1], low))) if tail is not None else (Z, low)
                 tail = (before[0][-R:], before[1][-R:])
             else:
@@ -658,10 +666,15 @@ class Handler:
         print()
         M = np.concatenate(masks, axis=0)
         stem = os.path.basename(out_path).rsplit(".", 1)[0]
+        smooth = {"radius": R, "sigma_t": temporal.sigma_t(R), "sigma_range": args.smooth_range} if R else None
+        if R and S:                                    # (the one host sync of the motion figures)
+            length, saturated = moved.tolist()
+            smooth["motion"] = {"search": S, "block": temporal.BLOCK, "mean_cells_per_frame": length / max(vectors, 1),
+                                "saturated": saturated / max(vectors, 1)}
         write_json(f"{out_dir}/{stem}.json", {
             "frame_size": [H, W], "frames": len(M), "rate": rate, "layout": args.overlay_layout, "color": list(args.overlay_color),
             "alpha256": args.overlay_alpha256, "outline": args.overlay_outline, "threshold": thr,
-            "smooth": {"radius": R, "sigma_t": temporal.sigma_t(R), "sigma_range": args.smooth_range} if R else None,
+            "smooth": smooth,
             "sigma_spatial": args.fit_spatial, "sigma_range": args.fit_range}, self.rank)
         return M
 

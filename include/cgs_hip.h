@@ -1083,6 +1083,51 @@ int cgs_overlay_compose(const uint8_t* guide, const uint8_t* grey, const uint8_t
                         int32_t g, int32_t b, int32_t alpha256, int32_t thickness, int32_t layout, int32_t flags, uint8_t* out,
                         cgs_stream_t stream);
 
+/* ---- block-matched motion for the temporal filter (csrc/temporal_motion.hip; -process --source-video --smooth R --smooth-motion S) -------
+ * cgs_temporal_smooth looks, for a tap in frame f + k, at the 3 x 3 cells around the cell's own position whatever k is; under a camera pan
+ * of a few cells a frame those taps leave the object and the range term switches them off.  These two entries estimate the motion of
+ * whole cells between neighbouring frames and let the taps follow it.  Both run on `stream` without synchronising, allocate nothing, use
+ * no global atomics, are deterministic and can be captured in a graph.
+ *
+ * cgs_temporal_flow: one integer vector per block of CGS_TEMPORAL_BLOCK x CGS_TEMPORAL_BLOCK cells and pair of neighbouring frames.
+ *   low     uint8 [n][64][64][3]: cgs_fit_down_u8 of the frames
+ *   search  S, 1 .. CGS_TEMPORAL_MAX_SEARCH cells each way
+ *   fwd     int8 [n - 1][8][8][2], components (dy, dx): fwd[g][by][bx] = the d, |dy|, |dx| <= S, that minimises
+ *             SAD(d) = sum over the 64 cells q of block (by, bx) and the colours c of |low[g][q][c] - low[g + 1][q + d][c]|   (an integer)
+ *           among the candidates whose displaced block lies entirely inside the grid ((0, 0) always does)
+ *   bwd     int8 [n - 1][8][8][2]: the same with frame g + 1 as the source and frame g searched -- not the negation of fwd
+ * The candidates are ranked by ascending dy^2 + dx^2, then dy, then dx, and a later one wins only with a strictly smaller SAD: ties go to
+ * the smallest motion, a constant frame gives all zeros.  (SAD <= 64 * 765 = 48960 and the rank is below 81: SAD << 7 | rank is one
+ * uint32 key and the answer is its minimum.)  A vector depends on its two frames only, so a caller that works in windows gets, pair for
+ * pair, the vectors of the one-call run.
+ * low, fwd, bwd not NULL, n >= 2, search >= 1, else CGS_ERR_BADARG (nothing is launched); then search <= CGS_TEMPORAL_MAX_SEARCH, else
+ * CGS_ERR_UNSUPPORTED.
+ *
+ * cgs_temporal_smooth_mc: cgs_temporal_smooth with the taps of frame f + k centred where the motion carries the cell.
+ *   z, low, n, f0, f1, radius, sigma_r, out   as cgs_temporal_smooth
+ *   fwd, bwd  int8 [n - 1][8][8][2] as cgs_temporal_flow writes them (of the same n frames); not read, and may be NULL, when n == 1
+ * The path of cell p of frame f: m_0 = (0, 0) and, for j = 0 .. k - 1, q = p + m_j with each coordinate clamped into 0 .. 63,
+ *   m_{j+1} = m_j + fwd[f + j][q.y >> 3][q.x >> 3]             (k > 0)
+ *   m_{j+1} = m_j + bwd[f - j - 1][q.y >> 3][q.x >> 3]         (k < 0, j = 0 .. |k| - 1)
+ * The taps are those of cgs_temporal_smooth IN THE SAME ORDER -- the centre tap (f, p) with weight exactly 1, then k = -radius .. -1, 1 ..
+ * radius ascending with 0 <= g = f + k < n, dy = -1, 0, 1 (outer), dx = -1, 0, 1 (inner) -- at the cell t = p + m_k + (dy, dx) of frame g
+ * when t lies inside the grid (skipped, not clamped, otherwise; p + m_k itself may lie outside):
+ *   w = exp(-(k^2 / (2 sigma_t^2) + (dy^2 + dx^2) / 2 + d2 / (2 sigma_r^2))),  d2 = |low[g][t] - low[f][p]|^2 (an integer),
+ *   num = fma(w, z[g][t], num),  den = den + w,  out = num / den (the IEEE division).
+ * The spatial term counts (dy, dx) only, not m_k: following the motion costs no weight.  The arithmetic and its order are those of
+ * cgs_temporal_smooth, so all-zero fields give its output bit for bit; den >= 1, 0 <= out <= 1, ones in give 1.0f out, and with `radius`
+ * frames of halo a window gives the one-call result bit for bit, as there.  No read is out of range for any int8 content of the fields;
+ * components beyond +-CGS_TEMPORAL_MAX_SEARCH are the caller's error and merely move the taps further.  Compensated: translation by whole
+ * cells, up to S cells a frame, one vector per 8 x 8 block.  Not compensated: motion inside a block, sub-cell motion, occlusion (no
+ * forward / backward consistency check) -- there the range term is what is left.  Block 8 and S <= 4 are judgements, not tuned results.
+ * As cgs_temporal_smooth: z, low, out not NULL, n >= 1, 0 <= f0 < f1 <= n, radius >= 1, sigma_r > 0 and finite, z / out 4-byte aligned,
+ * and fwd, bwd not NULL when n > 1, else CGS_ERR_BADARG (nothing is launched); then radius <= CGS_TEMPORAL_MAX_RADIUS, else
+ * CGS_ERR_UNSUPPORTED.                                                                                                                    */
+enum { CGS_TEMPORAL_BLOCK = 8, CGS_TEMPORAL_MAX_SEARCH = 4 };
+int cgs_temporal_flow(const uint8_t* low, int32_t n, int32_t search, int8_t* fwd, int8_t* bwd, cgs_stream_t stream);
+int cgs_temporal_smooth_mc(const float* z, const uint8_t* low, const int8_t* fwd, const int8_t* bwd, int32_t n, int32_t f0, int32_t f1,
+                           int32_t radius, float sigma_r, float* out, cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
