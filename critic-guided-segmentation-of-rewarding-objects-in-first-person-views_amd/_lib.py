@@ -128,7 +128,7 @@ SIGNATURES = {
     "cgs_tail_enc_bwd_slabs": (i32, [i32]),
     "cgs_tail_enc_bwd": (i32, [i32, C.POINTER(TailEncWeights)] + [vp] * 10 + [f32, i32] + [vp] * 4 + [i32] + [vp] * 4 + [Dropout, Dropout, Dropout, vp]),
     "cgs_tail_enc_bwd_rider": (i32, [i32, C.POINTER(TailEncWeights)] + [vp] * 10 + [f32, i32] + [vp] * 4 + [i32] + [vp] * 4 + [Dropout, Dropout, Dropout, i32, vp, vp, vp, vp, i32, vp]),
-    "cgs_tail_enc_bwd_enc1": (i32, [i32, C.POINTER(TailEncWeights)] + [vp] * 10 + [f32, i32] + [vp] * 4 + [i32] + [vp] * 4 + [Dropout, Dropout, Dropout, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "cgs_tail_enc_bwd_enc1": (i32, [i32, C.POINTER(TailEncWeights)] + [vp] * 10 + [f32, i32] + [vp] * 4 + [i32] + [vp] * 4 + [Dropout, Dropout, Dropout, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
     "cgs_enc1_wgrad_rider_slabs": (i32, [i32]),
     "cgs_enc0_wgrad_u8_with_head_enc1": (i32, [i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp]),
     "cgs_enc0_bwd_mix_enc1": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -139,9 +139,6 @@ SIGNATURES = {
     "cgs_tail_dec_bwd_slabs": (i32, [i32]),
     "cgs_tail_dec_bwd": (i32, [i32, C.POINTER(TailDecWeights)] + [vp] * 14 + [vp]),
     "cgs_dec0_tail_dec_bwd": (i32, [i32, C.POINTER(TailDecWeights)] + [vp] * 17 + [vp]),
-    "cgs_dec0_tail_dec_bwd_do3": (i32, [i32, C.POINTER(TailDecWeights)] + [vp] * 18 + [vp]),
-    "cgs_dec3_wgrad_rider_slabs": (i32, [i32]),
-    "cgs_enc0_wgrad_u8_with_head_riders": (i32, [i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "cgs_tail_dec_fwd_dec0": (i32, [i32, C.POINTER(TailDecWeights)] + [vp] * 13 + [vp]),
     "cgs_dec_mask_fwd": (i32, [i32, C.POINTER(TailDecWeights)] + [vp] * 11 + [i32] + [vp] * 8 + [vp]),
     "cgs_conv3x3_bwd_weight_slabs": (i32, [C.POINTER(ConvDesc)]),

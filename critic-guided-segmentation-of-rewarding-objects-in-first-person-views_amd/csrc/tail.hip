@@ -904,14 +904,9 @@ struct TailEncBwdParams {
 #ifndef CGS_ENC1_WGRAD_STAGES
 #define CGS_ENC1_WGRAD_STAGES 1
 #endif
-// MODE 2 / 3 (round 5): ... and features.0's sparse WEIGHT gradient of the same images on the uint8 frames (2) / the virtual mixes (3), after
-// their d e0 has been written: the critic's whole backward pass of an image except features.0's data gradient in one workgroup; the
-// stand-alone launches then hold no weight-gradient role of this pass (cgs_enc0_bwd_mix(slab = NULL), cgs_tail_head_wgrad alone).
-template <int MODE>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) tail_enc_bwd_kernel(TailEncBwdParams P, ConvParams PC, WgradParams PW1,
-                                                                                                       WgradParams PW0) {
-    constexpr bool ENC1 = MODE >= 1;
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailEncBwdParams) + (ENC1 ? sizeof(ConvParams) + sizeof(WgradParams) : 0) + (MODE >= 2 ? sizeof(WgradParams) : 0)>();
+template <bool ENC1>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) tail_enc_bwd_kernel(TailEncBwdParams P, ConvParams PC, WgradParams PW1) {
+    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailEncBwdParams) + (ENC1 ? sizeof(ConvParams) + sizeof(WgradParams) : 0)>();
     // The chain of one image is latency-bound, so: every global load of an image is issued at the top of its iteration (one
     // memory latency instead of one per stage), the head runs redundantly in all waves on shuffles (no single-wave sections),
     // four barriers per image.
@@ -1182,21 +1177,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
         } else {
             enc1_dgrad();
         }
-        if constexpr (MODE >= 2) {
-            if (PW0.slab) {
-                // features.0's weight gradient of this workgroup's images (8 strips each) from the d e0 just written (same workgroup: visible
-                // after the barrier) and the frames / virtual mixes; one slab row per workgroup
-                __syncthreads();
-                int b0 = (int)blockIdx.x, tz = 0;
-                asm volatile("" : "+s"(b0));
-                asm volatile("" : "+v"(tz));
-                const int nb = P.nblocks;
-                const int nimg = b0 < P.n ? (P.n - b0 + nb - 1) / nb : 0;
-                using SP0 = SpCfg<64, 3, MODE == 2 ? WSRC_U8 : WSRC_MIX>;
-                wgrad_sparse_body_seq<SP0>(PW0, [=](int k) { return 8 * (b0 + (k >> 3) * nb) + (k & 7); }, 8 * nimg,
-                                           PW0.slab + (size_t)b0 * ((9 * 3 + 1) * 8), (float4*)lds_all, tz);
-            }
-        }
     }
     if (CGS_STAMP_PTR(P.dbg) && tid == 0) CGS_STAMP_PTR(P.dbg)[(size_t)blockIdx.x * 16 + 15] = __builtin_amdgcn_s_memtime();
 }
@@ -1213,7 +1193,7 @@ static int tail_enc_bwd_launch(int32_t n, const cgs_tail_enc_weights* w, const f
                                const float* dE2, const float* dE3, const float* d_o4, int32_t n_add, float* de1, float* hvec,
                                float* slab10, float* slab6, cgs_dropout drop_e2, cgs_dropout drop_e3, cgs_dropout drop_h1,
                                int32_t n_r, const float* e0_r, const float* o1_r, const float* dy_r, float* slab_r, int32_t nslab_r,
-                               const ConvParams* enc1, const WgradParams* enc1w, const WgradParams* enc0w, int enc0_mix, cgs_stream_t stream) {
+                               const ConvParams* enc1, const WgradParams* enc1w, cgs_stream_t stream) {
     if (n < 0 || !w || !e1 || !e2 || !am2 || !e3 || !am3 || !e4 || !h1 || !pred || !de1) return CGS_ERR_BADARG;
     if (!w->w6 || !w->w10 || !w->w14 || !w->wl1 || !w->wl2) return CGS_ERR_BADARG;
     if (d_o4 && !w->wpw) return CGS_ERR_BADARG;
@@ -1224,11 +1204,9 @@ static int tail_enc_bwd_launch(int32_t n, const cgs_tail_enc_weights* w, const f
                        WDec0Params{e0_r, o1_r, dy_r, slab_r, n_r, n_r * kStrips}};
     const int riders = slab_r ? nslab_r : 0;
     const dim3 grid(tail_blocks(n, tail_enc_bwd_cap()) + riders);
-    const WgradParams w1 = enc1w ? *enc1w : WgradParams{}, w0 = enc0w ? *enc0w : WgradParams{};
-    if (enc1 && enc0w && enc0_mix) hipLaunchKernelGGL(tail_enc_bwd_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, P, *enc1, w1, w0);
-    else if (enc1 && enc0w) hipLaunchKernelGGL(tail_enc_bwd_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, P, *enc1, w1, w0);
-    else if (enc1) hipLaunchKernelGGL(tail_enc_bwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, P, *enc1, w1, w0);
-    else hipLaunchKernelGGL(tail_enc_bwd_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, P, ConvParams{}, w1, w0);
+    const WgradParams w1 = enc1w ? *enc1w : WgradParams{};
+    if (enc1) hipLaunchKernelGGL(tail_enc_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, P, *enc1, w1);
+    else hipLaunchKernelGGL(tail_enc_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, P, ConvParams{}, w1);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
 }
@@ -1241,7 +1219,7 @@ extern "C" int cgs_tail_enc_bwd_rider(int32_t n, const cgs_tail_enc_weights* w, 
                                       int32_t n_r, const float* e0_r, const float* o1_r, const float* dy_r, float* slab_r, int32_t nslab_r,
                                       cgs_stream_t stream) {
     return tail_enc_bwd_launch(n, w, e1, e2, am2, e3, am3, e4, h1, pred, dpred, target, loss_scale, bce, dE1, dE2, dE3, d_o4, n_add, de1, hvec,
-                               slab10, slab6, drop_e2, drop_e3, drop_h1, n_r, e0_r, o1_r, dy_r, slab_r, nslab_r, nullptr, nullptr, nullptr, 0, stream);
+                               slab10, slab6, drop_e2, drop_e3, drop_h1, n_r, e0_r, o1_r, dy_r, slab_r, nslab_r, nullptr, nullptr, stream);
 }
 
 // cgs_tail_enc_bwd_rider AND features.3's data gradient (the data-gradient half of cgs_conv3x3_bwd_both for the 8 -> 8 layer at 32x32 with
@@ -1255,31 +1233,16 @@ extern "C" int cgs_tail_enc_bwd_enc1(int32_t n, const cgs_tail_enc_weights* w, c
                                      float* slab10, float* slab6, cgs_dropout drop_e2, cgs_dropout drop_e3, cgs_dropout drop_h1,
                                      int32_t n_r, const float* e0_r, const float* o1_r, const float* dy_r, float* slab_r, int32_t nslab_r,
                                      const uint32_t* am1, const float* w_enc1, const float* addend0, int32_t n_addend, float* de0,
-                                     const float* e0, float* slab1,
-                                     int32_t x_kind, const void* x, const uint32_t* am0, float* slab0, cgs_stream_t stream) {
+                                     const float* e0, float* slab1, cgs_stream_t stream) {
     if (!am1 || !w_enc1 || !de0 || n_addend < 0 || (n_addend > 0 && !addend0) || (slab1 && !e0)) return CGS_ERR_BADARG;
-    if (slab0 && (!x || !am0 || (x_kind != CGS_SRC_U8 && x_kind != CGS_SRC_MIX))) return CGS_ERR_BADARG;
-    if (slab0 && wgrad_sparse_lds_bytes<SpCfg<64, 3, WSRC_U8>>() > sizeof(float) * (size_t)kTailEncBwdLdsFloats) return CGS_ERR_UNSUPPORTED;
     if (conv_lds_bytes<DEnc1P>() > sizeof(float) * (size_t)kTailEncBwdLdsFloats) return CGS_ERR_UNSUPPORTED;
     if (wgrad_sparse_lds_bytes<SpCfg<32, 8, WSRC_F32>>() > sizeof(float) * (size_t)kTailEncBwdLdsFloats) return CGS_ERR_UNSUPPORTED;
     ConvParams pd{};
     pd.src_a = de1; pd.amask_in = am1; pd.w = w_enc1; pd.out = de0; pd.addend = addend0; pd.n_addend = n_addend; pd.n = n;
     WgradParams pw{};
     pw.src_a = e0; pw.dy = de1; pw.amask = am1; pw.slab = slab1; pw.n = n; pw.ntiles = 2 * n;
-    WgradParams p0{};
-    if (slab0) {
-        p0.dy = de0; p0.amask = am0; p0.slab = slab0; p0.n = n; p0.ntiles = 8 * n;
-        if (x_kind == CGS_SRC_MIX) {
-            const cgs_mix_src* m = (const cgs_mix_src*)x;
-            if (!m->a || !m->b || !m->z || m->n_a <= 0 || (n != m->n_a && n != 2 * m->n_a)) return CGS_ERR_BADARG;
-            p0.mix_a = m->a; p0.mix_b = m->b; p0.mix_z = m->z; p0.mix_n_a = m->n_a;
-        } else {
-            p0.src_a = x;
-        }
-    }
     return tail_enc_bwd_launch(n, w, e1, e2, am2, e3, am3, e4, h1, pred, dpred, target, loss_scale, bce, dE1, dE2, dE3, d_o4, n_add, de1, hvec,
-                               slab10, slab6, drop_e2, drop_e3, drop_h1, n_r, e0_r, o1_r, dy_r, slab_r, nslab_r, &pd, &pw, slab0 ? &p0 : nullptr,
-                               x_kind == CGS_SRC_MIX, stream);
+                               slab10, slab6, drop_e2, drop_e3, drop_h1, n_r, e0_r, o1_r, dy_r, slab_r, nslab_r, &pd, &pw, stream);
 }
 
 extern "C" int cgs_tail_enc_bwd(int32_t n, const cgs_tail_enc_weights* w, const float* e1, const float* e2, const uint32_t* am2,
@@ -1335,7 +1298,6 @@ struct TailDecBwdParams {
     int n;
     int nblocks;
     unsigned long long* dbg;
-    float* do3;           // W3 = false: d o3 [n,4,4,16] for the dec_model.3 weight-gradient riders
 };
 
 using T1Q = TileP<16, 16, 16, 16, 304>;   // cat(e1, up(o2)): only the weight gradient's dword reads (2 taps x 4 channel groups on 32 banks)
@@ -1351,9 +1313,7 @@ struct TailDecBwdLds {
 // gradient d e0 and the cell-summed d o1 go to memory as cgs_conv3x3_bwd_data writes them; the tile region of this kernel is its
 // scratch), then the tail stages read that d o1 back (same workgroup: visible after the barrier).  Every other co-resident workgroup
 // starts ~4 us late, so the latency-bound chains of one half run under the matrix instructions of the other (cgs_stagger).
-// W3 = false (round 5): dec_model.3's weight gradient is NOT formed here -- d o3 [n,4,4,16] goes to P.do3 and a few rider workgroups of a later launch
-// form it as a GEMM over the images (wgrad_dec3.h): 64 slab rows of 27.7 KB instead of one per image.
-template <bool FUSED, bool W3 = true>
+template <bool FUSED>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) tail_dec_bwd_kernel(TailDecBwdParams P, ConvParams PC) {
     if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailDecBwdParams) + sizeof(ConvParams)>();
     using L = TailDecBwdLds;
@@ -1490,15 +1450,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             wave, lane_i);
         __syncthreads();
         TAIL_STAMP(4);
-        if constexpr (!W3) {
-            if (tid < 64) {
-                const int p4 = tid & 3, x = (tid >> 2) & 3, y = tid >> 4;
-                ((float4*)P.do3)[(size_t)img * 64 + tid] = *(const float4*)(dy3 + T4x16::at(y, x) + 4 * p4);
-            }
-        }
         // ---- dec_model.3: weight gradient on the matrix cores; data gradient on the vector ALU (48 input channels x 4 quads:
         //      thread = (ci, quad), weights read in their natural [tap][ci][co] order, 16 contiguous floats per (tap, ci)) ----
-        if constexpr (W3) wg3.accumulate(t3, dy3, lane_i);
+        wg3.accumulate(t3, dy3, lane_i);
         // (round 6) dec_model.3's data gradient on the matrix cores (it was 576 multiply-adds per thread on the vector ALU behind nine dependent L2
         // round trips for the weights: 16.5 k of the kernel's 105 k cycles by the stamps).  GEMM: M = the 16 pixels of the 4x4 map (four 2x2 quads),
         // N = 48 input channels = one 16-column block per wave (waves 0, 1, 2), K = 9 taps x 16 channels of d o3; the B operand (W^T, flipped taps) sits
@@ -1547,7 +1501,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     __syncthreads();
     if (tid < 8 && P.slab1) P.slab1[b * kTailSlabD1 + 1152 + tid] = (red[tid * 4] + red[tid * 4 + 1]) + (red[tid * 4 + 2] + red[tid * 4 + 3]);
     if (P.slab2) wg2.store(P.slab2 + b * kTailSlabD2, wave, lane);
-    if constexpr (W3) { if (P.slab3) wg3.store(P.slab3 + b * kTailSlabD3, wave, lane); }
+    if (P.slab3) wg3.store(P.slab3 + b * kTailSlabD3, wave, lane);
     if (CGS_STAMP_PTR(P.dbg) && tid == 0) CGS_STAMP_PTR(P.dbg)[(size_t)blockIdx.x * 16 + 15] = __builtin_amdgcn_s_memtime();
 }
 
@@ -1571,14 +1525,11 @@ extern "C" int cgs_tail_dec_bwd(int32_t n, const cgs_tail_dec_weights* w, const 
 // dec_model.0's data gradient (cgs_conv3x3_bwd_data of the 16 -> 8 layer at 32x32: dy = d o0 [n,32,32,8] -> d e0 [n,32,32,8] and the
 // cell-summed d o1 [n,16,16,8]) AND cgs_tail_dec_bwd in one launch, one workgroup per image (n <= cgs_tail_dec_bwd_slabs' cap: the
 // tail's slabs are one row per image).  w0: dec_model.0's HWIO weights.  CGS_ERR_UNSUPPORTED for larger n (the caller launches the two).
-// do3 != NULL (round 5; then slab3 must be NULL): dec_model.3's weight gradient is left to the riders of cgs_enc0_wgrad_u8_with_head_riders --
-// this launch writes d o3 [n,4,4,16] for them instead of one 27.7 KB slab row per image.
-extern "C" int cgs_dec0_tail_dec_bwd_do3(int32_t n, const cgs_tail_dec_weights* w, const float* dy_o0, const float* w0, float* dE0, const float* e1,
-                                         const float* e2, const float* e3, const float* o4, const float* o3, const float* o2, float* do1,
-                                         float* dE1, float* dE2, float* dE3, float* d_o4, float* slab3, float* slab2, float* slab1,
-                                         float* do3, cgs_stream_t stream) {
+extern "C" int cgs_dec0_tail_dec_bwd(int32_t n, const cgs_tail_dec_weights* w, const float* dy_o0, const float* w0, float* dE0, const float* e1,
+                                     const float* e2, const float* e3, const float* o4, const float* o3, const float* o2, float* do1,
+                                     float* dE1, float* dE2, float* dE3, float* d_o4, float* slab3, float* slab2, float* slab1,
+                                     cgs_stream_t stream) {
     if (n < 0 || !w || !dy_o0 || !w0 || !dE0 || !e1 || !e2 || !e3 || !o4 || !o3 || !o2 || !do1 || !dE1 || !dE2 || !dE3 || !d_o4) return CGS_ERR_BADARG;
-    if (do3 && slab3) return CGS_ERR_BADARG;
     if (!w->w3 || !w->w2 || !w->w1) return CGS_ERR_BADARG;
     if (n == 0) return CGS_OK;
     if (n > tail_bwd_cap()) return CGS_ERR_UNSUPPORTED;
@@ -1587,21 +1538,10 @@ extern "C" int cgs_dec0_tail_dec_bwd_do3(int32_t n, const cgs_tail_dec_weights* 
     static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_dec_bwd_kernel<true>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)TailDecBwdLds::BYTES);
     if (attr != hipSuccess) return (int)attr;
-    static hipError_t attr3 = hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_dec_bwd_kernel<true, false>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)TailDecBwdLds::BYTES);
-    if (attr3 != hipSuccess) return (int)attr3;
-    TailDecBwdParams P{*w, e1, e2, e3, o4, o3, o2, do1, dE1, dE2, dE3, d_o4, slab3, slab2, slab1, n, n, g_tail_stamps ? g_tail_stamps + 3 * 2048 * 16 : nullptr, do3};
+    TailDecBwdParams P{*w, e1, e2, e3, o4, o3, o2, do1, dE1, dE2, dE3, d_o4, slab3, slab2, slab1, n, n, g_tail_stamps ? g_tail_stamps + 3 * 2048 * 16 : nullptr};
     ConvParams PC{};
     PC.src_a = dy_o0; PC.w = w0; PC.out = dE0; PC.out2 = do1; PC.n = n;
-    if (do3) hipLaunchKernelGGL((tail_dec_bwd_kernel<true, false>), dim3(n), dim3(256), TailDecBwdLds::BYTES, (hipStream_t)stream, P, PC);
-    else hipLaunchKernelGGL((tail_dec_bwd_kernel<true, true>), dim3(n), dim3(256), TailDecBwdLds::BYTES, (hipStream_t)stream, P, PC);
+    hipLaunchKernelGGL(tail_dec_bwd_kernel<true>, dim3(n), dim3(256), TailDecBwdLds::BYTES, (hipStream_t)stream, P, PC);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
-}
-
-extern "C" int cgs_dec0_tail_dec_bwd(int32_t n, const cgs_tail_dec_weights* w, const float* dy_o0, const float* w0, float* dE0, const float* e1,
-                                     const float* e2, const float* e3, const float* o4, const float* o3, const float* o2, float* do1,
-                                     float* dE1, float* dE2, float* dE3, float* d_o4, float* slab3, float* slab2, float* slab1,
-                                     cgs_stream_t stream) {
-    return cgs_dec0_tail_dec_bwd_do3(n, w, dy_o0, w0, dE0, e1, e2, e3, o4, o3, o2, do1, dE1, dE2, dE3, d_o4, slab3, slab2, slab1, nullptr, stream);
 }

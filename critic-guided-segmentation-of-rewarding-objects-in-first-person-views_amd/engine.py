@@ -88,7 +88,6 @@ class HourglassEngine:
         n4 = 4 * n
         self.ab = z(2 * n, 64, 64, 3, dt=torch.uint8)       # [B | A]
         self.y = z(n)
-        self.mixed = None if hg.ENC0_MIX_FUSED else z(2 * n, 64, 64, 3)      # [replaced | injected] (virtual on the fused path)
         self.cbuf: Dict[str, torch.Tensor] = {}              # critic activations for the 4N slots
         for i, (key, hw, ca, cb, co, *_r) in enumerate(ENC_LAYERS):
             self.cbuf[f"e{i}"] = z(n4, hw // 2, hw // 2, co)
@@ -100,20 +99,19 @@ class HourglassEngine:
                 self.sbuf[f"e{i}"] = z(n, hw // 2, hw // 2, co)
                 self.sbuf[f"am{i}"] = z(n, hw // 2, hw // 2, co // 8, dt=torch.int32)
             self.sbuf["e4"], self.sbuf["h1"], self.sbuf["pred"] = z(n, 32), z(n, 32), z(n)
-            self._zero_dpred = z(n)
         self.mbuf: Dict[str, torch.Tensor] = {}
-        # partial sums of |Z| and Z^2: from the mask layer's workgroups (4 per image) or from cgs_mix_fwd's
-        self.nzpart = hg.zpart_count(n) if hg.ENC0_MIX_FUSED else _lib.load().cgs_mix_fwd_partials(n, 4096)
+        # partial sums of |Z| and Z^2 from the mask layer's workgroups
+        self.nzpart = hg.zpart_count(n)
         self.zsum, self.losses, self.dpred = z(2 * self.nzpart), z(8), z(n4)
-        self.dmixed = None if hg.ENC0_MIX_FUSED else z(2 * n, 64, 64, 3)
         self.dzpre = z(n, 64, 64)
         self._ws = {"mb": {}, "cb_mix": {}, "cb_a": {}, "cb_sep": {}, "p1": {}}
         self._infer_step = z(1, dt=torch.int64)              # -noevalmode: Dropout stream of inference batches
         self._ticket = z(4096, dt=torch.int32)               # cgs_reduce_adam's last-workgroup counters (1 + one per job row)
         # the loss gradients at pred are derived inside the tail backward kernels and the step ends in ONE launch: slab reduction
         # + loss values + Adam on one GPU; under data parallelism slab reduction + loss values, then the all-reduce, then ONE Adam
-        # launch (round 3: the data-parallel step is the single-GPU step + one launch + the collective)
-        self.fused_tail = hg.TAIL_BWD
+        # launch (round 3: the data-parallel step is the single-GPU step + one launch + the collective).  (GenericEngine, whose steps end in
+        # separate reduction and Adam launches, sets this to False.)
+        self.fused_tail = True
         self._graphs: Dict[str, object] = {}
         self._forms: Dict[str, dict] = {}                    # data parallel: the captured launch forms of a step kind (set_dp_launch_form)
         # parameter version (shared by engines that share the parameters): the fp16 inference path repacks its weight copies when it moves
@@ -176,17 +174,16 @@ class HourglassEngine:
         lib = _lib.load()
         out1, out2 = {}, {}
         nd = _lib.Dropout(0.0, 0, 0, None, 0, 0)
-        tail = hg.TAIL_BWD       # head / features.10 / features.6 slabs then come from the tail kernel's workgroups
-        # (tail path: the head's slabs come from ONE cgs_tail_head_wgrad launch over both passes, allocated there)
-        specs = [] if tail else [("slab_head", lambda n, first: lib.cgs_head_bwd_slabs(n), hg.HEAD_SLAB)]
+        # (the head's slabs come from ONE cgs_tail_head_wgrad launch over both passes, allocated there)
+        specs = []
         for i, (key, hw, ca, cb, co, ups, act, pool, site) in enumerate(ENC_LAYERS):
             def f(n, first, i=i, hw=hw, ca=ca, cb=cb, co=co, ups=ups, act=act, pool=pool):
                 d = hg.conv_desc(n, hw, ca, cb, co, False, ups, act, pool, nd)
                 # mirrors critic_backward: features.0 shares a launch with its data gradient only in the first pass
                 # (fp32 mixes, image gradient wanted); the second pass reads uint8 frames and needs no image gradient
                 in_tail1 = hg.enc1_tail_bwd_fused(n) and hg.ENC1_WGRAD_IN_TAIL and 1 in hg.BOTH_ENC
-                # features.3 / features.0: weight gradients formed inside the tail backward kernel (first pass = the mixes, second = A's frames)
-                if tail and (i >= 2 or (i == 1 and in_tail1) or (i == 0 and in_tail1 and tag == "p2" and hg.enc0_in_tail(first, not first, None))):
+                # features.10 / features.6 (and features.3, in_tail1): weight gradients formed inside the tail backward kernel
+                if i >= 2 or (i == 1 and in_tail1):
                     return lib.cgs_tail_enc_bwd_slabs(n)
                 if i in hg.BOTH_ENC and (i > 0 or first):
                     return lib.cgs_conv3x3_bwd_both_slabs(C.byref(d))
@@ -233,7 +230,7 @@ class HourglassEngine:
               self._o4_full)
         # (where the decoder and the mask head run as one launch below, the mask head's packed weights are built by a spare workgroup here)
         m0 = None
-        if hg.ENC0_MIX_FUSED and hg.dec_mask_fwd_fused(n, self.ab.dtype == torch.uint8) and hg.critic_fwd_whole(False, True):
+        if hg.dec_mask_fwd_fused(n, self.ab.dtype == torch.uint8) and hg.critic_fwd_whole(False, True):
             if self.mbuf.get("m0pack") is None:
                 self.mbuf["m0pack"] = torch.empty(40 * 64, device=self.dev, dtype=torch.float32)
             m0 = (C.c_void_p(fm_ptr + 4 * self.lm.off("masker.0.weight")), self.mbuf["m0pack"])
@@ -247,25 +244,17 @@ class HourglassEngine:
         else:
             embeds = [sa[f"e{i}"] for i in range(5)]
         hg.masker_forward(self.fm, self.lm, A, embeds, n, out=self.mbuf, o4_done=True,
-                          zpart=self.zsum if hg.ENC0_MIX_FUSED else None, m0pack_done=m0 is not None)
-        if hg.ENC0_MIX_FUSED:
-            # the mixes are virtual: features.0 computes them in its tile loaders (forward here, weight gradient below); the
-            # mask layer left the (sum |z|, sum z^2) partials in self.zsum
-            mixsrc = hg.MixInput(A, B, self.mbuf["Z"])
-            hg.critic_forward(self.fc, self.lc, mixsrc, nmix, drop.shifted(2 * n), out=self._cview(2 * n, 2 * n + nmix))
-        else:
-            mixsrc = self.mixed[:nmix]
-            _lib.call("cgs_mix_fwd", n, 4096, _P(A), _P(B), _P(self.mbuf["Z"]), int(self.inject), _P(self.mixed), _P(self.zsum), _S())
-            hg.critic_forward(self.fc, self.lc, mixsrc, nmix, drop.shifted(2 * n), out=self._cview(2 * n, 2 * n + nmix))
+                          zpart=self.zsum, m0pack_done=m0 is not None)
+        # the mixes are virtual: features.0 computes them in its tile loaders (forward here, weight gradient below); the
+        # mask layer left the (sum |z|, sum z^2) partials in self.zsum
+        mixsrc = hg.MixInput(A, B, self.mbuf["Z"])
+        hg.critic_forward(self.fc, self.lc, mixsrc, nmix, drop.shifted(2 * n), out=self._cview(2 * n, 2 * n + nmix))
         flags = (1 if self.live else 0) | (2 if self.inject else 0) | (4 if self.bce else 0) | (0 if self.staticnorm else 8)
-        ft = self.fused_tail
-        if not ft:
-            _lib.call("cgs_phase2_losses", n, _P(self.cbuf["pred"]), _P(self.y), _P(self.zsum), self.nzpart, self.lfak, self.L1, self.L2,
-                      flags, n * 4096, _P(self.losses), _P(self.dpred), _S())
-        # (fused tail) targets of the three loss terms: replaced -> pred of B, injected -> pred of A (slots [B | A] = the first 2n
-        # entries of pred, aligned with the mix slots [rep | inj]); A -> y with weight lfak (or BCE)
-        loss_mix = (self.cbuf["pred"][:nmix], 1.0 / n, False) if ft else None
-        loss_a = (self.y, self.lfak / n, self.bce) if ft else None
+        # the tail backward kernels derive the loss gradients at pred themselves.  Targets of the three loss terms: replaced -> pred of B,
+        # injected -> pred of A (slots [B | A] = the first 2n entries of pred, aligned with the mix slots [rep | inj]); A -> y with
+        # weight lfak (or BCE)
+        loss_mix = (self.cbuf["pred"][:nmix], 1.0 / n, False)
+        loss_a = (self.y, self.lfak / n, self.bce)
         plan = self._plans.get("p2")
         first = plan is None
         if first:
@@ -274,46 +263,37 @@ class HourglassEngine:
             self._ws["cb_mix"].update(self._sl_mix)
             self._ws["cb_a"].update(self._sl_a)
         pc = plan if first else hg.SlabPlan()   # job registration only matters the first time
-        sink_c = [] if hg.TAIL_BWD else None     # the critic's passes whose head weight gradients are formed together below
+        sink_c = []      # the critic's passes whose head weight gradients are formed together below
         # critic backward on the mixes: image gradient for the mask path (+ weight gradients when live)
         nz = float(n * 4096)
-        if hg.ENC0_MIX_FUSED:
-            # features.0's backward carries the mix backward: the image gradients of the mixes never leave the chip
-            hg.critic_backward(self.fc, self.lc, mixsrc, nmix, self._cview(2 * n, 2 * n + nmix),
-                               None if ft else self.dpred[2 * n:2 * n + nmix], pc, drop.shifted(2 * n), dx=None, dx_from=0,
-                               ws=self._ws["cb_mix"], side=self.side, need_wgrad=self.live, loss=loss_mix, head_sink=sink_c,
-                               mix_bwd=(A, B, self.mbuf["Z"], self.inject, self.L1 / nz, self.L2 / nz, self.dzpre,
-                                        None if self.staticnorm else sa["pred"]))
-        else:
-            hg.critic_backward(self.fc, self.lc, self.mixed[:nmix], nmix, self._cview(2 * n, 2 * n + nmix),
-                               self.dpred[2 * n:2 * n + nmix], pc, drop.shifted(2 * n), dx=self.dmixed[:nmix], dx_from=0,
-                               ws=self._ws["cb_mix"], side=self.side, need_wgrad=self.live)
-            _lib.call("cgs_mix_bwd", n, 4096, _P(A), _P(B), _P(self.mbuf["Z"]), _P(self.dmixed), int(self.inject),
-                      self.L1 / nz, self.L2 / nz, _P(self.dzpre), _S())
+        # features.0's backward carries the mix backward: the image gradients of the mixes never leave the chip
+        hg.critic_backward(self.fc, self.lc, mixsrc, nmix, self._cview(2 * n, 2 * n + nmix), None, pc, drop.shifted(2 * n), dx=None, dx_from=0,
+                           ws=self._ws["cb_mix"], side=self.side, need_wgrad=self.live, loss=loss_mix, head_sink=sink_c,
+                           mix_bwd=(A, B, self.mbuf["Z"], self.inject, self.L1 / nz, self.L2 / nz, self.dzpre,
+                                    None if self.staticnorm else sa["pred"]))
         pm = hg.SlabPlan()
         # live: the 1x1 bottleneck conv's backward runs inside the critic head kernel (frozen: no critic backward on A,
         # the masker does it itself)
         # (live critic, one module: dec_model.0's weight gradient rides in the A pass's tail backward launch below)
-        defer = [] if (self.live and not self.separate and hg.TAIL_BWD) else None
+        defer = [] if (self.live and not self.separate) else None
         d_emb = hg.masker_backward(self.fm, self.lm, A, embeds, n, self.mbuf, self.dzpre, pm, ws=self._ws["mb"], side=self.side,
                                    pw_in_head=self.live or self.separate, defer_dec0=defer)
-        rider = next((d for d in (defer or []) if not isinstance(d, dict)), None)            # dec_model.0's weight gradient (tail launch riders)
-        dec3 = next((d["dec3"] for d in (defer or []) if isinstance(d, dict)), None)          # dec_model.3's (features.0 launch riders)
+        rider = defer[0] if defer else None            # dec_model.0's weight gradient (tail launch riders)
         ps = hg.SlabPlan()
         if self.separate:
             # the skip gradients (and the bottleneck's) go into the SECOND critic; its own head sees no loss (dpred = 0)
             d_o4, d_emb[4] = d_emb[4], None
-            hg.critic_backward(self.fs, self.lc, A, n, self.sbuf, None if ft else self._zero_dpred, ps, drop.shifted(4 * n), d_embeds=d_emb,
+            hg.critic_backward(self.fs, self.lc, A, n, self.sbuf, None, ps, drop.shifted(4 * n), d_embeds=d_emb,
                                n_add=n, ws=self._ws["cb_sep"], side=self.side,
                                pw_bwd=(d_o4, pw[0], pm, self.lm.off("dec_model.4.weight")))
             if self.live:
-                hg.critic_backward(self.fc, self.lc, A, n, sa, None if ft else self.dpred[n:2 * n], pc, drop.shifted(n),
+                hg.critic_backward(self.fc, self.lc, A, n, sa, None, pc, drop.shifted(n),
                                    ws=self._ws["cb_a"], side=self.side, loss=loss_a, head_sink=sink_c)
         elif self.live:
             d_o4, d_emb[4] = d_emb[4], None
-            hg.critic_backward(self.fc, self.lc, A, n, sa, None if ft else self.dpred[n:2 * n], pc, drop.shifted(n), d_embeds=d_emb,
+            hg.critic_backward(self.fc, self.lc, A, n, sa, None, pc, drop.shifted(n), d_embeds=d_emb,
                                n_add=n, ws=self._ws["cb_a"], side=self.side, loss=loss_a, head_sink=sink_c,
-                               pw_bwd=(d_o4, pw[0], pm, self.lm.off("dec_model.4.weight")), rider=rider, dec3_rider=dec3)
+                               pw_bwd=(d_o4, pw[0], pm, self.lm.off("dec_model.4.weight")), rider=rider)
         if sink_c:
             hg.head_wgrad(sink_c, pc, self.lc, self._ws["cb_a"])
         self.side.join()
@@ -327,13 +307,11 @@ class HourglassEngine:
             for slab, nsl, cnt, off in ps.jobs:
                 full.jobs.append((slab, nsl, cnt, self.off_s + off))
             self._plans["p2"] = full.build(self.grad)
-        if ft:      # reduction + Adam + loss values in one launch; the optimiser group is exactly the set of reduced elements
-            # (data parallel: param = None -> reduction + loss values + step tick; the all-reduce and one Adam launch follow)
-            self._plans["p2"].run_adam(self.step_t, None if self.dp else self.flat, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps,
-                                       self._ticket, loss=(n, self.cbuf["pred"], self.y, self.zsum, self.nzpart, self.lfak, self.L1,
-                                                           self.L2, flags, n * 4096, self.losses))
-        else:
-            self._plans["p2"].run(self.step_t)
+        # reduction + Adam + loss values in one launch; the optimiser group is exactly the set of reduced elements
+        # (data parallel: param = None -> reduction + loss values + step tick; the all-reduce and one Adam launch follow)
+        self._plans["p2"].run_adam(self.step_t, None if self.dp else self.flat, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps,
+                                   self._ticket, loss=(n, self.cbuf["pred"], self.y, self.zsum, self.nzpart, self.lfak, self.L1,
+                                                       self.L2, flags, n * 4096, self.losses))
 
     def phase2_step(self, A_u8: Optional[torch.Tensor] = None, B_u8: Optional[torch.Tensor] = None,
                     Y: Optional[torch.Tensor] = None):
@@ -399,7 +377,7 @@ class HourglassEngine:
         first = "p1" not in self._plans
         pc = hg.SlabPlan()
         # (round 5) as phase 2 does: the head's weight gradients in the features.0 weight-gradient launch, reduction + Adam in one launch on one GPU
-        sink = [] if (hg.TAIL_BWD and PHASE1_FUSED_TAIL) else None
+        sink = [] if PHASE1_FUSED_TAIL else None
         hg.critic_backward(self.fc, self.lc, X, n, self._cview(0, n), self.dpred[:n], pc, self.drop.shifted(0), ws=self._ws["p1"],
                            side=self.side, head_sink=sink)
         if sink:

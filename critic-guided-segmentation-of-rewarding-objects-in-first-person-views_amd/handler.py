@@ -27,11 +27,6 @@ from .generic_engine import GenericEngine
 from .nets import NewCritic, UnetDecoder
 
 
-def hg_mix_fused():
-    from . import hourglass
-    return hourglass.ENC0_MIX_FUSED
-
-
 def checkpoint_names(args):
     """Checkpoint file stems of the reference: ``k=v`` joined by '-' for TRUTHY values only (main.py:86-91), e.g.
     critic-rewidx=1-cepochs=15-datamode=trunk-datasize=100000-shift=12-chfak=1-dropout=0.3 / masker-mepochs=1-L1=0.5-inject=True."""
@@ -229,11 +224,9 @@ class Handler:
 
     # ------------------------------------------------------------------ phase 1: critic regression
     def _refuse_unbuilt_flags(self):
-        """Flags the reference reads on this path that this build does not implement: refuse instead of training something else."""
-        a = self.args
-        if not a.staticnorm and not hg_mix_fused():
-            raise NotImplementedError("-staticnorm '' (mask regulariser weighted by 1 - pred, main.py:415-418) needs the fused "
-                                      "features.0 + mix backward (hourglass.ENC0_MIX_FUSED, this build's fixed configuration)")
+        """Flags the reference reads on this path that this build does not implement: refuse instead of training something else.
+        None at present: -staticnorm '' (mask regulariser weighted by 1 - pred, main.py:415-418) runs in the fused features.0 + mix
+        backward, which every step takes."""
 
     def critic_pipe(self, mode="train", test=0):
         args = self.args

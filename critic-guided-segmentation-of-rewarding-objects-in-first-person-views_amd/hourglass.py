@@ -18,24 +18,17 @@ from .spec import (DEC_LAYERS, DROP_SITE_E2, DROP_SITE_E3, DROP_SITE_H1, ENC_LAY
 
 _ACT = {"none": _lib.ACT_NONE, "relu": _lib.ACT_RELU, "lrelu": _lib.ACT_LRELU, "sigmoid": _lib.ACT_SIGMOID}
 HEAD_SLAB = 8192 + 32 + 1024 + 32 + 32 + 1
-# Which kernel forms the step is composed of.  These are the build's fixed configuration (round 3: environment switches removed);
-# the per-layer forms they replaced stay reachable through the C ABI and are parity-tested there (tests/test_gpu_kernels.py).
-# small layers: weight- and data-gradient halves share one launch (csrc/conv_bwd_both.hip)
-BWD_BOTH = True
-MASK_INFER_FUSED = True   # inference: masker.0 + masker.2 in one kernel
-ENC0_MIX_FUSED = True   # features.0 backward + mix backward in one launch
-MASK_HEAD_FUSED = True   # masker.2+masker.0 data gradients in one pass
-# training forward: masker.0 + masker.2 in one kernel on v_mfma_f32_4x4x1 (csrc/mask_fwd.hip, round 3: 68 us vs 60 + 38 us)
-MASK_TRAIN_FUSED = True
-# ... from this many images on: the one-kernel form is one workgroup per image (two per CU), the two-launch form splits an image into strips -- on a
+# Which kernel forms the step is composed of.  The forms without a switch here are the build's fixed configuration: the 16x16-and-smaller
+# layers image by image in one workgroup (csrc/tail.hip), the small layers' weight- and data-gradient halves in one launch
+# (csrc/conv_bwd_both.hip), the mask head's two layers in one kernel forward and backward, features.0's backward carrying the mix backward.
+# The per-layer forms they replaced stay reachable through the C ABI and are parity-tested there (tests/test_gpu_kernels.py).
+# Training forward: masker.0 + masker.2 run as one kernel on v_mfma_f32_4x4x1 (csrc/mask_fwd.hip, round 3: 68 us vs 60 + 38 us) from this many
+# images on: the one-kernel form is one workgroup per image (two per CU), the two-launch form splits an image into strips -- on a
 # 256-CU device the step is faster WITHOUT it at the reference's own batch (r05, tools/ab_flags_n.py: N = 64: -14 us of 257, 128: -5, 192: +9, 256: +14)
 # (this threshold, ENC1_TAIL_BWD_FUSED_MIN_N below, the 768-workgroup caps of the tail kernels and cgs_stagger were all measured on ONE device
 #  shape: MI355X in SPX mode, 8 XCDs x 32 CUs = 256 CUs; on another partitioning they are only a starting point.  The small-batch forms the
 #  reference's N = 64 takes are pinned by the reference's own run: tests/test_gpu_loops.py G9 (34 phase-2 steps) and G12 (48 phase-1 steps).)
 MASK_TRAIN_FUSED_MIN_N = int(os.environ.get("CGS_MASK_TRAIN_FUSED_MIN_N", "160"))
-# the 16x16-and-smaller layers image by image in one workgroup (csrc/tail.hip) instead of one launch per layer
-TAIL_FWD = True
-TAIL_BWD = True
 # features.3 and the encoder tail as ONE launch, one workgroup per image (csrc/tail.hip: tail_enc_fwd_kernel<true>, round 4)
 ENC1_TAIL_FUSED = True
 # ... and features.0 in front of it: the whole critic forward of an image in one workgroup (uint8 frames and virtual mixes)
@@ -56,17 +49,17 @@ DEC_MASK_FWD_FUSED = os.environ.get("CGS_DEC_MASK_FWD_FUSED", "1") != "0"
 
 
 def mask_train_fused(n: int) -> bool:
-    return MASK_TRAIN_FUSED and n >= MASK_TRAIN_FUSED_MIN_N
+    return n >= MASK_TRAIN_FUSED_MIN_N
 
 
 def critic_fwd_whole(mixin: bool, u8: bool) -> bool:
     """Does critic_forward run the whole forward as one launch (cgs_critic_fwd_fused)?  Not for fp32 frames."""
-    return TAIL_FWD and ENC1_TAIL_FUSED and CRITIC_FWD_FUSED and (mixin or u8)
+    return ENC1_TAIL_FUSED and CRITIC_FWD_FUSED and (mixin or u8)
 
 
 def dec_mask_fwd_fused(n: int, u8: bool) -> bool:
     """Does the training masker forward of n images take the one-launch decoder + mask head form (given the packed weights, see masker_forward)?"""
-    return DEC_MASK_FWD_FUSED and TAIL_FWD and DEC_TAIL_DEC0_FUSED and mask_train_fused(n) and u8
+    return DEC_MASK_FWD_FUSED and DEC_TAIL_DEC0_FUSED and mask_train_fused(n) and u8
 
 
 def enc1_tail_bwd_fused(n: int) -> bool:
@@ -74,24 +67,10 @@ def enc1_tail_bwd_fused(n: int) -> bool:
 # ... and features.3's (sparse) weight gradient inside that kernel too, per workgroup over its own images (False: as rider workgroups of the
 # features.0 backward launch, which reproduces cgs_conv3x3_bwd_both's slabs bit for bit but costs 24 us per step, r05k)
 ENC1_WGRAD_IN_TAIL = os.environ.get("CGS_ENC1_WGRAD_IN_TAIL", "1") != "0"
-# ... and features.0's (sparse) weight gradient of the pass in the same kernel as well (uint8 frames / virtual mixes), after the image's d e0:
-# "A" = only the pass over A (features.0's stand-alone weight-gradient launch then holds only the head's GEMM), "mix" = only the mixes' pass
-# (cgs_enc0_bwd_mix then runs without its weight-gradient role), "both", "" = neither.  MEASURED SLOWER, default off (r05n, three interleaved
-# runs: 0.5642 ms without, 0.5649 "A", 0.5717 "mix", 0.5733 "both"): eight 8-row tiles per image lengthen the per-image chain by more than the
-# stand-alone roles cost next to features.0's data gradient.  Kept as an opt-in that the bit-identity test still exercises.
-ENC0_WGRAD_IN_TAIL = os.environ.get("CGS_ENC0_WGRAD_IN_TAIL", "")
-# dec_model.0's weight gradient as spare workgroups of the last critic pass's tail backward launch (live critic; csrc/tail.hip)
-DEC0_WGRAD_RIDER = True
+# dec_model.0's weight gradient rides as this many spare workgroups of the last critic pass's tail backward launch (live critic; csrc/tail.hip)
 DEC0_RIDERS = 256
-# dec_model.3's weight gradient as a GEMM over the images in <= 64 rider workgroups of the A pass's features.0 weight-gradient launch instead of
-# one 27.7 KB slab row per image inside the decoder tail's backward (round 5; equal up to fp32 summation order).  MEASURED SLOWER, default off
-# (r05z: 0.5581 ms with, 0.5508 without): the decoder backward gets 3.7 us shorter and the final reduction reads 12 MB less, but the riders'
-# 8-image chains lengthen the step's last weight-gradient launch by more.  Kept as an opt-in that the bit-identity test still exercises.
-DEC3_WGRAD_RIDER = os.environ.get("CGS_DEC3_WGRAD_RIDER", "0") != "0"
-_both = "c3,c2,c1,c0,d3,d2,d1"   # measured: d0 and m0 do not gain
-BOTH_ENC = {int(t[1]) for t in _both.split(",") if t.startswith("c")} if BWD_BOTH else set()
-BOTH_DEC = {t for t in _both.split(",") if t[0] in "dm"} if BWD_BOTH else set()
-_DEC_TAG = {0: "d3", 1: "d2", 2: "d1", 3: "d0", 4: "m0", 5: "m2"}
+# the encoder layers whose weight- and data-gradient halves share one launch (csrc/conv_bwd_both.hip)
+BOTH_ENC = {3, 2, 1, 0}
 PW_SLAB = 32 * 32 + 32
 
 
@@ -279,7 +258,7 @@ def critic_forward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, dro
         am = o.get(f"am{i}")
         if am is None:
             am = o[f"am{i}"] = torch.empty((n, hw // 2, hw // 2, co // 8), device=dev, dtype=torch.int32)
-        if TAIL_FWD and (i >= 2 or (i == 1 and ENC1_TAIL_FUSED) or (i == 0 and whole)):
+        if i >= 2 or (i == 1 and ENC1_TAIL_FUSED) or (i == 0 and whole):
             src = e
             continue        # features.6 / features.10 / head (and, fused, features.3 / features.0): one tail kernel below
         d = conv_desc(n, hw, ca, cb, co, u8 and i == 0, ups, act, pool, drop.desc(DROP_SITE_E2, site is not None, 128))
@@ -292,48 +271,31 @@ def critic_forward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, dro
     for k, shape in (("e4", (n, 32)), ("h1", (n, 32)), ("pred", (n,))):
         if o.get(k) is None:
             o[k] = torch.empty(shape, device=dev, dtype=torch.float32)
-    if TAIL_FWD:
-        pwp = (pw[0], pw[1]) if pw else None
-        tw = tail_enc_weights(flat, lay, (pwp[0].value, pwp[1].value) if pwp else None)
-        if whole:
-            k0, k3 = ENC_LAYERS[0][0], ENC_LAYERS[1][0]
-            wp_ = lambda k: C.c_void_p(flat.data_ptr() + 4 * lay.off(k))
-            args = (n, C.byref(tw), x.ptr() if mixin else _p(x), int(mixin), wp_(k0 + ".weight"), wp_(k0 + ".bias"),
-                    _p(o["e0"]), _p(o["am0"]), wp_(k3 + ".weight"), wp_(k3 + ".bias"), _p(o["e1"]), _p(o["am1"]), _p(o["e2"]), _p(o["am2"]),
-                    _p(o["e3"]), _p(o["am3"]), _p(o["e4"]), _p(o["h1"]), _p(o["pred"]), _p(pw[2]) if pw else None,
-                    drop.desc(DROP_SITE_E2, True, 128), drop.desc(DROP_SITE_E3, True, 64), drop.desc(DROP_SITE_H1, True, 8))
-            if m0 is not None:
-                _lib.call("cgs_critic_fwd_fused_pack", *args, m0[0], _p(m0[1]), _stream())
-            else:
-                _lib.call("cgs_critic_fwd_fused", *args, _stream())
-            return o
-        if ENC1_TAIL_FUSED:
-            k3 = ENC_LAYERS[1][0]
-            _lib.call("cgs_enc1_tail_fwd", n, C.byref(tw), _p(o["e0"]), C.c_void_p(flat.data_ptr() + 4 * lay.off(k3 + ".weight")),
-                      C.c_void_p(flat.data_ptr() + 4 * lay.off(k3 + ".bias")), _p(o["e1"]), _p(o["am1"]), _p(o["e2"]), _p(o["am2"]), _p(o["e3"]),
-                      _p(o["am3"]), _p(o["e4"]), _p(o["h1"]), _p(o["pred"]), _p(pw[2]) if pw else None, drop.desc(DROP_SITE_E2, True, 128),
-                      drop.desc(DROP_SITE_E3, True, 64), drop.desc(DROP_SITE_H1, True, 8), _stream())
-            return o
-        _lib.call("cgs_tail_enc_fwd", n, C.byref(tw), _p(o["e1"]), _p(o["e2"]), _p(o["am2"]), _p(o["e3"]), _p(o["am3"]),
-                  _p(o["e4"]), _p(o["h1"]), _p(o["pred"]), _p(pw[2]) if pw else None, drop.desc(DROP_SITE_E2, True, 128),
+    pwp = (pw[0], pw[1]) if pw else None
+    tw = tail_enc_weights(flat, lay, (pwp[0].value, pwp[1].value) if pwp else None)
+    if whole:
+        k0, k3 = ENC_LAYERS[0][0], ENC_LAYERS[1][0]
+        wp_ = lambda k: C.c_void_p(flat.data_ptr() + 4 * lay.off(k))
+        args = (n, C.byref(tw), x.ptr() if mixin else _p(x), int(mixin), wp_(k0 + ".weight"), wp_(k0 + ".bias"),
+                _p(o["e0"]), _p(o["am0"]), wp_(k3 + ".weight"), wp_(k3 + ".bias"), _p(o["e1"]), _p(o["am1"]), _p(o["e2"]), _p(o["am2"]),
+                _p(o["e3"]), _p(o["am3"]), _p(o["e4"]), _p(o["h1"]), _p(o["pred"]), _p(pw[2]) if pw else None,
+                drop.desc(DROP_SITE_E2, True, 128), drop.desc(DROP_SITE_E3, True, 64), drop.desc(DROP_SITE_H1, True, 8))
+        if m0 is not None:
+            _lib.call("cgs_critic_fwd_fused_pack", *args, m0[0], _p(m0[1]), _stream())
+        else:
+            _lib.call("cgs_critic_fwd_fused", *args, _stream())
+        return o
+    if ENC1_TAIL_FUSED:
+        k3 = ENC_LAYERS[1][0]
+        _lib.call("cgs_enc1_tail_fwd", n, C.byref(tw), _p(o["e0"]), C.c_void_p(flat.data_ptr() + 4 * lay.off(k3 + ".weight")),
+                  C.c_void_p(flat.data_ptr() + 4 * lay.off(k3 + ".bias")), _p(o["e1"]), _p(o["am1"]), _p(o["e2"]), _p(o["am2"]), _p(o["e3"]),
+                  _p(o["am3"]), _p(o["e4"]), _p(o["h1"]), _p(o["pred"]), _p(pw[2]) if pw else None, drop.desc(DROP_SITE_E2, True, 128),
                   drop.desc(DROP_SITE_E3, True, 64), drop.desc(DROP_SITE_H1, True, 8), _stream())
         return o
-    fp = flat.data_ptr()
-    _lib.call("cgs_head_fwd", n, _p(o["e3"]), C.c_void_p(fp + 4 * lay.off("features.14.weight")),
-              C.c_void_p(fp + 4 * lay.off("features.14.bias")), C.c_void_p(fp + 4 * lay.off("crit.1.weight")),
-              C.c_void_p(fp + 4 * lay.off("crit.1.bias")), C.c_void_p(fp + 4 * lay.off("crit.4.weight")),
-              C.c_void_p(fp + 4 * lay.off("crit.4.bias")), drop.desc(DROP_SITE_E3, True, 64), drop.desc(DROP_SITE_H1, True, 8),
-              _p(o["e4"]), _p(o["h1"]), _p(o["pred"]), pw[0] if pw else None, pw[1] if pw else None,
-              _p(pw[2]) if pw else None, _stream())
+    _lib.call("cgs_tail_enc_fwd", n, C.byref(tw), _p(o["e1"]), _p(o["e2"]), _p(o["am2"]), _p(o["e3"]), _p(o["am3"]),
+              _p(o["e4"]), _p(o["h1"]), _p(o["pred"]), _p(pw[2]) if pw else None, drop.desc(DROP_SITE_E2, True, 128),
+              drop.desc(DROP_SITE_E3, True, 64), drop.desc(DROP_SITE_H1, True, 8), _stream())
     return o
-
-
-def enc0_in_tail(mixin: bool, u8: bool, dx) -> bool:
-    """Does this critic pass form features.0's weight gradient inside its tail backward kernel (ENC0_WGRAD_IN_TAIL)?  Only the two forms the
-    training step uses: the virtual mixes, and uint8 frames without an image gradient."""
-    if mixin:
-        return ENC0_WGRAD_IN_TAIL in ("both", "mix")
-    return u8 and dx is None and ENC0_WGRAD_IN_TAIL in ("both", "A")
 
 
 def head_wgrad(ranges, plan: "SlabPlan", lay: Layout, ws: Dict[str, torch.Tensor]):
@@ -362,14 +324,7 @@ def head_wgrad(ranges, plan: "SlabPlan", lay: Layout, ws: Dict[str, torch.Tensor
     if enc0 is not None:
         n_e, x_e, dy_e, am_e, slab_e = enc0[:5]
         e1w = enc0[5] if len(enc0) > 5 else None          # features.3's deferred weight gradient: (n, e0, d e1, am1, slab, rows)
-        d3 = enc0[6] if len(enc0) > 6 else None           # dec_model.3's deferred weight gradient: (n, e3, o4, d o3, slab)
-        if d3 is not None:
-            w1 = e1w if e1w is not None else (0, None, None, None, None, 0)
-            _lib.call("cgs_enc0_wgrad_u8_with_head_riders", n_e, _p(x_e), _p(dy_e), _p(am_e), _p(slab_e), r0[3], _p(r0[0]), _p(r0[1]), _p(r0[2]),
-                      r0[4], r1[3], _p(r1[0]), _p(r1[1]), _p(r1[2]), r1[4], _p(sl), _p(slpw),
-                      int(w1[0]), _p(w1[1]), _p(w1[2]), _p(w1[3]), _p(w1[4]), int(w1[5]),
-                      int(d3[0]), _p(d3[1]), _p(d3[2]), _p(d3[3]), _p(d3[4]), _stream())
-        elif e1w is not None:
+        if e1w is not None:
             _lib.call("cgs_enc0_wgrad_u8_with_head_enc1", n_e, _p(x_e), _p(dy_e), _p(am_e), _p(slab_e), r0[3], _p(r0[0]), _p(r0[1]), _p(r0[2]),
                       r0[4], r1[3], _p(r1[0]), _p(r1[1]), _p(r1[2]), r1[4], _p(sl), _p(slpw),
                       int(e1w[0]), _p(e1w[1]), _p(e1w[2]), _p(e1w[3]), _p(e1w[4]), int(e1w[5]), _stream())
@@ -389,8 +344,7 @@ def critic_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, sa
                     d_embeds: Optional[List[torch.Tensor]] = None, n_add: int = 0,
                     dx: Optional[torch.Tensor] = None, dx_from: int = 0,
                     ws: Optional[Dict[str, torch.Tensor]] = None, side: "SideStream" = None,
-                    need_wgrad: bool = True, pw_bwd=None, mix_bwd=None, loss=None, head_sink=None, rider=None,
-                    dec3_rider=None) -> Optional[torch.Tensor]:
+                    need_wgrad: bool = True, pw_bwd=None, mix_bwd=None, loss=None, head_sink=None, rider=None) -> Optional[torch.Tensor]:
     """Backward of critic_forward for images [0,n).  pw_bwd = (d_o4 [n_add,32], w_pw_ptr, plan_pw, dst_off): the decoder
     bottleneck's backward (dec_model.4) runs inside the head kernel; its slab is registered in plan_pw at dst_off.
     mix_bwd = (A_u8, B_u8, Z, inject, l1_scale, l2_scale, dzpre): x are the replaced|injected mixes of n_a = len(A) images;
@@ -401,8 +355,6 @@ def critic_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, sa
     # dpred may be None with loss = (target [n], scale, bce): the tail kernel derives d loss / d pred itself
     # (scale * 2 (pred - target), or the BCE form); both None = no loss on this pass's head.  Tail path only.
     mixin = isinstance(x, MixInput)
-    if dpred is None and not TAIL_BWD:
-        raise _lib.CgsError("critic_backward without dpred needs the tail kernels (CGS_TAIL_BWD=1)")
     if mixin and mix_bwd is None:
         raise _lib.CgsError("a MixInput critic input needs mix_bwd (features.0's backward consumes the virtual mixes)")
     u8 = (not mixin) and x.dtype == torch.uint8
@@ -428,9 +380,8 @@ def critic_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, sa
     side = side if side is not None else NO_SIDE
     lib = _lib.load()
     first_layer = 3
-    enc0_done = False        # features.0's weight gradient was formed inside the tail backward kernel (ENC0_WGRAD_IN_TAIL)
     enc1_wgrad = None        # features.3's weight gradient, deferred into this pass's features.0 backward launch (ENC1_TAIL_BWD_FUSED)
-    if TAIL_BWD and not (has_add and d_embeds[4] is not None and pw_bwd is None):
+    if not (has_add and d_embeds[4] is not None and pw_bwd is None):
         # head + features.10 + features.6 backward in one tail kernel: d e1 (skip gradients included)
         use_pw = pw_bwd is not None and has_add
         nsl = lib.cgs_tail_enc_bwd_slabs(n)
@@ -457,14 +408,9 @@ def critic_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, sa
             # features.3's weight gradient inside the same kernel (ENC1_WGRAD_IN_TAIL) or as riders of the features.0 backward launch
             # (one row per tail workgroup; engine._slab_views allocates the two passes' rows adjacent under the same name)
             slab1_in = buf("slab_enc1", (nsl, 9 * 8 * 8 + 8)) if (need_wgrad and ENC1_WGRAD_IN_TAIL) else None
-            slab0_in, xk, xp = None, 0, None
-            if need_wgrad and slab1_in is not None and enc0_in_tail(mixin, u8, dx):
-                slab0_in = buf("slab_enc0", (nsl, 9 * 3 * 8 + 8))
-                xk, xp = (_lib.SRC_MIX, x.ptr()) if mixin else (_lib.SRC_U8, _p(x))
             rc = lib.cgs_tail_enc_bwd_enc1(*targs, _p(saved["am1"]), C.c_void_p(fp + 4 * lay.off("features.3.weight")),
                                            _p(d_embeds[0]) if has_add else None, n_add if has_add else 0, _p(de0),
-                                           _p(saved["e0"]) if slab1_in is not None else None, _p(slab1_in),
-                                           xk, xp, _p(saved["am0"]) if slab0_in is not None else None, _p(slab0_in), _stream())
+                                           _p(saved["e0"]) if slab1_in is not None else None, _p(slab1_in), _stream())
             if rc == 0:
                 fused1 = True
             elif rc != _lib.ERR_UNSUPPORTED:
@@ -482,9 +428,6 @@ def critic_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, sa
                 head_wgrad([rng], plan, lay, ws)
         first_layer = 1
         if fused1:
-            if slab0_in is not None:
-                plan.add(slab0_in, nsl, 9 * 3 * 8 + 8, lay.off("features.0.weight"))
-                enc0_done = True
             if need_wgrad and slab1_in is not None:
                 plan.add(slab1_in, nsl, 9 * 8 * 8 + 8, lay.off("features.3.weight"))
             elif need_wgrad:
@@ -497,7 +440,6 @@ def critic_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, sa
         raise _lib.CgsError("critic_backward: a deferred dec_model.0 weight gradient needs the tail backward launch to ride with")
     # ---- head: d e3 = head gradient (through dropout) + decoder skip gradient ----
     if first_layer == 3:
-      if True:
         nsl = lib.cgs_head_bwd_slabs(n)
         slab = buf("slab_head", (nsl, HEAD_SLAB))
         d_cur = buf("de3", (n, 4, 4, 16))
@@ -523,7 +465,7 @@ def critic_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, sa
             A8, B8, Zm, inj, l1s, l2s, dzp = mix_bwd[:7]
             vfp = mix_bwd[7] if len(mix_bwd) > 7 else None      # -staticnorm '': pred of A, the regulariser's per-image weight
             slab = None
-            if need_wgrad and not enc0_done:
+            if need_wgrad:
                 nsl = lib.cgs_enc0_bwd_mix_slabs(n)
                 slab = buf("slab_enc0", (nsl, cnt))
                 plan.add(slab, nsl, cnt, lay.off(key + ".weight"))
@@ -548,12 +490,12 @@ def critic_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, sa
         nsl = lib.cgs_conv3x3_bwd_weight_slabs(C.byref(d))
         if nsl < 0:
             _lib.check(nsl, "cgs_conv3x3_bwd_weight_slabs")
-        if need_wgrad and not (i == 0 and enc0_done):
+        if need_wgrad:
             slab = buf(f"slab_enc{i}", (nsl, cnt))
             if i == 0 and head_sink is not None and u8:
                 # features.0 on the uint8 frames: launched together with the head's weight gradients (head_wgrad below)
-                head_sink.append({"enc0": (n, src, d_cur, saved["am0"], slab, enc1_wgrad, dec3_rider)})
-                enc1_wgrad, dec3_rider = None, None
+                head_sink.append({"enc0": (n, src, d_cur, saved["am0"], slab, enc1_wgrad)})
+                enc1_wgrad = None
             else:
                 with side.fork():
                     _lib.call("cgs_conv3x3_bwd_weight", C.byref(d), _p(src), None, _p(d_cur), _p(saved[f"am{i}"]), _p(slab), _stream())
@@ -570,8 +512,6 @@ def critic_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, n: int, sa
                       _lib.ACT_NONE, None, 0, _p(dx), None, _stream())
     if enc1_wgrad is not None:
         raise _lib.CgsError("critic_backward: features.3's deferred weight gradient found no features.0 launch to ride with")
-    if dec3_rider is not None:
-        raise _lib.CgsError("critic_backward: dec_model.3's deferred weight gradient found no features.0 launch to ride with")
     return dx
 
 
@@ -606,57 +546,57 @@ def masker_forward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, embeds: Lis
     names = ("o3", "o2", "o1", "o0", "hm", "Z")
     srcs_a = (embeds[3], embeds[2], embeds[1], embeds[0], x, None)
     prev = o["o4"]
-    if fp16_mask_head and (keep_hm or not MASK_INFER_FUSED):
+    if fp16_mask_head and keep_hm:
         raise _lib.CgsError("fp16_mask_head is an inference-only option of the one-kernel mask head (keep_hm=False)")
-    if TAIL_FWD:      # dec_model.3 / .2 / .1 in one tail kernel
-        for nm, shp in (("o3", (n, 4, 4, 16)), ("o2", (n, 8, 8, 8)), ("o1", (n, 16, 16, 8))):
-            if o.get(nm) is None:
-                o[nm] = torch.empty(shp, device=dev, dtype=torch.float32)
-        tw = tail_dec_weights(flat, lay)
-        m0pack = None
-        if (keep_hm and mask_train_fused(n) and zpart is not None) or (not keep_hm and MASK_INFER_FUSED and not fp16_mask_head):
-            # the mask head forward's weight registers, built once by a spare workgroup of this launch (the mask head follows two launches later;
-            # inference runs the same kernel, storing nothing but Z)
-            m0pack = o.get("m0pack")
-            if m0pack is None:
-                m0pack = o["m0pack"] = torch.empty(40 * 64, device=dev, dtype=torch.float32)
-        if m0pack_done and keep_hm and zpart is not None and dec_mask_fwd_fused(n, u8):
-            assert o.get("m0pack") is not None, "m0pack_done: the caller's critic launch already built out['m0pack']"
-            for k, shp in (("o0", (n, 32, 32, 8)), ("hm", (n, 64, 64, 16)), ("Z", (n, 64, 64))):
-                if o.get(k) is None:
-                    o[k] = torch.empty(shp, device=dev, dtype=torch.float32)
-            wp_ = lambda k: C.c_void_p(fp + 4 * lay.off(k))
-            rc = _lib.load().cgs_dec_mask_fwd(n, C.byref(tw), _p(embeds[0]), _p(embeds[1]), _p(embeds[2]), _p(embeds[3]), _p(o["o4"]),
-                                              _p(o["o3"]), _p(o["o2"]), _p(o["o1"]), wp_("dec_model.0.weight"), wp_("dec_model.0.bias"), _p(o["o0"]),
-                                              _lib.SRC_U8, _p(x), wp_("masker.0.bias"), wp_("masker.2.weight"), wp_("masker.2.bias"),
-                                              _p(o["hm"]), _p(o["Z"]), _p(zpart), _p(o["m0pack"]), _stream())
-            if rc == 0:
-                return o
-            if rc != _lib.ERR_UNSUPPORTED:
-                _lib.check(rc, "cgs_dec_mask_fwd")
-            # beyond the library's cap: the two launches below
-        dec0_done = False
-        if DEC_TAIL_DEC0_FUSED:
-            # one workgroup per image up to the library's own cap (tail_fwd_cap in csrc/tail.hip): beyond it the entry point answers
-            # CGS_ERR_UNSUPPORTED and the two-launch form below runs -- the cap is not restated here
-            if o.get("o0") is None:
-                o["o0"] = torch.empty((n, 32, 32, 8), device=dev, dtype=torch.float32)
-            rc = _lib.load().cgs_tail_dec_fwd_dec0(n, C.byref(tw), _p(embeds[0]), _p(embeds[1]), _p(embeds[2]), _p(embeds[3]), _p(o["o4"]),
-                                                   _p(o["o3"]), _p(o["o2"]), _p(o["o1"]), C.c_void_p(fp + 4 * lay.off("dec_model.0.weight")),
-                                                   C.c_void_p(fp + 4 * lay.off("dec_model.0.bias")), _p(o["o0"]),
-                                                   C.c_void_p(fp + 4 * lay.off("masker.0.weight")), _p(m0pack), _stream())
-            if rc == 0:
-                dec0_done = True
-            elif rc != _lib.ERR_UNSUPPORTED:
-                _lib.check(rc, "cgs_tail_dec_fwd_dec0")
-        if not dec0_done:
-            _lib.call("cgs_tail_dec_fwd_pack", n, C.byref(tw), _p(embeds[1]), _p(embeds[2]), _p(embeds[3]), _p(o["o4"]),
-                      _p(o["o3"]), _p(o["o2"]), _p(o["o1"]), C.c_void_p(fp + 4 * lay.off("masker.0.weight")), _p(m0pack), _stream())
-        prev = o["o0"] if dec0_done else o["o1"]
+    # dec_model.3 / .2 / .1 in one tail kernel
+    for nm, shp in (("o3", (n, 4, 4, 16)), ("o2", (n, 8, 8, 8)), ("o1", (n, 16, 16, 8))):
+        if o.get(nm) is None:
+            o[nm] = torch.empty(shp, device=dev, dtype=torch.float32)
+    tw = tail_dec_weights(flat, lay)
+    m0pack = None
+    if (keep_hm and mask_train_fused(n) and zpart is not None) or (not keep_hm and not fp16_mask_head):
+        # the mask head forward's weight registers, built once by a spare workgroup of this launch (the mask head follows two launches later;
+        # inference runs the same kernel, storing nothing but Z)
+        m0pack = o.get("m0pack")
+        if m0pack is None:
+            m0pack = o["m0pack"] = torch.empty(40 * 64, device=dev, dtype=torch.float32)
+    if m0pack_done and keep_hm and zpart is not None and dec_mask_fwd_fused(n, u8):
+        assert o.get("m0pack") is not None, "m0pack_done: the caller's critic launch already built out['m0pack']"
+        for k, shp in (("o0", (n, 32, 32, 8)), ("hm", (n, 64, 64, 16)), ("Z", (n, 64, 64))):
+            if o.get(k) is None:
+                o[k] = torch.empty(shp, device=dev, dtype=torch.float32)
+        wp_ = lambda k: C.c_void_p(fp + 4 * lay.off(k))
+        rc = _lib.load().cgs_dec_mask_fwd(n, C.byref(tw), _p(embeds[0]), _p(embeds[1]), _p(embeds[2]), _p(embeds[3]), _p(o["o4"]),
+                                          _p(o["o3"]), _p(o["o2"]), _p(o["o1"]), wp_("dec_model.0.weight"), wp_("dec_model.0.bias"), _p(o["o0"]),
+                                          _lib.SRC_U8, _p(x), wp_("masker.0.bias"), wp_("masker.2.weight"), wp_("masker.2.bias"),
+                                          _p(o["hm"]), _p(o["Z"]), _p(zpart), _p(o["m0pack"]), _stream())
+        if rc == 0:
+            return o
+        if rc != _lib.ERR_UNSUPPORTED:
+            _lib.check(rc, "cgs_dec_mask_fwd")
+        # beyond the library's cap: the two launches below
+    dec0_done = False
+    if DEC_TAIL_DEC0_FUSED:
+        # one workgroup per image up to the library's own cap (tail_fwd_cap in csrc/tail.hip): beyond it the entry point answers
+        # CGS_ERR_UNSUPPORTED and the two-launch form below runs -- the cap is not restated here
+        if o.get("o0") is None:
+            o["o0"] = torch.empty((n, 32, 32, 8), device=dev, dtype=torch.float32)
+        rc = _lib.load().cgs_tail_dec_fwd_dec0(n, C.byref(tw), _p(embeds[0]), _p(embeds[1]), _p(embeds[2]), _p(embeds[3]), _p(o["o4"]),
+                                               _p(o["o3"]), _p(o["o2"]), _p(o["o1"]), C.c_void_p(fp + 4 * lay.off("dec_model.0.weight")),
+                                               C.c_void_p(fp + 4 * lay.off("dec_model.0.bias")), _p(o["o0"]),
+                                               C.c_void_p(fp + 4 * lay.off("masker.0.weight")), _p(m0pack), _stream())
+        if rc == 0:
+            dec0_done = True
+        elif rc != _lib.ERR_UNSUPPORTED:
+            _lib.check(rc, "cgs_tail_dec_fwd_dec0")
+    if not dec0_done:
+        _lib.call("cgs_tail_dec_fwd_pack", n, C.byref(tw), _p(embeds[1]), _p(embeds[2]), _p(embeds[3]), _p(o["o4"]),
+                  _p(o["o3"]), _p(o["o2"]), _p(o["o1"]), C.c_void_p(fp + 4 * lay.off("masker.0.weight")), _p(m0pack), _stream())
+    prev = o["o0"] if dec0_done else o["o1"]
     for name, sa, (key, hw, ca, cb, co, ups, act, pool, _s) in zip(names, srcs_a, DEC_LAYERS):
-        if TAIL_FWD and (name in ("o3", "o2", "o1") or (name == "o0" and dec0_done)):
+        if name in ("o3", "o2", "o1") or (name == "o0" and dec0_done):
             continue
-        if name == "hm" and not keep_hm and MASK_INFER_FUSED:
+        if name == "hm" and not keep_hm:
             if o.get("Z") is None:
                 o["Z"] = torch.empty((n, 64, 64), device=dev, dtype=torch.float32)
             margs = (n, _lib.SRC_U8 if u8 else _lib.SRC_F32, _p(x), _p(prev),
@@ -665,7 +605,7 @@ def masker_forward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, embeds: Lis
             if fp16_mask_head:
                 rc = _lib.load().cgs_mask_infer_fwd_f16(*margs, _stream())
             else:
-                rc = _lib.load().cgs_mask_infer_fwd_packed(*margs, _p(o.get("m0pack")) if TAIL_FWD else None, _stream())
+                rc = _lib.load().cgs_mask_infer_fwd_packed(*margs, _p(o.get("m0pack")), _stream())
             if rc == 0:
                 return o
             if rc != _lib.ERR_UNSUPPORTED:
@@ -679,7 +619,7 @@ def masker_forward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, embeds: Lis
             _lib.call("cgs_mask_train_fwd_packed", n, _lib.SRC_U8 if u8 else _lib.SRC_F32, _p(x), _p(prev),
                       C.c_void_p(fp + 4 * lay.off("masker.0.weight")), C.c_void_p(fp + 4 * lay.off("masker.0.bias")),
                       C.c_void_p(fp + 4 * lay.off("masker.2.weight")), C.c_void_p(fp + 4 * lay.off("masker.2.bias")),
-                      _p(o["hm"]), _p(o["Z"]), _p(zpart), _p(o.get("m0pack")) if TAIL_FWD else None, _stream())
+                      _p(o["hm"]), _p(o["Z"]), _p(zpart), _p(o.get("m0pack")), _stream())
             return o
         shape = (n, hw, hw) if co == 1 else (n, hw, hw, co)
         if o.get(name) is None:
@@ -728,11 +668,10 @@ def masker_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, embeds: Li
     fused_head_do0 = None
     head_done = False    # masker.2 AND masker.0 fully handled by the mask-head kernel
     fuse_dec0 = None
-    u8_or_f32_needs_da = False   # the image never needs a gradient on this path
-    for li in (5, 4, 3, 2, 1, 0):
+    for li in (5, 4, 3, 2):
         if li == 4 and head_done:
             continue
-        if TAIL_BWD and li == 2:
+        if li == 2:
             # dec_model.1 / .2 / .3 backward in one tail kernel: dy = d o1 -> skip gradients dE1..dE3 and d o4
             nsl = lib.cgs_tail_dec_bwd_slabs(n)
             cnts = {1: 9 * 16 * 8 + 8, 2: 9 * 24 * 8 + 8, 3: 9 * 48 * 16 + 16}
@@ -741,25 +680,17 @@ def masker_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, embeds: Li
                 d_embeds[ei] = buf(f"dE{ei}", shp)
             do4 = buf("do4", (n, 32))
             tw = tail_dec_weights(flat, lay)
-            dec3_rider = (fuse_dec0 is not None and defer_dec0 is not None and DEC3_WGRAD_RIDER and u8 and not enc0_in_tail(False, True, None))
-            nsl_k = {1: nsl, 2: nsl, 3: nsl}
-            if dec3_rider:      # the layer's slab rows come from the riders: allocate their (few) rows instead of one per image
-                nsl_k[3] = lib.cgs_dec3_wgrad_rider_slabs(n)
-                sl[3] = buf("slab_dec0_rider", (nsl_k[3], cnts[3]))
             if fuse_dec0 is not None:      # dec_model.0's data gradient rides in front, one workgroup per image
                 dy_o0, w0ptr, de0 = fuse_dec0
-                do3 = buf("do3", (n, 4, 4, 16)) if dec3_rider else None
-                _lib.call("cgs_dec0_tail_dec_bwd_do3", n, C.byref(tw), _p(dy_o0), w0ptr, _p(de0), _p(embeds[1]), _p(embeds[2]), _p(embeds[3]),
+                _lib.call("cgs_dec0_tail_dec_bwd", n, C.byref(tw), _p(dy_o0), w0ptr, _p(de0), _p(embeds[1]), _p(embeds[2]), _p(embeds[3]),
                           _p(saved["o4"]), _p(saved["o3"]), _p(saved["o2"]), _p(dy), _p(d_embeds[1]), _p(d_embeds[2]), _p(d_embeds[3]), _p(do4),
-                          None if dec3_rider else _p(sl[3]), _p(sl[2]), _p(sl[1]), _p(do3), _stream())
-                if dec3_rider:
-                    defer_dec0.append({"dec3": (n, embeds[3], saved["o4"], do3, sl[3])})
+                          _p(sl[3]), _p(sl[2]), _p(sl[1]), _stream())
             else:
                 _lib.call("cgs_tail_dec_bwd", n, C.byref(tw), _p(embeds[1]), _p(embeds[2]), _p(embeds[3]), _p(saved["o4"]),
                           _p(saved["o3"]), _p(saved["o2"]), _p(dy), _p(d_embeds[1]), _p(d_embeds[2]), _p(d_embeds[3]), _p(do4),
                           _p(sl[3]), _p(sl[2]), _p(sl[1]), _stream())
             for k, c in cnts.items():
-                plan.add(sl[k], nsl_k[k], c, lay.off(f"dec_model.{k}.weight"))
+                plan.add(sl[k], nsl, c, lay.off(f"dec_model.{k}.weight"))
             dy = do4
             break
         key, hw, ca, cb, co, ups, act, pool, _s = DEC_LAYERS[li]
@@ -767,24 +698,7 @@ def masker_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, embeds: Li
         d = conv_desc(n, hw, ca, cb, co, u8 and is_img, ups, act, pool, nd)
         cnt = 9 * (ca + cb) * co + co
         wptr = C.c_void_p(fp + 4 * lay.off(key + ".weight"))
-        if _DEC_TAG[li] in BOTH_DEC and li != 5:
-            nsl = lib.cgs_conv3x3_bwd_both_slabs(C.byref(d))
-            if nsl < 0:
-                _lib.check(nsl, "cgs_conv3x3_bwd_both_slabs")
-            slab = buf(f"slab_dec{li}", (nsl, cnt))
-            if li == 4:   # masker.0: only the upsampled decoder channels need a gradient
-                de, db = None, buf("do0", (n, 32, 32, 8))
-            else:
-                ei = 3 - li
-                de = buf(f"dE{ei}", (n, hw, hw, ca))
-                db = buf(f"do{ei + 1}", (n, 32) if ups == 4 else (n, hw // 2, hw // 2, cb))
-                d_embeds[ei] = de
-            _lib.call("cgs_conv3x3_bwd_both", C.byref(d), _p(srcs_a[li]), _p(srcs_b[li]), _p(dy), None, wptr, None, 0,
-                      _p(de), _p(db), _p(slab), _stream())
-            plan.add(slab, nsl, cnt, lay.off(key + ".weight"))
-            dy = db
-            continue
-        head_fused = li == 5 and MASK_HEAD_FUSED and not u8_or_f32_needs_da
+        head_fused = li == 5
         nsl = lib.cgs_mask_head_bwd_slabs(n) if head_fused else 0
         if nsl > 0:
             # the whole mask head in one launch: d o0, masker.2 and masker.0 weight gradients; d hm is never stored
@@ -803,7 +717,7 @@ def masker_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, embeds: Li
         if nsl < 0:
             _lib.check(nsl, "cgs_conv3x3_bwd_weight_slabs")
         slab = buf(f"slab_dec{li}", (nsl, cnt))
-        if li == 3 and defer_dec0 is not None and DEC0_WGRAD_RIDER:
+        if li == 3 and defer_dec0 is not None:
             # dec_model.0's weight gradient: only the final reduction waits for it -- the caller hands it to the last critic pass's tail
             # launch, whose spare workgroup slots compute it (critic_backward(rider=...)): one persistent rider per CU
             nsl = min(nsl, DEC0_RIDERS)
@@ -819,23 +733,18 @@ def masker_backward(flat: torch.Tensor, lay: Layout, x: torch.Tensor, embeds: Li
                       C.c_void_p(fp + 4 * lay.off("masker.0.weight")), _p(dhm), _p(do0), None, None, _stream())
             dy = dhm
             fused_head_do0 = do0
-        elif li == 5:    # masker.2: d hm = conv_bwd(dzpre) * LeakyReLU'(hm)
-            dhm = buf("dhm", (n, 64, 64, 16))
-            _lib.call("cgs_conv3x3_bwd_data", C.byref(d), _p(dy), None, wptr, _p(saved["hm"]), _lib.ACT_LRELU, None, 0,
-                      _p(dhm), None, _stream())
-            dy = dhm
         elif li == 4 and fused_head_do0 is not None:
             dy = fused_head_do0      # already produced together with d hm
         elif li == 4:  # masker.0: only the upsampled decoder channels need a gradient
             do0 = buf("do0", (n, 32, 32, 8))
             _lib.call("cgs_conv3x3_bwd_data", C.byref(d), _p(dy), None, wptr, None, _lib.ACT_NONE, None, 0, None, _p(do0), _stream())
             dy = do0
-        else:          # dec_model.{0,1,2,3}: skip gradient at full res + upsample-backward sum
+        else:          # dec_model.0: skip gradient at full res + upsample-backward sum
             ei = 3 - li
             de = buf(f"dE{ei}", (n, hw, hw, ca))
             shape_b = (n, 32) if ups == 4 else (n, hw // 2, hw // 2, cb)
             db = buf(f"do{ei + 1}", shape_b)
-            if li == 3 and TAIL_BWD and DEC0_TAIL_BWD_FUSED and n <= lib.cgs_tail_dec_bwd_slabs(n) and lib.cgs_tail_dec_bwd_slabs(n) == n:
+            if li == 3 and DEC0_TAIL_BWD_FUSED and n <= lib.cgs_tail_dec_bwd_slabs(n) and lib.cgs_tail_dec_bwd_slabs(n) == n:
                 fuse_dec0 = (dy, wptr, de)      # launched together with the decoder tail's backward below
             else:
                 _lib.call("cgs_conv3x3_bwd_data", C.byref(d), _p(dy), None, wptr, None, _lib.ACT_NONE, None, 0, _p(de), _p(db), _stream())

@@ -572,7 +572,7 @@ def tail_enc_case(env, c, v, enc1, i, entry):
             de0 = Buf((n, 32, 32, 8), dev)
             s1 = Buf((nsl, 584), dev) if (v["slabs"] and with_s1) else None
             args += [P(c.f("am1")), wc(env, "features.3.weight"), P(c.f("dE0")) if n_add0 else None, n_add0, de0.ptr,
-                     P(c.f("e0")) if s1 else None, s1.ptr if s1 else None, 0, None, None, None]
+                     P(c.f("e0")) if s1 else None, s1.ptr if s1 else None]
         args += [stream()]
     L.call(entry, *args)
     sync()
@@ -658,9 +658,9 @@ def am0_words(c, n):
     return c.hold(torch.full((n, 32, 32, 1), 0x3210F123, dtype=torch.int32, device=c.env["dev"]))
 
 
-@pytest.mark.parametrize("entry", ["cgs_enc0_wgrad_u8_with_head", "cgs_enc0_wgrad_u8_with_head_enc1", "cgs_enc0_wgrad_u8_with_head_riders"])
+@pytest.mark.parametrize("entry", ["cgs_enc0_wgrad_u8_with_head", "cgs_enc0_wgrad_u8_with_head_enc1"])
 def test_enc0_wgrad_u8_with_head(env, entry):
-    """The head GEMM, features.3's rider slab and dec_model.3's rider slab are exact; the features.0 part gets real uint8 frames and dy = 0:
+    """The head GEMM and features.3's rider slab are exact; the features.0 part gets real uint8 frames and dy = 0:
     its slab must be exactly zero (features.0's input is not dyadic: its non-zero gradients are out of scope here)."""
     L, hg = env["lib"], env["hg"]
     d0 = lambda n: hg.conv_desc(n, 64, 3, 0, 8, True, 2, "relu", 1, L.Dropout())
@@ -673,14 +673,11 @@ def test_enc0_wgrad_u8_with_head(env, entry):
         s0 = Buf((ns0, 224), dev)
         sh, spw = Buf((L.load().cgs_tail_head_wgrad_slabs(n), HEAD_SLAB), dev), Buf((L.load().cgs_tail_head_wgrad_slabs(n), PW_SLAB), dev)
         args = [n, P(frames(c, 5)), P(c.hold(torch.zeros(n, 32, 32, 8, device=dev))), P(am0_words(c, n)), s0.ptr] + head_args(c, k, with_o4) + [sh.ptr, spw.ptr if with_o4 else None]
-        s1 = s3 = None
+        s1 = None
         if entry != "cgs_enc0_wgrad_u8_with_head":
             ns1 = L.load().cgs_enc1_wgrad_rider_slabs(n)
             s1 = Buf((ns1, 584), dev)
             args += [n, P(c.f("e0")), P(c.f("de1")), P(c.f("am1")), s1.ptr, ns1]
-        if entry.endswith("riders"):
-            s3 = Buf((L.load().cgs_dec3_wgrad_rider_slabs(n), 6928), dev)
-            args += [n, P(c.f("e3")), P(c.f("o4")), P(c.f("do3")), s3.ptr]
         L.call(entry, *args, stream())
         sync()
         form = f"{entry}[ranges {k}+{n - k} d_o4={with_o4}]"
@@ -689,9 +686,7 @@ def test_enc0_wgrad_u8_with_head(env, entry):
         expect_head(c, form, sh, spw, with_o4)
         if s1 is not None:
             expect_slab(c, form, "g_enc1 (rider)", s1, c.g["g_enc1"], lambda mut: c.mutated(mut)[1]["g_enc1"])
-        if s3 is not None:
-            expect_slab(c, form, "g_dec3 (rider)", s3, c.g["g_dec3"], lambda mut: c.mutated(mut)[1]["g_dec3"])
-    run_form(env, fn, lambda n: [L.load().cgs_tail_head_wgrad_slabs(n), L.load().cgs_enc1_wgrad_rider_slabs(n), L.load().cgs_dec3_wgrad_rider_slabs(n),
+    run_form(env, fn, lambda n: [L.load().cgs_tail_head_wgrad_slabs(n), L.load().cgs_enc1_wgrad_rider_slabs(n),
                                  L.load().cgs_conv3x3_bwd_weight_slabs(C.byref(d0(n)))], big_i=(0, 1))          # one range at 600, two at 1100, with d_o4
 
 
@@ -722,48 +717,38 @@ def test_enc0_bwd_mix_enc1(env):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # decoder tail
 # ---------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("entry", ["cgs_tail_dec_bwd", "cgs_dec0_tail_dec_bwd", "cgs_dec0_tail_dec_bwd_do3"])
+@pytest.mark.parametrize("entry", ["cgs_tail_dec_bwd", "cgs_dec0_tail_dec_bwd"])
 def test_tail_dec_bwd(env, entry):
-    """cgs_dec0_tail_dec_bwd(_do3): one workgroup and one slab row per image up to the documented limit (cgs_tail_dec_bwd_slabs' cap, 512);
+    """cgs_dec0_tail_dec_bwd: one workgroup and one slab row per image up to the documented limit (cgs_tail_dec_bwd_slabs' cap, 512);
     beyond it CGS_ERR_UNSUPPORTED and nothing written.  So besides n = 600 and 1100 there is a batch AT the limit, n = 512: the largest at
-    which these two forms compute anything, and the one the benchmark runs.  A large batch runs _do3 both with and without do3."""
+    which this form computes anything, and the one the benchmark runs."""
     L, hg = env["lib"], env["hg"]
     dec0 = entry != "cgs_tail_dec_bwd"
 
     def fn(c, i):
-        for with_do3 in ((True, False) if (c.sub is not None and entry.endswith("do3")) else (entry.endswith("do3") and i % 2 == 0,)):
-            one(c, with_do3)
-
-    def one(c, with_do3):
         dev, n = c.env["dev"], c.n
         nsl = L.load().cgs_tail_dec_bwd_slabs(n)
         td = hg.tail_dec_weights(env["fm"], env["lm"])
         outs = {k: Buf((n,) + SHAPE[k], dev) for k in ("dE1", "dE2", "dE3", "d_o4")}
-        sl = {3: None if with_do3 else Buf((nsl, 6928), dev), 2: Buf((nsl, 1736), dev), 1: Buf((nsl, 1160), dev)}
-        sp = lambda b: b.ptr if b is not None else None
+        sl = {3: Buf((nsl, 6928), dev), 2: Buf((nsl, 1736), dev), 1: Buf((nsl, 1160), dev)}
         if dec0:
             outs["dE0"], outs["do1"] = Buf((n, 32, 32, 8), dev), Buf((n, 16, 16, 8), dev)
-            if with_do3:
-                outs["do3"] = Buf((n, 4, 4, 16), dev)
             args = [n, C.byref(td), P(c.f("dy_o0")), wm(env, "dec_model.0.weight"), outs["dE0"].ptr, P(c.f("e1")), P(c.f("e2")), P(c.f("e3")), P(c.f("o4")),
-                    P(c.f("o3")), P(c.f("o2")), outs["do1"].ptr, outs["dE1"].ptr, outs["dE2"].ptr, outs["dE3"].ptr, outs["d_o4"].ptr, sp(sl[3]), sp(sl[2]), sp(sl[1])]
-            if entry.endswith("do3"):
-                args.append(outs["do3"].ptr if with_do3 else None)
+                    P(c.f("o3")), P(c.f("o2")), outs["do1"].ptr, outs["dE1"].ptr, outs["dE2"].ptr, outs["dE3"].ptr, outs["d_o4"].ptr, sl[3].ptr, sl[2].ptr, sl[1].ptr]
         else:
             args = [n, C.byref(td), P(c.f("e1")), P(c.f("e2")), P(c.f("e3")), P(c.f("o4")), P(c.f("o3")), P(c.f("o2")), P(c.f("do1")),
-                    outs["dE1"].ptr, outs["dE2"].ptr, outs["dE3"].ptr, outs["d_o4"].ptr, sp(sl[3]), sp(sl[2]), sp(sl[1])]
+                    outs["dE1"].ptr, outs["dE2"].ptr, outs["dE3"].ptr, outs["d_o4"].ptr, sl[3].ptr, sl[2].ptr, sl[1].ptr]
         rc = getattr(L.load(), entry)(*args, stream())
         sync()
-        form = f"{entry}[do3={with_do3}]"
+        form = entry
         if dec0 and n > nsl:
             assert rc == L.ERR_UNSUPPORTED, f"{form} {c}: return code {rc}"
-            for k, b in list(outs.items()) + [(f"slab{j}", s) for j, s in sl.items() if s is not None]:
+            for k, b in list(outs.items()) + [(f"slab{j}", s) for j, s in sl.items()]:
                 expect_untouched(c, form, k, b)
             return
         L.check(rc, entry)
         for k, b in outs.items():
             expect(c, form, k, b, c.g[k], lambda mut, k=k: c.mutated(mut)[1][k])
         for j, s in sl.items():
-            if s is not None:
-                expect_slab(c, form, f"g_dec{j}", s, c.g[f"g_dec{j}"], lambda mut, j=j: c.mutated(mut)[1][f"g_dec{j}"])
+            expect_slab(c, form, f"g_dec{j}", s, c.g[f"g_dec{j}"], lambda mut, j=j: c.mutated(mut)[1][f"g_dec{j}"])
     run_form(env, fn, lambda n: [L.load().cgs_tail_dec_bwd_slabs(n)], big=(512,) + BIG)

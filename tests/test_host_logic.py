@@ -188,6 +188,23 @@ def test_checkpoint_names_follow_reference_mangling():
     assert m == "mepochs=1-L1=0.5-L2=0.1"
 
 
+def test_build_headers_list_every_quoted_include():
+    """build.py rebuilds the library when a file in HEADERS is newer than it: every header a file under csrc/ includes with quotes
+    must be listed there (by file name), or editing it leaves a stale library behind."""
+    from cgs_amd import build
+    csrc = build.CSRC
+    listed = {os.path.basename(h) for h in build.HEADERS}
+    included = {}
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".hip", ".h")):
+            with open(os.path.join(csrc, name)) as fp:
+                for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', fp.read(), re.M):
+                    included.setdefault(os.path.basename(inc), name)
+    assert included, "no quoted include found under csrc/: the pattern is wrong"
+    missing = {h: src for h, src in included.items() if h not in listed}
+    assert not missing, f"headers included under csrc/ but missing from build.HEADERS (header: first includer): {missing}"
+
+
 def test_c_abi_library_exports_every_declared_symbol():
     """libcgs_hip.so loads (no GPU needed for dlopen) and exports exactly the entry points include/cgs_hip.h
     declares; the ctypes signature table covers all of them.  No compute call is made here."""
