@@ -29,13 +29,6 @@ def _align4(x):
 
 
 GATHER_ONE_LAUNCH = os.environ.get("CGS_GATHER_ONE_LAUNCH", "1") != "0"
-PHASE1_FUSED_TAIL = os.environ.get("CGS_PHASE1_FUSED_TAIL", "1") != "0"      # (A/B switch: phase 1 with phase 2's fused step tail)
-# config 4's layers between features.0 and dec_model.0: "fused1" = features.3 .. dec_model.1 in one launch per image on fp16 tiles (csrc/tail_infer.hip),
-# "fused" = features.3 as a launch of its own (cgs_f16_enc1_fwd) + that kernel from features.6 on, "1" = ... + the two tail launches with fp16 operands
-# (csrc/tail_h16.h), "0" = ... + the fp32 tail kernels (A/B switch)
-# Measured at batch 2048 (profiles/r06_config4_fused_tail_ab.txt, r06_config4_enc1_in_tail_ab.txt): "0" 0.1819 ms, "1" 0.1685, "fused" 0.1562, "fused1" 0.1612 --
-# features.3 is a throughput-bound convolution: inside the per-image latency chain (three workgroups per CU) it costs more than as a launch of its own.
-F16_TAILS = os.environ.get("CGS_F16_TAILS", "fused")
 
 
 class HourglassEngine:
@@ -377,7 +370,7 @@ class HourglassEngine:
         first = "p1" not in self._plans
         pc = hg.SlabPlan()
         # (round 5) as phase 2 does: the head's weight gradients in the features.0 weight-gradient launch, reduction + Adam in one launch on one GPU
-        sink = [] if PHASE1_FUSED_TAIL else None
+        sink = []
         hg.critic_backward(self.fc, self.lc, X, n, self._cview(0, n), self.dpred[:n], pc, self.drop.shifted(0), ws=self._ws["p1"],
                            side=self.side, head_sink=sink)
         if sink:
@@ -402,7 +395,7 @@ class HourglassEngine:
             self._plans["p1"].run(self.step_t)
 
     def _p1_fused_adam(self):
-        return self.fused_tail and not self.dp and PHASE1_FUSED_TAIL
+        return self.fused_tail and not self.dp
 
     def _adam_p1(self):
         if self._p1_fused_adam():
@@ -553,52 +546,39 @@ class HourglassEngine:
         pred, Z, _ = gen.infer_f16(self.fc, self.lc, self.fm if want_mask else None, self.lm, X, chfak, neck, w16, embeds_from=emb)
         return pred, Z
 
-    def _infer_f16_fused(self, X: torch.Tensor, want_mask: bool):
+    def _infer_f16_fused(self, X: torch.Tensor, want_mask: bool, fp32_tail: bool = False):
         """BASELINE config 4 on the FUSED path (round 4): features.0 / features.3 / dec_model.0 on the fp16 convolutions of
         csrc/hconv.hip (fp16 activations in HBM, v_mfma_f32_16x16x32_f16), the mask head on the fp16 one-kernel form reading the fp16
-        o0, the 16x16-and-smaller layers on the fp32 tail kernels.  uint8 frames, eval mode, one critic."""
+        o0, the 16x16-and-smaller layers of an image in one workgroup on fp16 tiles (round 6, csrc/tail_infer.hip).  uint8 frames, eval
+        mode, one critic.  fp32_tail (the tests' comparator): the two fp32 tail kernels in that kernel's place."""
         b, dev = X.shape[0], X.device
+        f16 = lambda *s: torch.empty(s, device=dev, dtype=torch.float16)
+        f32 = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)
         ws = getattr(self, "_f16ws", None)
         if ws is None or ws["b"] != b:
-            f16 = lambda *s: torch.empty(s, device=dev, dtype=torch.float16)
-            f32 = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)
-            ws = self._f16ws = dict(b=b, e0=f16(b, 32, 32, 8), e1=f32(b, 16, 16, 8), e2=f32(b, 8, 8, 8), am2=torch.empty((b, 8, 8, 1), device=dev, dtype=torch.int32),
-                                    e3=f32(b, 4, 4, 16), am3=torch.empty((b, 4, 4, 2), device=dev, dtype=torch.int32), e4=f32(b, 32), h1=f32(b, 32),
-                                    o4=f32(b, 32), o3=f32(b, 4, 4, 16), o2=f32(b, 8, 8, 8), o1=f32(b, 16, 16, 8), o0=f16(b, 32, 32, 8))
+            ws = self._f16ws = dict(b=b, e0=f16(b, 32, 32, 8), e1=f32(b, 16, 16, 8), o1=f32(b, 16, 16, 8), o0=f16(b, 32, 32, 8))
         pred = torch.empty(b, device=dev, dtype=torch.float32)
         cp, mp = self.fc.data_ptr(), self.fm.data_ptr()
         wc = lambda k: C.c_void_p(cp + 4 * self.lc.off(k))
         wm = lambda k: C.c_void_p(mp + 4 * self.lm.off(k))
         _lib.call("cgs_f16_enc0_fwd", b, _P(X), wc("features.0.weight"), wc("features.0.bias"), _P(ws["e0"]), _S())
-        if F16_TAILS != "fused1":
-            _lib.call("cgs_f16_enc1_fwd", b, _P(ws["e0"]), wc("features.3.weight"), wc("features.3.bias"), _P(ws["e1"]), _S())
+        _lib.call("cgs_f16_enc1_fwd", b, _P(ws["e0"]), wc("features.3.weight"), wc("features.3.bias"), _P(ws["e1"]), _S())
         tw = hg.tail_enc_weights(self.fc, self.lc, (mp + 4 * self.lm.off("dec_model.4.weight"), mp + 4 * self.lm.off("dec_model.4.bias")))
-        # (round 6) the tails' 3x3 layers with fp16 operands too (csrc/tail_h16.h): at this batch the fp32 decoder tail was bound by the fp32 matrix pipe
-        if F16_TAILS == "fused1":
-            td = hg.tail_dec_weights(self.fm, self.lm) if want_mask else None
-            _lib.call("cgs_f16_enc1_tail_infer", b, _P(ws["e0"]), wc("features.3.weight"), wc("features.3.bias"), C.byref(tw),
-                      C.byref(td) if want_mask else None, _P(pred), _P(ws["o1"]) if want_mask else None, _S())
-            if not want_mask:
-                return pred, None
-        elif F16_TAILS == "fused":
-            td = hg.tail_dec_weights(self.fm, self.lm) if want_mask else None
+        td = hg.tail_dec_weights(self.fm, self.lm) if want_mask else None
+        if not fp32_tail:
             _lib.call("cgs_tail_infer_h16", b, C.byref(tw), C.byref(td) if want_mask else None, _P(ws["e1"]), _P(pred),
                       _P(ws["o1"]) if want_mask else None, _S())
-            if not want_mask:
-                return pred, None
-        elif F16_TAILS != "0":
-            _lib.call("cgs_tail_enc_fwd_h16", b, C.byref(tw), _P(ws["e1"]), _P(ws["e2"]), _P(ws["am2"]), _P(ws["e3"]), _P(ws["am3"]), _P(ws["e4"]),
-                      _P(ws["h1"]), _P(pred), _P(ws["o4"]) if want_mask else None, _S())
         else:
+            i32 = lambda *s: torch.empty(s, device=dev, dtype=torch.int32)
+            e2, am2, e3, am3, e4, h1 = f32(b, 8, 8, 8), i32(b, 8, 8, 1), f32(b, 4, 4, 16), i32(b, 4, 4, 2), f32(b, 32), f32(b, 32)
+            o4, o3, o2 = f32(b, 32), f32(b, 4, 4, 16), f32(b, 8, 8, 8)
             nd = _lib.Dropout(0.0, 0, 0, None, 0, 0)
-            _lib.call("cgs_tail_enc_fwd", b, C.byref(tw), _P(ws["e1"]), _P(ws["e2"]), _P(ws["am2"]), _P(ws["e3"]), _P(ws["am3"]), _P(ws["e4"]),
-                      _P(ws["h1"]), _P(pred), _P(ws["o4"]) if want_mask else None, nd, nd, nd, _S())
-        if F16_TAILS not in ("fused", "fused1"):
-            if not want_mask:
-                return pred, None
-            td = hg.tail_dec_weights(self.fm, self.lm)
-            _lib.call("cgs_tail_dec_fwd_h16" if F16_TAILS != "0" else "cgs_tail_dec_fwd", b, C.byref(td), _P(ws["e1"]), _P(ws["e2"]), _P(ws["e3"]), _P(ws["o4"]),
-                      _P(ws["o3"]), _P(ws["o2"]), _P(ws["o1"]), _S())
+            _lib.call("cgs_tail_enc_fwd", b, C.byref(tw), _P(ws["e1"]), _P(e2), _P(am2), _P(e3), _P(am3), _P(e4), _P(h1), _P(pred),
+                      _P(o4) if want_mask else None, nd, nd, nd, _S())
+            if want_mask:
+                _lib.call("cgs_tail_dec_fwd", b, C.byref(td), _P(ws["e1"]), _P(e2), _P(e3), _P(o4), _P(o3), _P(o2), _P(ws["o1"]), _S())
+        if not want_mask:
+            return pred, None
         _lib.call("cgs_f16_dec0_fwd", b, _P(ws["e0"]), _P(ws["o1"]), wm("dec_model.0.weight"), wm("dec_model.0.bias"), _P(ws["o0"]), _S())
         Z = torch.empty((b, 64, 64), device=dev, dtype=torch.float32)
         _lib.call("cgs_mask_infer_fwd_f16o", b, _lib.SRC_U8, _P(X), _P(ws["o0"]), wm("masker.0.weight"), wm("masker.0.bias"), wm("masker.2.weight"),
@@ -614,7 +594,7 @@ class HourglassEngine:
         tap products; fp32 accumulation, fp32 sums of the tap planes, sigmoid via v_exp / v_rcp.  Z differs from the fp32 path by < 2e-3 absolute
         (tests/test_gpu_kernels.py: max 2e-3, mean 3e-4 bounds; measured on the G1 weights ~3e-5 max).
         fp16 (opt-in, uint8 frames, eval mode): BASELINE config 4 -- the fused fp16 path (fp16 activations / weights in the 64x64 and 32x32
-        convolutions and the mask head, fp32 accumulation, the 16x16-and-smaller tail in fp32); fp16_layerwise=True: the shape-generic
+        convolutions and the mask head, fp32 accumulation, the 16x16-and-smaller layers of an image in one workgroup on fp16 tiles); fp16_layerwise=True: the shape-generic
         chain with fp16 activations in EVERY layer (what chfak != 1 runs).
         train_mode (-noevalmode, main.py:1109-1118): Dropout stays active, a fresh mask per call.
         With a second critic (-separate, main.py:1140-1142) the masker's inputs come from it."""

@@ -17,9 +17,11 @@ buffer (kernel layout: HWIO weights followed by their bias, k-major GEMM matrice
     ds_read_b64_tr_b16 (csrc/hwgrad.hip);
   * the 16x16-and-smaller levels have exactly the shapes of the 64x64 model's lower levels and run on ITS fp32 per-image tail kernels
     (csrc/tail.hip: cgs_tail_enc_fwd / _bwd, cgs_tail_dec_fwd / _bwd, cgs_tail_head_wgrad); their activations are fp32.
-Other channel counts (chfak != 1, neck != 32): the shape-generic 16-bit family (csrc/gen_f16.hip forward / data gradient = the same
-kernel on the flipped / transposed operand; csrc/gen_bf16_train.hip weight gradient and element-wise steps; the 4x4 valid convolution,
-the Linear layers and the decoder's 1x1 pointwise convolution as MFMA GEMMs).
+Other channel counts (chfak != 1, neck != 32), or Hourglass128(dedicated=False): the shape-generic 16-bit family (csrc/gen_f16.hip
+forward / data gradient = the same kernel on the flipped / transposed operand; csrc/gen_bf16_train.hip weight gradient and element-wise
+steps; the 4x4 valid convolution, the Linear layers and the decoder's 1x1 pointwise convolution as MFMA GEMMs; the two mixes as fp32
+tensors through cgs_mix_fwd / cgs_mix_bwd).  Which family a layer runs on is decided per instance: self.dedicated (the constructor's
+argument), self.h5 (the 128x128 .. 32x32 kernels' channel counts) and self.tail (... and the tail kernels' shapes).
 PARITY UNPINNED: there is no reference counterpart; tests compare against the build's own fp32 CPU restatement and its autograd
 (oracle/hourglass_ref.py, hourglass128_apply / hourglass128_phase2_loss) with a stated bf16 tolerance.  Not wired into main.py (the
 reference's CLI has no such size); `bench.py --config 5 [--mode train]` measures it."""
@@ -35,14 +37,7 @@ from . import hourglass as hg
 from . import parallel
 from .generic import _ACT, _p, _s
 
-TAIL = True                 # the 16x16-and-smaller layers of chfak 1 (same shapes as the 64x64 model's) on the fp32 per-image tail kernels (csrc/tail.hip)
 TAIL_INFER_H16 = os.environ.get("CGS_C5_TAIL_H16", "1") != "0"      # inference: the two tail launches as ONE, on fp16 tiles (csrc/tail_infer.hip; A/B switch)
-H5CONV = True               # the 128x128 layers of chfak 1 (masker.0 / masker.2 forward, the three data gradients) on h5conv_kernel (csrc/hconv.hip)
-MIX_VIRTUAL = True          # the two mixes are formed inside features.0's forward / weight-gradient staging (no fp32 mix tensor, no mix kernel)
-MIX_BWD_FUSED = True        # features.0's image gradient of the two mixes + cgs_mix_bwd as one kernel (cgs_bf16_enc0_bwd_mix)
-POOL_FUSED = True           # ... and the pooled gradients of features.0 / features.3 re-expanded inside their consumers (no cgs_bf16_pool_expand)
-HWGRAD = True               # weight gradients of the 128x128 / 64x64 layers of chfak 1 on csrc/hwgrad.hip (False: the shape-generic kernel)
-ENC0_DIRECT = True          # features.0 of chfak 1 on cgs_bf16_enc0_fwd (False: the generic bf16 convolution; r4 A/B)
 ENC_KEYS = ("features.0", "features.3", "features.6", "features.9", "features.13")
 ENC_HW = (128, 64, 32, 16, 8)            # pre-pool map size of the five encoder stages
 GEMM_KEYS = ("features.17", "crit.1", "crit.4")
@@ -66,14 +61,16 @@ class Hourglass128:
 
     def __init__(self, critic_params: Dict[str, torch.Tensor], masker_params: Dict[str, torch.Tensor], device="cuda:0", chfak: int = 1,
                  neck: int = 32, masker_channels: int = 16, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, lfak: float = 5.0,
-                 L1: float = 0.5, L2: float = 0.0, process_group=None, force_allreduce: bool = False, dp_graph: Optional[bool] = None):
+                 L1: float = 0.5, L2: float = 0.0, process_group=None, force_allreduce: bool = False, dp_graph: Optional[bool] = None,
+                 dedicated: bool = True):
         if not torch.cuda.is_available():
             raise _lib.CgsError("Hourglass128 needs an MI355X (HIP device); there is no CPU fallback")
         self.lib = _lib.load()
         self.dev = dev = torch.device(device)
         d = [8 * chfak, 8 * chfak, 8 * chfak, 8 * chfak, 16 * chfak]
         self.d, self.nb, self.mc = d, neck * chfak, masker_channels
-        self.h5 = chfak == 1 and masker_channels == 16       # the dedicated 128x128 kernels are compiled for these channel counts
+        self.dedicated = dedicated                           # False: every layer on the shape-generic 16-bit family (the tests' comparator at chfak 1)
+        self.h5 = dedicated and chfak == 1 and masker_channels == 16      # the dedicated 128x128 kernels are compiled for these channel counts
         self.tail = self.h5 and neck == 32                   # ... and the tail kernels for the 64x64 model's 16x16-and-smaller shapes
         nb = self.nb
         self.lr, self.b1, self.b2, self.eps, self.lfak, self.L1, self.L2 = lr, betas[0], betas[1], eps, lfak, L1, L2
@@ -168,9 +165,9 @@ class Hourglass128:
         return out
 
     def _packs_unused(self) -> bool:
-        """chfak 1 with every dedicated path on: no layer runs on the shape-generic 16-bit convolution, so its bf16 operand copies are never read
+        """Every layer on a dedicated kernel: none runs on the shape-generic 16-bit convolution, so its bf16 operand copies are never read
         (the dedicated kernels convert the fp32 master weights themselves)."""
-        return bool(self.tail and TAIL and H5CONV and HWGRAD and POOL_FUSED and ENC0_DIRECT)
+        return self.tail
 
     def _pack_weights(self, transposed: bool):
         """bf16 operand copies of every 3x3 layer from the fp32 master weights: ONE launch (a device job table, built once)."""
@@ -197,18 +194,18 @@ class Hourglass128:
             out = torch.empty((n, oh, oh, co), device=a.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
         if a_kind is None:
             a_kind = 1 if a.dtype == torch.uint8 else (2 if a.dtype == torch.float32 else 0)
-        if ENC0_DIRECT and key == "features.0" and w16 is None and (ca, cb, co, hw) == (3, 0, 8, 128) and pool and act == "relu" \
+        if self.dedicated and key == "features.0" and w16 is None and (ca, cb, co, hw) == (3, 0, 8, 128) and pool and act == "relu" \
                 and not out_f32 and a_kind in (1, 2):
             # chfak 1: the whole-strip kernel of the fp16 inference path in bfloat16 (csrc/hconv.hip), weights from the fp32 master copy
             w, bias = self._wview(key)
             _lib.call("cgs_bf16_enc0_fwd", n, _p(a), int(a_kind == 2), _p(w), _p(bias), _p(out), _p(codes), _s())
             return out
-        if H5CONV and self.h5 and w16 is None and out_f32 and a_kind == 0 and key == "features.6" and (hw, ca, cb, co) == (32, 8, 0, 8) and pool \
+        if self.h5 and w16 is None and out_f32 and a_kind == 0 and key == "features.6" and (hw, ca, cb, co) == (32, 8, 0, 8) and pool \
                 and act == "relu":       # (fp32 output: the tail kernels' input)
             w, bias = self._wview(key)
             _lib.call("cgs_bf16_h5conv", _lib.H5_ENC2_FWD, n, _p(a), None, _p(w), _p(bias), _p(out), _p(codes), _s())
             return out
-        if H5CONV and self.h5 and w16 is None and not out_f32 and a_kind == 0:
+        if self.h5 and w16 is None and not out_f32 and a_kind == 0:
             w, bias = self._wview(key)
             if key == "dec_model.1" and (hw, ca, cb, co, ups) == (32, 8, 8, 8, 2) and not pool and act == "none":
                 which = _lib.H5_DEC1_FWD_F32B if b.dtype == torch.float32 else _lib.H5_DEC1_FWD      # fp32 o2: straight from the tail kernel
@@ -255,7 +252,7 @@ class Hourglass128:
             raise _lib.CgsError("Hourglass128.infer reads uint8 frames [n,128,128,3] (NHWC, contiguous, on the device)")
         n, d, nb = x_u8.shape[0], self.d, self.nb
         e, src = [], x_u8
-        if TAIL and self.tail:      # the 16x16-and-smaller levels: two fp32 per-image launches (csrc/tail.hip) instead of eleven
+        if self.tail:      # the 16x16-and-smaller levels: two fp32 per-image launches (csrc/tail.hip) instead of eleven
             f32 = lambda *sh: torch.empty(sh, device=self.dev, dtype=torch.float32)
             i32 = lambda *sh: torch.empty(sh, device=self.dev, dtype=torch.int32)
             for i in (0, 1):
@@ -272,11 +269,7 @@ class Hourglass128:
                           _NODROP, _NODROP, _NODROP, _s())
                 o4, o3, o2 = f32(n, 4, 4, 16), f32(n, 8, 8, 8), f32(n, 16, 16, 8)
                 _lib.call("cgs_tail_dec_fwd", n, C.byref(tdw), _p(e2), _p(e3), _p(e4), _p(o5), _p(o4), _p(o3), _p(o2), _s())
-            if H5CONV:      # dec_model.1 reads the tail kernel's fp32 o2 directly
-                o = o2
-            else:
-                o = torch.empty((n, 16, 16, 8), device=self.dev, dtype=torch.bfloat16)
-                _lib.call("cgs_bf16_convert", n * 256, 8, 8, 0, _p(o2), _p(o), _s())
+            o = o2      # dec_model.1 reads the tail kernel's fp32 o2 directly
             lower = (1, 0)
         else:
             for key, co in zip(ENC_KEYS, d):
@@ -290,7 +283,7 @@ class Hourglass128:
             lower = (3, 2, 1, 0)
         for i in lower:
             o = self._conv(f"dec_model.{i}", e[i], o, d[i])
-        if H5CONV and self.h5:
+        if self.h5:
             hm = torch.empty((n, 128, 128, 16), device=self.dev, dtype=torch.bfloat16)
             Z = torch.empty((n, 128, 128), device=self.dev)
             self._mask_head_fwd(n, x_u8, o, hm, Z)
@@ -312,12 +305,12 @@ class Hourglass128:
             n4 = 4 * n
             self.ab = u8(2 * n, 128, 128, 3)              # [B | A]
             self.y = f32(n)
-            self.mixed = self.dmixed = None          # fp32 mixes / their gradient: only the paths without MIX_VIRTUAL / MIX_BWD_FUSED materialise them
+            self.mixed = self.dmixed = None          # fp32 mixes / their gradient: only the path without the tail kernels materialises them
             # critic activations for the 4n slots [B | A | replaced | injected]
             self.e = [bf(n4, hw // 2, hw // 2, co) for hw, co in zip(ENC_HW, d)]
             self.codes = [u8(n4, hw // 2, hw // 2, co) for hw, co in zip(ENC_HW, d)]
             self.e4f = f32(n4, 16 * d[4])
-            if TAIL and net.tail:       # fp32 activations of the levels the tail kernels own (their names: e1 e2 am2 e3 am3 | o4 o3 o2 o1)
+            if net.tail:       # fp32 activations of the levels the tail kernels own (their names: e1 e2 am2 e3 am3 | o4 o3 o2 o1)
                 i32 = lambda *s: torch.empty(s, device=dev, dtype=torch.int32)
                 self.t_e2, self.t_e3, self.t_am3 = f32(n4, 16, 16, 8), f32(n4, 8, 8, 8), i32(n4, 8, 8, 1)
                 self.t_e4, self.t_am4 = f32(n4, 4, 4, 16), i32(n4, 4, 4, 2)
@@ -372,7 +365,7 @@ class Hourglass128:
 
     def _critic_forward(self, T, src, lo: int, hi: int, want_o5: bool = False):
         """Critic on slots [lo, hi): src = the frames / mixes of those slots (uint8 or fp32 NHWC)."""
-        if TAIL and self.tail:
+        if self.tail:
             return self._critic_forward_tail(T, src, lo, hi, want_o5)
         n, d, nb = hi - lo, self.d, self.nb
         x = src
@@ -387,7 +380,7 @@ class Hourglass128:
     def _masker_forward(self, T, A):
         n, d, nb = T.n, self.d, self.nb
         ea = [t[n:2 * n] for t in T.e]
-        if TAIL and self.tail:      # dec_model.5 came out of the critic's tail kernel; .4 / .3 / .2 in one launch, fp32
+        if self.tail:      # dec_model.5 came out of the critic's tail kernel; .4 / .3 / .2 in one launch, fp32
             tdw = self._tail_dec_w()
             _lib.call("cgs_tail_dec_fwd", n, C.byref(tdw), _p(T.t_e2[n:2 * n]), _p(T.t_e3[n:2 * n]), _p(T.t_e4[n:2 * n]), _p(T.t_o5[n:2 * n]),
                       _p(T.t_o4), _p(T.t_o3), _p(T.t_o2), _s())
@@ -399,7 +392,7 @@ class Hourglass128:
             lower = (3, 2, 1, 0)
         for i in lower:
             self._conv(f"dec_model.{i}", ea[i], T.o[i + 1], d[i], out=T.o[i])
-        if H5CONV and self.h5:
+        if self.h5:
             self._mask_head_fwd(n, A, T.o[0], T.hm, T.Z)
             return
         self._conv("masker.0", A, T.o[0], self.mc, act="lrelu", out=T.hm)
@@ -410,7 +403,7 @@ class Hourglass128:
         ca, cb, co = self.convs[key]
         cnt = 9 * (ca + cb) * co + co
         a_kind = 1 if a.dtype == torch.uint8 else (2 if a.dtype == torch.float32 else 0)
-        nsl = self.lib.cgs_bf16_hwgrad_slabs(n, hw, ca, cb, co) if HWGRAD and (cb == 0 or ups == 2) and (co > 1 or dy_f32 is not None) else 0
+        nsl = self.lib.cgs_bf16_hwgrad_slabs(n, hw, ca, cb, co) if self.dedicated and (cb == 0 or ups == 2) and (co > 1 or dy_f32 is not None) else 0
         if nsl > 0:          # the large-map layers of chfak 1: csrc/hwgrad.hip
             slab = T.buf(f"slab_{key}_{tag}", (nsl, cnt), torch.float32, self.dev)
             _lib.call("cgs_bf16_hwgrad", n, hw, ca, cb, co, a_kind, _p(a), _p(b), _p(dy_f32 if co == 1 else dy), _p(slab), _s())
@@ -484,7 +477,7 @@ class Hourglass128:
         """Backward of the critic on slots [lo, hi) from T.dpred; skips = [dskip_0..4] gradients arriving at the embeds from the
         decoder (bf16), d_e5_add fp32 [n,nb]; want_dx: fp32 [n,128,128,3] output for the image gradient."""
         n, d, nb = hi - lo, self.d, self.nb
-        if TAIL and self.tail:
+        if self.tail:
             # head + features.13 + features.9 in one launch from dpred: d e2 (fp32, the decoder's skip gradient included); skips[2..4] / d_e5_add
             # are the fp32 tensors cgs_tail_dec_bwd left (dE1 dE2 dE3 / d_o4 in its names)
             f32 = torch.float32
@@ -514,7 +507,7 @@ class Hourglass128:
             dp = self._head_backward(T, plan, tag, lo, hi, d_e5_add)
         for i in levels:
             key, hw, co = ENC_KEYS[i], ENC_HW[i], d[i]
-            if (i <= 1 or (i == 2 and TAIL and self.tail)) and H5CONV and HWGRAD and POOL_FUSED and self.h5:
+            if (i <= 1 or (i == 2 and self.tail)) and self.h5:
                 # the 128x128 / 64x64 (/ 32x32) levels: weight and data gradient read the pooled gradient + argmax bytes (no re-expanded copy)
                 a = src if i == 0 else T.e[i - 1][lo:hi]
                 add, cod = (_p(skips[i]) if skips is not None and skips[i] is not None else None), _p(T.codes[i][lo:hi])
@@ -542,13 +535,8 @@ class Hourglass128:
             _lib.call("cgs_bf16_pool_expand", n, hw // 2, co, _p(dp), _p(skips[i]) if skips is not None else None, _p(T.codes[i][lo:hi]), _p(dyf), _s())
             a = src if i == 0 else T.e[i - 1][lo:hi]
             self._wgrad(T, plan, key, tag, n, hw, a, None, 2, dyf)
-            if i == 1 and H5CONV and self.h5:
-                dp = T.buf(f"de0_{tag}", (n, 64, 64, d[0]), torch.bfloat16, self.dev)
-                _lib.call("cgs_bf16_h5conv", _lib.H5_ENC1_BWD_DATA, n, _p(dyf), None, _p(self._wview(key)[0]), None, _p(dp), None, _s())
-            elif i > 0:
+            if i > 0:
                 dp = self._dgrad(T, key, dyf, f"de{i - 1}_{tag}")
-            elif want_dx is not None and H5CONV and self.h5:
-                _lib.call("cgs_bf16_enc0_bwd_data", n, _p(dyf), _p(self._wview(key)[0]), _p(want_dx), _s())
             elif want_dx is not None:
                 ca = 3
                 _lib.call("cgs_genbf16_conv3x3_fwd_train", n, hw, co, 0, ca, 0, 1, _lib.ACT_NONE, 0.01, 0, 1, _p(dyf), None, _p(self.w16T[key]),
@@ -558,7 +546,7 @@ class Hourglass128:
         n, d, nb = T.n, self.d, self.nb
         ea = [t[n:2 * n] for t in T.e]
         do = T.buf("do0", (n, 64, 64, d[0]), torch.bfloat16, self.dev)
-        if H5CONV and HWGRAD and self.h5:        # fp32 dz read directly; LeakyReLU' and the 2x2 cell sums in the data gradients' epilogues
+        if self.h5:        # fp32 dz read directly; LeakyReLU' and the 2x2 cell sums in the data gradients' epilogues
             self._wgrad(T, plan, "masker.2", "m", n, 128, T.hm, None, 2, None, dy_f32=T.dzpre)
             dh = T.buf("dhm", (n, 128, 128, 16), torch.bfloat16, self.dev)
             _lib.call("cgs_bf16_mask2_bwd_data", n, _p(T.dzpre), _p(T.hm), _p(self._wview("masker.2")[0]), _p(dh), _s())
@@ -574,14 +562,14 @@ class Hourglass128:
             dcat = self._dgrad(T, "masker.0", dh, "dcat_m0")
             _lib.call("cgs_bf16_cat_split", n, 128, 3, d[0], 2, _p(dcat), None, _p(do), 0, _s())
         skips = [None] * 5
-        tail = TAIL and self.tail
+        tail = self.tail
         for i in ((0, 1) if tail else (0, 1, 2, 3)):
             key, hw = f"dec_model.{i}", 64 >> i
             self._wgrad(T, plan, key, "m", n, hw, ea[i], T.o[i + 1], 2, do)
             skips[i] = T.buf(f"dskip{i}", (n, hw, hw, d[i]), torch.bfloat16, self.dev)
             low_f32 = tail and i == 1        # the tail kernel below reads its d o (16x16) in fp32
             dlow = T.buf(f"do{i + 1}" + ("f" if low_f32 else ""), (n, hw // 2, hw // 2, d[i + 1]), torch.float32 if low_f32 else torch.bfloat16, self.dev)
-            if (i == 0 or (i == 1 and low_f32)) and H5CONV and self.h5:      # the two halves of d cat(e, up(o)) straight from the whole-strip kernel
+            if (i == 0 or (i == 1 and low_f32)) and self.h5:      # the two halves of d cat(e, up(o)) straight from the whole-strip kernel
                 w = self._wview(key)[0]
                 _lib.call("cgs_bf16_h5conv", _lib.H5_DEC0_BWD_SKIP if i == 0 else _lib.H5_DEC1_BWD_SKIP, n, _p(do), None, _p(w), None, _p(skips[i]), None, _s())
                 _lib.call("cgs_bf16_h5conv", _lib.H5_DEC0_BWD_LOW if i == 0 else _lib.H5_DEC1_BWD_LOW, n, _p(do), None, _p(w), None, _p(dlow), None, _s())
@@ -617,7 +605,7 @@ class Hourglass128:
         A, B = T.ab[n:], T.ab[:n]
         self._critic_forward(T, T.ab, 0, 2 * n, want_o5=True)
         self._masker_forward(T, A)
-        virt = MIX_VIRTUAL and MIX_BWD_FUSED and TAIL and H5CONV and HWGRAD and POOL_FUSED and self.tail
+        virt = self.tail      # the two mixes are formed inside features.0's forward / weight-gradient staging (no fp32 mix tensor, no mix kernel)
         if not virt and T.mixed is None:
             T.mixed = torch.empty((2 * n, 128, 128, 3), device=self.dev)
         mixsrc = MixSrc(A, B, T.Z) if virt else T.mixed
@@ -628,8 +616,8 @@ class Hourglass128:
                   _p(T.dpred), _s())
         first = T.plan_a is None
         pa, pb = hg.SlabPlan(), hg.SlabPlan()
-        sink = [] if (TAIL and self.tail) else None      # the head's weight gradients of the mix pass and the A pass: one launch at the end
-        if MIX_BWD_FUSED and H5CONV and HWGRAD and POOL_FUSED and self.h5:
+        sink = [] if self.tail else None      # the head's weight gradients of the mix pass and the A pass: one launch at the end
+        if self.h5:      # features.0's image gradient of the two mixes + cgs_mix_bwd as one kernel (cgs_bf16_enc0_bwd_mix)
             self._critic_backward(T, pa, "mix", mixsrc, 2 * n, 4 * n, mix_bwd=(A, B, self.L1 / nz, self.L2 / nz), head_sink=sink)
         else:
             if T.dmixed is None:

@@ -123,8 +123,8 @@ int cgs_mask_head_bwd(int32_t n, int32_t src_a, const void* x, const float* o0, 
  * z [n,64,64] = sigmoid(conv3x3(LeakyReLU(conv3x3(cat(x, up(o0)); w_m0, b_m0)); w_m2, b_m2)) without ever storing the
  * 16-channel intermediate (it is needed only by the backward pass).  x [n,64,64,3] of kind src_a (CGS_SRC_U8 / CGS_SRC_F32), o0 [n,32,32,8].
  * Since round 5 this is the training forward's kernel (cgs_mask_train_fwd) storing nothing but z: masker.0 and masker.2 on the
- * matrix cores from registers; z is bit-identical to the training forward's.  (cgs_mask_infer_fwd_tile, or CGS_MASK_INFER_KERNEL=tile in the
- * environment: the earlier tile kernel -- masker.0 into an LDS tile, masker.2 + sigmoid on that tile.)  cgs_mask_infer_fwd_packed: the same with
+ * matrix cores from registers; z is bit-identical to the training forward's.  (cgs_mask_infer_fwd_tile: the earlier tile
+ * kernel -- masker.0 into an LDS tile, masker.2 + sigmoid on that tile.)  cgs_mask_infer_fwd_packed: the same with
  * masker.0's per-lane weight registers w_m0_pack [40][64] as cgs_tail_dec_fwd_pack / cgs_tail_dec_fwd_dec0 build them (NULL: gathered
  * per workgroup).  Returns CGS_ERR_UNSUPPORTED in the VALU fallback build (use two cgs_conv3x3_fwd calls).          */
 int cgs_mask_infer_fwd(int32_t n, int32_t src_a, const void* x, const float* o0, const float* w_m0_hwio,
@@ -274,22 +274,13 @@ int cgs_critic_fwd_fused_pack(int32_t n, const cgs_tail_enc_weights* w, const vo
                               cgs_dropout drop_h1, const float* w_m0, float* m0_pack, cgs_stream_t stream);
 int cgs_tail_dec_fwd(int32_t n, const cgs_tail_dec_weights* w, const float* e1, const float* e2, const float* e3,
                      const float* o4, float* o3, float* o2, float* o1, cgs_stream_t stream);
-/* (round 6, BASELINE config 4: main.py:1130-1151 with fp16 conv kernels) cgs_tail_enc_fwd in eval mode / cgs_tail_dec_fwd with fp16 OPERANDS in
- * their 3x3 layers (features.6 / .10, nets.py:176-183; dec_model.3 / .2 / .1, nets.py:503-513) on v_mfma_f32_16x16x16_f16: fp32 accumulation,
- * fp32 tensors in and out, the Linear layers and the head in fp32.  Used by the fused fp16 inference path only (engine.infer(fp16=True)).   */
-int cgs_tail_enc_fwd_h16(int32_t n, const cgs_tail_enc_weights* w, const float* e1, float* e2, uint32_t* am2, float* e3,
-                         uint32_t* am3, float* e4, float* h1, float* pred, float* o4, cgs_stream_t stream);
-int cgs_tail_dec_fwd_h16(int32_t n, const cgs_tail_dec_weights* w, const float* e1, const float* e2, const float* e3,
-                         const float* o4, float* o3, float* o2, float* o1, cgs_stream_t stream);
-/* (round 6) Both of them in ONE launch, one workgroup per image, storing only what the -process path consumes (nets.py:176-194 + 501-513 in eval
- * mode; csrc/tail_infer.hip): e1 [n,16,16,8] -> pred [n] and o1 [n,16,16,8] (both fp32); the tiles between the layers hold halves and never leave
- * the workgroup.  wd = NULL and o1 = NULL: the critic alone.                                                                                  */
+/* (round 6, BASELINE config 4: main.py:1130-1151 with fp16 conv kernels) cgs_tail_enc_fwd in eval mode and cgs_tail_dec_fwd in ONE launch with fp16
+ * OPERANDS in every layer but the head's Linear layers (v_mfma_f32_16x16x16_f16, fp32 accumulation), one workgroup per image, storing only what the
+ * -process path consumes (nets.py:176-194 + 501-513 in eval mode; csrc/tail_infer.hip): e1 [n,16,16,8] -> pred [n] and o1 [n,16,16,8] (both fp32);
+ * the tiles between the layers hold halves and never leave the workgroup.  wd = NULL and o1 = NULL: the critic alone.  Used by the fused fp16
+ * inference path (engine.infer(fp16=True)) and by config 5's inference.                                                                        */
 int cgs_tail_infer_h16(int32_t n, const cgs_tail_enc_weights* we, const cgs_tail_dec_weights* wd, const float* e1, float* pred, float* o1,
                        cgs_stream_t stream);
-/* ... and features.3 in front of it (cgs_f16_enc1_fwd + cgs_tail_infer_h16 in one launch; nets.py:173-175 in eval mode): e0 fp16 [n,32,32,8] as
- * cgs_f16_enc0_fwd writes it, w3 / b3 = features.3's HWIO weights and bias; e1 is never stored.                                              */
-int cgs_f16_enc1_tail_infer(int32_t n, const void* e0_f16, const float* w3, const float* b3, const cgs_tail_enc_weights* we,
-                            const cgs_tail_dec_weights* wd, float* pred, float* o1, cgs_stream_t stream);
 /* cgs_tail_dec_fwd + (m0_pack != NULL) one extra workgroup that packs masker.0's HWIO weights w_m0 [9][11][16] into the mask head
  * forward's weight registers m0_pack [40 * 64] (cgs_mask_train_fwd_packed).                                                     */
 int cgs_tail_dec_fwd_pack(int32_t n, const cgs_tail_dec_weights* w, const float* e1, const float* e2, const float* e3,

@@ -480,36 +480,27 @@ def test_config5_training_step_vs_autograd_of_the_build_restatement(n, chfak, ge
     the measured worst, 0.99962 / 0.030 at n = 256 and 0.99798 / 0.064 at n = 6; bf16 carries 8 significant bits and the
     mask head sums 16 k pixels per weight; a pool-argmax flip between the bf16 and fp32 forward moves a whole window's gradient),
     parameters after the Adam step within 2.2e-3 absolute (lr = 1e-3: the update is +-lr).
-    Kernel paths: chfak 1 on its dedicated whole-strip / tail kernels (the benchmarked form); the same model with those switched off
+    Kernel paths: chfak 1 on its dedicated whole-strip / tail kernels (the benchmarked form); the same model built with dedicated=False
     (generic = True) on the shape-generic 16-bit family (chfak != 1 is an inference-only configuration: see the test below)."""
     from cgs_amd import hourglass128
     pc = orc.seeded_params(orc.critic128_shapes(chfak), 31)
     pm = orc.seeded_params(orc.masker128_shapes(chfak), 32)
-    flags = ("TAIL", "H5CONV", "HWGRAD", "POOL_FUSED", "ENC0_DIRECT")
-    saved_flags = {k: getattr(hourglass128, k) for k in flags}
-    if generic:
-        for k in flags:
-            setattr(hourglass128, k, False)
     rs = np.random.RandomState(n)
     A = rs.randint(0, 256, (n, 128, 128, 3)).astype(np.uint8)
     B = rs.randint(0, 256, (n, 128, 128, 3)).astype(np.uint8)
     A[: n // 2] = (A[: n // 2] * 0.4).astype(np.uint8)
     Y = rs.rand(n).astype(np.float32)
-    try:
-        net = hourglass128.Hourglass128(pc, pm, chfak=chfak)
-        assert net.tail == (chfak == 1) and net.h5 == (chfak == 1)
-        losses = net.phase2_step(torch.from_numpy(A).cuda(), torch.from_numpy(B).cuda(), torch.from_numpy(Y).cuda(), use_graph=False)
-        torch.cuda.synchronize()
-        got_l = losses.cpu().tolist()
-        gc, gm = _grad_dicts(net)
-        # a second and third step through the HIP graph run and stay finite (same kernel path)
-        l2 = net.phase2_step(use_graph=True)
-        l3 = net.phase2_step()
-        torch.cuda.synchronize()
-        assert torch.isfinite(l2).all() and torch.isfinite(l3).all() and int(net.step_t.item()) == 3
-    finally:
-        for k, v in saved_flags.items():
-            setattr(hourglass128, k, v)
+    net = hourglass128.Hourglass128(pc, pm, chfak=chfak, dedicated=not generic)
+    assert net.tail == net.h5 == (chfak == 1 and not generic)
+    losses = net.phase2_step(torch.from_numpy(A).cuda(), torch.from_numpy(B).cuda(), torch.from_numpy(Y).cuda(), use_graph=False)
+    torch.cuda.synchronize()
+    got_l = losses.cpu().tolist()
+    gc, gm = _grad_dicts(net)
+    # a second and third step through the HIP graph run and stay finite (same kernel path)
+    l2 = net.phase2_step(use_graph=True)
+    l3 = net.phase2_step()
+    torch.cuda.synchronize()
+    assert torch.isfinite(l2).all() and torch.isfinite(l3).all() and int(net.step_t.item()) == 3
     torch.set_num_threads(16)
     Pc, Pm = orc.leafify(pc), orc.leafify(pm)
     total, parts, Z, pred = orc.hourglass128_phase2_loss(Pc, Pm, torch.from_numpy(A).permute(0, 3, 1, 2).float() / 255.0,

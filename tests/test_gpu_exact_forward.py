@@ -256,7 +256,7 @@ def test_tail_enc_fwd(env, with_o4):
     run_form(env, f"cgs_tail_enc_fwd(o4={with_o4})", {"e1": F32}, outs, launch)
 
 
-@pytest.mark.parametrize("entry", ["cgs_tail_dec_fwd", "cgs_tail_dec_fwd_pack", "cgs_tail_dec_fwd_h16"])
+@pytest.mark.parametrize("entry", ["cgs_tail_dec_fwd", "cgs_tail_dec_fwd_pack"])
 def test_tail_dec_fwd(env, entry):
     L = env["lib"]
 
@@ -300,15 +300,6 @@ def test_f16_dec0_fwd(env):
     run_form(env, "cgs_f16_dec0_fwd", {"e0": F16, "o1": F32}, {"o0": F16}, launch)
 
 
-def test_tail_enc_fwd_h16(env):
-    L = env["lib"]
-
-    def launch(n, I, O):
-        tw = enc_w(env)
-        L.call("cgs_tail_enc_fwd_h16", n, C.byref(tw), I["e1"], O["e2"], O["am2"], O["e3"], O["am3"], O["e4"], O["h1"], O["pred"], O["o4"], stream())
-    run_form(env, "cgs_tail_enc_fwd_h16", {"e1": F32}, ENC_OUT, launch)
-
-
 @pytest.mark.parametrize("decoder", [True, False])
 def test_tail_infer_h16(env, decoder):
     L = env["lib"]
@@ -318,15 +309,3 @@ def test_tail_infer_h16(env, decoder):
         tw, td = enc_w(env), dec_w(env)
         L.call("cgs_tail_infer_h16", n, C.byref(tw), C.byref(td) if decoder else None, I["e1"], O["pred"], O.get("o1"), stream())
     run_form(env, f"cgs_tail_infer_h16(decoder={decoder})", {"e1": F32}, outs, launch)
-
-
-@pytest.mark.parametrize("decoder", [True, False])
-def test_f16_enc1_tail_infer(env, decoder):
-    L = env["lib"]
-    outs = {"pred": F32, "o1": F32} if decoder else {"pred": F32}
-
-    def launch(n, I, O):
-        tw, td = enc_w(env), dec_w(env)
-        L.call("cgs_f16_enc1_tail_infer", n, I["e0"], wc(env, "features.3.weight"), wc(env, "features.3.bias"), C.byref(tw),
-               C.byref(td) if decoder else None, O["pred"], O.get("o1"), stream())
-    run_form(env, f"cgs_f16_enc1_tail_infer(decoder={decoder})", {"e0": F16}, outs, launch)

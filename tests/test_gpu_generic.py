@@ -224,10 +224,10 @@ def test_config4_batch2048_fp16_inference_vs_fp32_oracle(g1):
         assert ((Z.cpu().numpy() > 0.5) != (rz > 0.5)).mean() < 1e-3
 
 
-def test_config4_tail_launch_forms_agree(g1, monkeypatch):
-    """The four forms of the fused fp16 inference path between features.0 and dec_model.0 (engine.F16_TAILS: fp32 tail kernels, the two tail launches
-    with fp16 operands -- csrc/tail_h16.h --, one launch per image on fp16 tiles -- csrc/tail_infer.hip, the default --, and that launch with
-    features.3 in front) against each other: same frames, same weights; they differ by fp16 roundings of the 16x16-and-smaller maps only."""
+def test_config4_tail_launch_forms_agree(g1):
+    """The fused fp16 inference path's layers between features.3 and dec_model.0 -- one launch per image on fp16 tiles, csrc/tail_infer.hip -- against
+    the two fp32 tail kernels in their place (_infer_f16_fused(fp32_tail=True)): same frames, same weights; they differ by fp16 roundings of the
+    16x16-and-smaller maps only."""
     from cgs_amd import engine
     dev = torch.device("cuda:0")
     pc, pm = g1
@@ -238,17 +238,17 @@ def test_config4_tail_launch_forms_agree(g1, monkeypatch):
     for b in (1, 3, 300, 1100):      # (ragged: not multiples of anything the kernels tile by; 1100 = more images than persistent workgroups)
         x = xall[:b].contiguous()
         out = {}
-        for form in ("0", "1", "fused", "fused1"):
-            monkeypatch.setattr(engine, "F16_TAILS", form)
-            p, z = e.infer(x, fp16=True)
-            p2, _ = e.infer(x, fp16=True, want_mask=False)
+        for form, kw in (("fp32", dict(fp32_tail=True)), ("fused", {})):
+            p, z = e._infer_f16_fused(x, True, **kw)
+            p2, _ = e._infer_f16_fused(x, False, **kw)
             assert torch.equal(p, p2), form            # the critic-only instance computes the same values
             out[form] = (p.cpu().numpy().astype(np.float64), z.cpu().numpy().astype(np.float64))
-        for form in ("1", "fused", "fused1"):
-            dp = np.abs(out[form][0] - out["0"][0]).max()
-            dz = np.abs(out[form][1] - out["0"][1]).max()
-            print(f"config 4 tails, batch {b}, form {form!r} vs the fp32 tail kernels: |dpred| max {dp:.2e}, |dZ| max {dz:.2e}")
-            assert dp < 2e-5 and dz < 5e-5, (b, form)
+        pi, zi = e.infer(x, fp16=True)                 # what infer() runs is the fused form
+        assert torch.equal(pi, p) and torch.equal(zi, z)
+        dp = np.abs(out["fused"][0] - out["fp32"][0]).max()
+        dz = np.abs(out["fused"][1] - out["fp32"][1]).max()
+        print(f"config 4 tails, batch {b}, the fused kernel vs the fp32 tail kernels: |dpred| max {dp:.2e}, |dZ| max {dz:.2e}")
+        assert dp < 2e-5 and dz < 5e-5, b
         # a batch is the concatenation of its images: image 0 of every batch equals the one-image batch's result bit for bit
         if b == 1:
             first = out["fused"]
