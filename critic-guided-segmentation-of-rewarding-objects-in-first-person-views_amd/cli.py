@@ -57,7 +57,11 @@ def build_parser():
     # folder of stills, through the -fit machinery, and the masks drawn on the frames at the frames' size as a video (overlay.py).
     # --smooth R filters the masks along time over +-R frames first (temporal.py; 0 = off), --smooth-range is its colour sigma,
     # --smooth-motion S lets its taps follow block-matched motion of up to S cells a frame (0 = off).  The defaults (0, 16, 0, overlay,
-    # 0,255,0, 0.5, 1) are filled in by check_video_flags, which has to see what was given
+    # 0,255,0, 0.5, 1) are filled in by check_video_flags, which has to see what was given.
+    # --overlay-tracks T labels the thresholded masks (8-connected, components below --overlay-min-area A cells dropped), follows the
+    # objects through the stream at link IoU T (objects.TrackStream) and draws every object in its track's colour with its bounding box,
+    # --overlay-boxes B pixels thick (0: none), and its track number (overlay.compose_tracks); leaves {R}/{stem}-objects.json and
+    # {R}/{stem}-tracks.json.  A and B default to 1
     p.add_argument("--source-video", type=str, default="")
     p.add_argument("--overlay-video", type=str, default="")
     p.add_argument("--smooth", type=int, default=None)
@@ -67,6 +71,9 @@ def build_parser():
     p.add_argument("--overlay-color", type=str, default=None)
     p.add_argument("--overlay-alpha", type=float, default=None)
     p.add_argument("--overlay-outline", type=int, default=None)
+    p.add_argument("--overlay-tracks", type=str, default=None)
+    p.add_argument("--overlay-min-area", type=int, default=None)
+    p.add_argument("--overlay-boxes", type=int, default=None)
     for flag in ("-masker", "-critic", "-cload", "-mload", "-staticnorm", "-visbesteval", "-salglobal"):
         p.add_argument(flag, type=bool, default=True)
     p.add_argument("--salience-thresh", type=float, default="1.5")
@@ -214,13 +221,16 @@ def check_fit_flags(args):
 def check_video_flags(args):
     """--source-video / --overlay-video and the --smooth* / --overlay-* options: combinations that could not run and values out of range
     are refused here, before any GPU work; the defaults (--smooth 0, --smooth-range 16, --smooth-motion 0, --overlay-layout overlay,
-    --overlay-color 0,255,0, --overlay-alpha 0.5, --overlay-outline 1) are filled in, --overlay-color becomes (r, g, b), args.overlay_alpha256 is
-    round(256 alpha), and -fit is switched on: a video goes through the -fit machinery.  The frame size is checked after the probe
+    --overlay-color 0,255,0, --overlay-alpha 0.5, --overlay-outline 1; with --overlay-tracks T also --overlay-min-area 1, --overlay-boxes 1) are filled
+    in, --overlay-color becomes (r, g, b), args.overlay_alpha256 is round(256 alpha), --overlay-tracks becomes a float (None without the
+    flag), and -fit is switched on: a video goes through the -fit machinery.  The frame size is checked after the probe
     (check_video_size)."""
     given = [f for f, v in (("--overlay-video", args.overlay_video or None), ("--smooth", args.smooth), ("--smooth-range", args.smooth_range),
                             ("--smooth-motion", args.smooth_motion),
                             ("--overlay-layout", args.overlay_layout), ("--overlay-color", args.overlay_color),
-                            ("--overlay-alpha", args.overlay_alpha), ("--overlay-outline", args.overlay_outline)) if v is not None]
+                            ("--overlay-alpha", args.overlay_alpha), ("--overlay-outline", args.overlay_outline),
+                            ("--overlay-tracks", args.overlay_tracks), ("--overlay-min-area", args.overlay_min_area),
+                            ("--overlay-boxes", args.overlay_boxes)) if v is not None]
     if not args.source_video:
         if given:
             raise ValueError(f"{' / '.join(given)} belong to --source-video: give --source-video")
@@ -255,6 +265,22 @@ def check_video_flags(args):
     args.overlay_alpha256 = named("--overlay-alpha", overlay.to_alpha256, args.overlay_alpha)
     args.overlay_outline = named("--overlay-outline", overlay.check_outline,
                                  overlay.OUTLINE if args.overlay_outline is None else args.overlay_outline)
+    if args.overlay_tracks is None:
+        extra = [f for f, v in (("--overlay-min-area", args.overlay_min_area), ("--overlay-boxes", args.overlay_boxes)) if v is not None]
+        if extra:
+            raise ValueError(f"{' / '.join(extra)} belong to --overlay-tracks: give --overlay-tracks T")
+    else:
+        from .objects import parse_track_iou
+        try:
+            args.overlay_tracks = parse_track_iou(args.overlay_tracks)
+        except ValueError as e:
+            raise ValueError(f"--overlay-tracks: {str(e).replace('--track-iou ', '', 1)}") from None
+        if not args.binarymaskthreshold:
+            raise ValueError("--overlay-tracks labels the thresholded mask: --binarymaskthreshold 0 leaves none")
+        args.overlay_min_area = 1 if args.overlay_min_area is None else args.overlay_min_area
+        if args.overlay_min_area < 1:
+            raise ValueError(f"--overlay-min-area {args.overlay_min_area}: an object has at least 1 cell")
+        args.overlay_boxes = named("--overlay-boxes", overlay.check_boxes, overlay.BOXES if args.overlay_boxes is None else args.overlay_boxes)
     args.fit = True
 
 

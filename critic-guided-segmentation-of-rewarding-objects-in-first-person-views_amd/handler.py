@@ -560,12 +560,19 @@ class Handler:
              after it, with their shrunk frames, with --smooth-motion S > 0 along temporal.flow of that same window -- then fit.up (the
              grey byte, and the hard mask at --binarymaskthreshold, inclusive; no hard mask and so no outline at threshold 0),
              overlay.compose, an asynchronous copy into a pinned double buffer and the encoder (video.ffmpeg_argv with the probed rate).
+             With --overlay-tracks T the smoothed masks are labelled (objects.label at the threshold, 8-connected, --overlay-min-area),
+             objects.TrackStream numbers the objects through the chunks as objects.track numbers the whole stack, and
+             overlay.compose_tracks draws each in its track's colour with its box and number in place of overlay.compose.
         Stage A of chunk c + 1 runs before stage B of chunk c (a chunk waits until R frames after it are there, or the stream has ended).
-        No PNG is written.  Rank 0 leaves {R}/{stem of OUT}.json.  Returns the 64 x 64 masks [n,1,64,64], the smoothed ones with --smooth."""
+        No PNG is written.  Rank 0 leaves {R}/{stem of OUT}.json, with --overlay-tracks also {R}/{stem}-objects.json and
+        {R}/{stem}-tracks.json (process.video_reports; skipped beyond objects.TRACK_MAX_FRAMES frames, the video is complete all the
+        same).  Returns the 64 x 64 masks [n,1,64,64], the smoothed ones with --smooth."""
         from collections import deque
         import subprocess
-        from . import cli, fit, overlay, temporal, video_in
+        from . import cli, fit, objects, overlay, temporal, video_in
         args = self.args
+        track_iou = getattr(args, "overlay_tracks", None)
+        stream = objects.TrackStream(track_iou, max_objects=overlay.MAX_TRACK_OBJECTS) if track_iou is not None else None
         ffmpeg, ffprobe = video_in.find_ffmpeg(), video_in.find_ffprobe()
         W, H, rate = video_in.probe(path, ffprobe)
         k = args.overlay_panels
@@ -625,8 +632,15 @@ class Handler:
                 Zs = Z
             masks.append(Zs.cpu().numpy()[:, None])
             up = fit.up(Zs, guide, low, thresh=thr if thr else None, want=("grey", "hard") if thr else ("grey",), **sig)
-            frames = overlay.compose(guide, up.grey, up.hard, color=args.overlay_color, alpha256=args.overlay_alpha256,
-                                     outline=args.overlay_outline, layout=args.overlay_layout)
+            if stream is not None:
+                res = objects.label(Zs, thresh=thr, inclusive=True, connectivity=8, min_area=args.overlay_min_area,
+                                    max_objects=overlay.MAX_TRACK_OBJECTS)
+                frames = overlay.compose_tracks(guide, up.grey, up.hard, res.labels, stream.push(res.labels), res.table,
+                                                color=args.overlay_color, alpha256=args.overlay_alpha256, outline=args.overlay_outline,
+                                                boxes=args.overlay_boxes, layout=args.overlay_layout)
+            else:
+                frames = overlay.compose(guide, up.grey, up.hard, color=args.overlay_color, alpha256=args.overlay_alpha256,
+                                         outline=args.overlay_outline, layout=args.overlay_layout)
             writer.submit(frames)
 
         failure, done = None, 0
@@ -664,11 +678,22 @@ class Handler:
             length, saturated = moved.tolist()
             smooth["motion"] = {"search": S, "block": temporal.BLOCK, "mean_cells_per_frame": length / max(vectors, 1),
                                 "saturated": saturated / max(vectors, 1)}
+        tracks = {}
+        if stream is not None:
+            reports = None
+            if len(M) <= objects.TRACK_MAX_FRAMES:
+                reports = process.video_reports(args, M, stem, self.device, self.rank)
+            else:
+                print(f"--overlay-tracks: {len(M)} frames are more than the {objects.TRACK_MAX_FRAMES} one report holds: the video is complete, "
+                      f"{stem}-objects.json and {stem}-tracks.json are not written")
+            tracks = {"tracks": {"iou": track_iou, "min_area": args.overlay_min_area, "boxes": args.overlay_boxes,
+                                 "scale": overlay.scale(H, W), "max_objects": overlay.MAX_TRACK_OBJECTS, "n_tracks": int(stream.n_tracks),
+                                 "reports": reports}}
         write_json(f"{out_dir}/{stem}.json", {
             "frame_size": [H, W], "frames": len(M), "rate": rate, "layout": args.overlay_layout, "color": list(args.overlay_color),
             "alpha256": args.overlay_alpha256, "outline": args.overlay_outline, "threshold": thr,
             "smooth": smooth,
-            "sigma_spatial": args.fit_spatial, "sigma_range": args.fit_range}, self.rank)
+            "sigma_spatial": args.fit_spatial, "sigma_range": args.fit_range, **tracks}, self.rank)
         return M
 
     def _sweep_masks(self, X, to_device, progress, want_saliency=False, fp16=False, batchsize=128, train_mode=None):

@@ -10,7 +10,8 @@ up the matched pairs' IoU on the device, and ``parse_match_iou`` / ``match_repor
 ``track`` (csrc/objects_track.hip) follows the objects of one label stack from frame to frame (mutual best partners above an IoU
 threshold, chains resolved on the device), ``switches`` counts identity switches of a prediction's tracks against the truth's, and
 ``parse_track_iou`` / ``natural_order`` / ``track_report`` / ``track_rows`` are the pure host helpers of ``-objects --track-iou``
-(eval_tracks.json, tracks.json)."""
+(eval_tracks.json, tracks.json).  ``TrackStream`` gives ``track``'s numbers to a label stack that arrives in chunks
+(``-process --source-video --overlay-tracks``); ``stream_remap`` is its arithmetic."""
 import re
 from collections import namedtuple
 
@@ -234,6 +235,60 @@ def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, w
                   totals.data_ptr(), table.data_ptr(), painted.data_ptr() if want_labels else None, rgb.data_ptr() if want_rgb else None,
                   scratch.data_ptr(), scratch.numel() * 8, torch.cuda.current_stream().cuda_stream)
     return Tracks(prev, trk, totals[0], totals[1], totals[2], totals[3], table, painted, rgb)
+
+
+def stream_remap(local, carried_local, carried_global, c0, n_tracks):
+    """The track numbers of a chunk tracked behind one carried frame, as numbers of the whole stream.  local: int [m,K], rows 1.. of
+    ``track(cat(carry, chunk)).track``; carried_local: int [K], its row 0 (every object of the carried frame heads a track there, so
+    these are 1..c0 in label order); carried_global: int [K], the carried frame's numbers in the stream; c0: the carried frame's object
+    count; n_tracks: the stream's tracks before this chunk (both scalars, tensors or ints).  A local number t of a carried object maps
+    to that object's number, every other t to n_tracks + (t - c0) -- heads are numbered by frame, then label, in both -- and 0 to 0.
+    Returns int64 [m,K].  torch gather / scatter on the tensors' device, no synchronisation."""
+    local, carried_local = local.to(torch.int64), carried_local.to(torch.int64)
+    size = local.shape[0] * local.shape[1] + carried_local.shape[0] + 1           # more than the largest local number
+    lut = torch.arange(size, dtype=torch.int64, device=local.device) - c0 + n_tracks
+    lut.scatter_(0, carried_local, carried_global.to(torch.int64))                # (an absent object writes 0 at 0)
+    lut[0] = 0
+    return lut[local]
+
+
+class TrackStream:
+    """``track`` for a label stack that comes in chunks: for every split of a stack, the concatenated results of ``push`` are
+    ``track(stack, iou, max_objects).track`` bit for bit.  A link depends on its two frames only and tracks are numbered by their first
+    frame, then label, so the last frame of a chunk (its labels and its numbers) is all that the next chunk needs.  ``n_tracks`` is the
+    number of tracks so far, an int32 scalar on the device (0 before the first push); nothing here synchronises with the host."""
+
+    def __init__(self, iou, max_objects=64):
+        self.milli = _track_milli(iou)
+        self.iou = self.milli / 1000
+        self.max_objects = _as_int(max_objects, "max_objects")
+        if not 1 <= self.max_objects <= MATCH_MAX_OBJECTS:
+            raise ValueError(f"max_objects must be 1..{MATCH_MAX_OBJECTS}, got {max_objects}")
+        self.n_tracks = 0
+        self._carry = None                     # (labels [1,h,w], numbers int32 [K], object count) of the last frame pushed
+
+    def push(self, labels):
+        """labels: int32 device tensor [m,h,w], m >= 1, of the shape and on the device of the first push, m + 1 <= 2^17.  Returns int32
+        [m,K]: the track number in the whole stream of every object, 0 where there is none."""
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.dim() != 3 or labels.shape[0] < 1:
+            raise ValueError("labels must be an int32 tensor [m,h,w] with at least one frame, got "
+                             + (f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, torch.Tensor) else type(labels).__name__))
+        m = int(labels.shape[0])
+        if m + 1 > TRACK_MAX_FRAMES:
+            raise ValueError(f"a chunk of {m} frames: with the carried frame at most {TRACK_MAX_FRAMES} are tracked at once")
+        if self._carry is None:
+            tr = track(labels, iou=self.iou, max_objects=self.max_objects, max_tracks=1)
+            ids, self.n_tracks = tr.track, tr.n_tracks
+        else:
+            last, last_ids, c0 = self._carry
+            if labels.shape[1:] != last.shape[1:] or labels.device != last.device:
+                raise ValueError(f"labels {tuple(labels.shape)} on {labels.device}: the stream holds frames of {tuple(last.shape[1:])} on "
+                                 f"{last.device}")
+            tr = track(torch.cat((last, labels)), iou=self.iou, max_objects=self.max_objects, max_tracks=1)
+            ids = stream_remap(tr.track[1:], tr.track[0], last_ids, c0, self.n_tracks).to(torch.int32)
+            self.n_tracks = (self.n_tracks + tr.n_tracks - c0).to(torch.int32)
+        self._carry = (labels[-1:].contiguous().clone(), ids[-1].clone(), (ids[-1] > 0).sum())
+        return ids
 
 
 def switches(truth_prev, pred_track, best, iou):

@@ -5,7 +5,10 @@ alone, frame | overlay, or frame | overlay | grey.  Integers throughout, so a re
 
 The outline is the set of on pixels within Manhattan distance t - 1 of an off pixel, where a pixel OUTSIDE the frame counts as on: a
 mask that the frame cuts draws no line along the frame's edge.  boundary.py scores with the opposite convention (there the frame's edge
-belongs to an object's outline); a drawn line along the border of the picture would only be noise."""
+belongs to an object's outline); a drawn line along the border of the picture would only be noise.
+
+``compose_tracks`` (csrc/overlay_tracks.hip, ``--overlay-tracks``) is ``compose`` with a colour per tracked object, the objects' bounding
+boxes and their track numbers; ``FONT`` holds the digits it draws, ``check_boxes`` / ``scale`` are its pure host helpers."""
 import numpy as np
 import torch
 
@@ -16,6 +19,22 @@ LAYOUTS = {"overlay": _lib.OVERLAY_ONLY, "side": _lib.OVERLAY_SIDE, "triple": _l
 MAX_OUTLINE = _lib.OVERLAY_MAX_OUTLINE
 COLOR, ALPHA, OUTLINE, LAYOUT = (0, 255, 0), 0.5, 1, "overlay"
 NONTEMPORAL = True
+MAX_BOXES, MAX_TRACK_OBJECTS, BOXES = _lib.OVERLAY_MAX_BOXES, _lib.OVERLAY_MAX_TRACK_OBJECTS, 1
+
+
+def _glyphs(*rows):
+    return np.array([[int(r, 2) for r in g.split()] for g in rows], dtype=np.uint8)
+
+
+# the digits 0..9 as 5 x 7 glyphs, a byte per glyph row from the top, bit 4 the leftmost pixel: the only copy of their shapes (the kernel
+# reads them from this array)
+FONT = _glyphs("01110 10001 10011 10101 11001 10001 01110", "00100 01100 00100 00100 00100 00100 01110",
+               "01110 10001 00001 00010 00100 01000 11111", "11111 00010 00100 00010 00001 10001 01110",
+               "00010 00110 01010 10010 11111 00010 00010", "11111 10000 11110 00001 00001 10001 01110",
+               "00110 01000 10000 11110 10001 10001 01110", "11111 00001 00010 00100 01000 01000 01000",
+               "01110 10001 10001 01110 10001 10001 01110", "01110 10001 10001 01111 00001 00010 01100")
+FONT.setflags(write=False)
+_font_on_device = {}            # (device, the font's bytes) -> its device copy: an upload per call would synchronise the stream
 
 
 def panels(layout):
@@ -59,6 +78,17 @@ def check_outline(t, name="outline"):
     return int(t)
 
 
+def check_boxes(b, name="boxes"):
+    if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 0 <= b <= MAX_BOXES:
+        raise ValueError(f"{name} = {b!r}: a box's thickness is an integer 0..{MAX_BOXES} pixels (0: no boxes, no numbers)")
+    return int(b)
+
+
+def scale(h, w):
+    """The size of a font pixel on frames of h x w: max(1, min(h, w) // 256)."""
+    return max(1, min(int(h), int(w)) // 256)
+
+
 def compose(guide, grey, hard=None, color=COLOR, alpha256=128, outline=OUTLINE, layout=LAYOUT, out=None, nontemporal=NONTEMPORAL):
     """guide: device tensor uint8 [n,H,W,3], the frames, 64 <= H, W <= 4096.  grey: uint8 [n,H,W] (fit.up's grey).  hard: uint8 / bool
     [n,H,W], zero / non-zero, or None (no outline).  color (r, g, b); alpha256: the opacity as an integer 0..256; outline: thickness 0..4;
@@ -98,4 +128,76 @@ def compose(guide, grey, hard=None, color=COLOR, alpha256=128, outline=OUTLINE, 
         _lib.call("cgs_overlay_compose", guide.data_ptr(), grey.data_ptr(), hard.data_ptr() if hard is not None else None, n, h, w, r, g, b,
                   int(alpha256), outline, k, _lib.OVERLAY_NONTEMPORAL if nontemporal else 0, out.data_ptr(),
                   torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def _device_font(font, device):
+    if isinstance(font, torch.Tensor):
+        if font.dtype != torch.uint8 or tuple(font.shape) != FONT.shape:
+            raise ValueError(f"font must be uint8 {list(FONT.shape)}, got {font.dtype} {tuple(font.shape)}")
+        return font.contiguous()
+    font = np.asarray(font)
+    if font.dtype != np.uint8 or font.shape != FONT.shape:
+        raise ValueError(f"font must be uint8 {list(FONT.shape)}, got {font.dtype} {font.shape}")
+    key = (str(device), font.tobytes())
+    if key not in _font_on_device:
+        _font_on_device[key] = torch.from_numpy(np.array(font)).to(device)
+    return _font_on_device[key]
+
+
+def compose_tracks(guide, grey, hard, labels, ids, table, font=FONT, color=COLOR, alpha256=128, outline=OUTLINE, boxes=BOXES, layout=LAYOUT,
+                   out=None, nontemporal=NONTEMPORAL):
+    """``compose`` with the tracked objects drawn: guide, grey, hard, color, alpha256, outline, layout, out, nontemporal as there (hard may
+    be None).  labels: int32 [n,64,64], ``objects.label``'s labels of the 64 x 64 masks; ids: int32 [n,K], K <= 64, the track number of
+    every object (``objects.TrackStream.push``; 0: none); table: int32 [n,K,8], ``objects.label``'s table (area and bounding box are
+    read; a row with area 0 is no object); font: uint8 [10,7] (array or device tensor), a byte per glyph row, bit 4 leftmost; boxes: the
+    thickness of a bounding box 0..4 (0: no boxes and no numbers).  Returns uint8 [n,H,k W,3].
+    A pixel takes the colour of its object's track, 64 + ((t 2654435761 mod 2^32) >> 8 c & 255) 191 // 255 (``objects.track``'s rgb),
+    its object being the label of its home cell (fit.home_cells) or, when that is 0, of the nearest labelled cell of the 5 x 5 cells
+    around it; `color` where there is none.  Every object with a track gets its box on the cells' pixel tiling and, at the box's top left
+    corner, a plate with the track number in digits scale(H, W) font pixels big.  Plates lie over borders, borders over the outline.
+    Integers throughout (include/cgs_hip.h has every formula).  No CPU path: raises CgsError without a GPU."""
+    n, h, w = _frames("guide", guide)
+    k = panels(layout)
+    r, g, b = parse_color(color)
+    outline, boxes = check_outline(outline), check_boxes(boxes)
+    if isinstance(alpha256, bool) or not isinstance(alpha256, (int, np.integer)) or not 0 <= alpha256 <= 256:
+        raise ValueError(f"alpha256 = {alpha256!r}: an integer 0..256 (overlay.to_alpha256 maps an opacity to it)")
+    if not isinstance(grey, torch.Tensor) or grey.dtype != torch.uint8 or tuple(grey.shape) != (n, h, w):
+        raise ValueError(f"grey must be a uint8 tensor [{n},{h},{w}], got "
+                         + (f"{grey.dtype} {tuple(grey.shape)}" if isinstance(grey, torch.Tensor) else type(grey).__name__))
+    if hard is not None and (not isinstance(hard, torch.Tensor) or hard.dtype not in (torch.uint8, torch.bool) or tuple(hard.shape) != (n, h, w)):
+        raise ValueError(f"hard must be a uint8 or bool tensor [{n},{h},{w}] or None, got "
+                         + (f"{hard.dtype} {tuple(hard.shape)}" if isinstance(hard, torch.Tensor) else type(hard).__name__))
+    for name, t in (("labels", labels), ("ids", ids), ("table", table)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise ValueError(f"{name} must be an int32 tensor, got " + (str(t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
+    side = _lib.FIT_SIDE
+    if tuple(labels.shape) != (n, side, side):
+        raise ValueError(f"labels must be [{n},{side},{side}] for {n} frames, got {tuple(labels.shape)}")
+    if ids.dim() != 2 or ids.shape[0] != n or not 1 <= ids.shape[1] <= MAX_TRACK_OBJECTS:
+        raise ValueError(f"ids must be [{n},K] with K in 1..{MAX_TRACK_OBJECTS}, got {tuple(ids.shape)}")
+    K = int(ids.shape[1])
+    if tuple(table.shape) != (n, K, _lib.OBJ_FIELDS):
+        raise ValueError(f"table must be [{n},{K},{_lib.OBJ_FIELDS}] beside ids {tuple(ids.shape)}, got {tuple(table.shape)}")
+    if n > 65535:
+        raise ValueError(f"guide: at most 65535 frames a call, got {n}")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous()
+                            or tuple(out.shape) != (n, h, k * w, 3)):
+        raise ValueError(f"out must be a contiguous uint8 tensor [{n},{h},{k * w},3]")
+    tensors = (guide, grey, labels, ids, table) + ((hard,) if hard is not None else ()) + ((out,) if out is not None else ()) \
+        + ((font,) if isinstance(font, torch.Tensor) else ())
+    _need_gpu("overlay.compose_tracks (cgs_overlay_compose_tracks)", *tensors)
+    font = _device_font(font, guide.device)
+    guide, grey, labels, ids, table = (t if t.is_contiguous() else t.contiguous() for t in (guide, grey, labels, ids, table))
+    if hard is not None:
+        hard = hard.contiguous()
+        if hard.dtype == torch.bool:
+            hard = hard.view(torch.uint8)
+    if out is None:
+        out = torch.empty((n, h, k * w, 3), dtype=torch.uint8, device=guide.device)
+    with torch.cuda.device(guide.device):
+        _lib.call("cgs_overlay_compose_tracks", guide.data_ptr(), grey.data_ptr(), hard.data_ptr() if hard is not None else None,
+                  labels.data_ptr(), ids.data_ptr(), table.data_ptr(), font.data_ptr(), n, h, w, K, r, g, b, int(alpha256), outline, boxes, k,
+                  _lib.OVERLAY_NONTEMPORAL if nontemporal else 0, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
     return out

@@ -1,6 +1,7 @@
 """What the three ``-process`` paths of handler.Handler share (segment, _segment_fit, _segment_video): the folder listing, the chunk
 size, how a shrunk uint8 frame is fed to the network, the PNG columns with their by-position names, and ``-objects`` /
-``--track-iou`` on the 64 x 64 masks (objects.json, tracks.json and their PNGs).  Under data parallelism every rank makes the GPU
+``--track-iou`` on the 64 x 64 masks (objects.json, tracks.json and their PNGs; ``video_reports`` writes the two reports of
+``--source-video --overlay-tracks`` without PNGs).  Under data parallelism every rank makes the GPU
 calls and rank 0 writes."""
 import os
 
@@ -76,28 +77,50 @@ def objects_and_tracks(args, M, crf_mask, stems, device, rank):
         _tracks(args, res, head, stems, rank)
 
 
-def _objects(args, res, head, stems, width, rank):
-    """Rank 0 writes {R}/objects.json and per frame {R}/{stem}-objects-mask.png, the pixels of the kept objects as 0 / 255 grey RGB."""
+def video_reports(args, M, stem, device, rank):
+    """--source-video --overlay-tracks: the whole-stack reports of the masks M [n,1,64,64] that the stream returned, labelled as the
+    stream labelled them (threshold inclusive, 8-connected, --overlay-min-area), as {R}/{stem}-objects.json and {R}/{stem}-tracks.json
+    with the frames keyed "000000", "000001", ... in stream order and no PNG.  objects.TrackStream gives objects.track's numbers, so
+    the numbers of tracks.json are the ones drawn on the video.  Returns the two file names."""
+    thresh = float(args.binarymaskthreshold)
+    stack = torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(device)
+    res = objects.label(stack, thresh=thresh, inclusive=True, connectivity=8, min_area=args.overlay_min_area,
+                        max_objects=PROCESS_MAX_OBJECTS, want_labels=True, want_mask=False)
+    head = {"source": "thresholded-mask", "threshold": thresh, "connectivity": 8, "min_area": args.overlay_min_area}
+    stems = [f"{i:06d}" for i in range(len(M))]
+    names = (f"{stem}-objects.json", f"{stem}-tracks.json")
+    _objects(args, res, head, stems, M.shape[-1], rank, png=False, name=names[0])
+    _tracks(args, res, head, stems, rank, png=False, name=names[1], iou=args.overlay_tracks)
+    return list(names)
+
+
+def _objects(args, res, head, stems, width, rank, png=True, name="objects.json"):
+    """Rank 0 writes {R}/objects.json and per frame {R}/{stem}-objects-mask.png, the pixels of the kept objects as 0 / 255 grey RGB
+    (png=False: the report alone, as {R}/{name})."""
     from PIL import Image
     if rank != 0:
         return
-    kept, found, mask = res.kept.cpu().numpy(), res.found.cpu().numpy(), res.mask.cpu().numpy()
+    kept, found = res.kept.cpu().numpy(), res.found.cpu().numpy()
     rows = objects.table_rows(res.table, kept, width=width)
     out_dir = args.mask_output_imgs
-    write_json(f"{out_dir}/objects.json", {**head, "max_objects": PROCESS_MAX_OBJECTS, "frames": {
+    write_json(f"{out_dir}/{name}", {**head, "max_objects": PROCESS_MAX_OBJECTS, "frames": {
         stem: {"found": int(found[i]), "kept": int(kept[i]), "objects": rows[i]} for i, stem in enumerate(stems)}})
+    if not png:
+        return
+    mask = res.mask.cpu().numpy()
     for i, stem in enumerate(stems):
         Image.fromarray(np.repeat((mask[i] * np.uint8(255))[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-objects-mask.png")
 
 
-def _tracks(args, res, head, stems, rank):
+def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None):
     """The objects objects.json describes followed through the frames in natural order of their names on the GPU (objects.track);
-    labels above 64 are untracked.  Rank 0 writes {R}/tracks.json and per frame {R}/{stem}-tracks-mask.png, a colour per track."""
+    labels above 64 are untracked.  Rank 0 writes {R}/tracks.json and per frame {R}/{stem}-tracks-mask.png, a colour per track
+    (png=False: the report alone, as {R}/{name}; iou: the link threshold when it is not --track-iou's)."""
     from PIL import Image
-    K, iou = MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou)
+    K, iou = MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou) if iou is None else iou
     order = objects.natural_order(stems)                             # os.listdir's order is arbitrary; only the label stack is reordered
     pick = torch.tensor(order, dtype=torch.int64, device=res.labels.device)
-    tr = objects.track(res.labels[pick], iou=iou, max_objects=K, want_rgb=True)
+    tr = objects.track(res.labels[pick], iou=iou, max_objects=K, want_rgb=png)
     if rank != 0:
         return
     totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
@@ -105,7 +128,7 @@ def _tracks(args, res, head, stems, rank):
                                 (res.kept[pick] - K).clamp(min=0).sum())
     rows = objects.track_rows(tr.table, side["tracks"])
     names = [stems[i] for i in order]
-    prev, trk, rgb = tr.prev.cpu().numpy(), tr.track.cpu().numpy(), tr.rgb.cpu().numpy()
+    prev, trk = tr.prev.cpu().numpy(), tr.track.cpu().numpy()
     report = {**head, "max_objects": K, "track_iou": iou, "summary": side, "order": names,
               "frames": {stem: [{"label": int(l) + 1, "track": int(trk[j, l]), "prev": int(prev[j, l])} for l in np.flatnonzero(trk[j])]
                          for j, stem in enumerate(names)},
@@ -113,6 +136,9 @@ def _tracks(args, res, head, stems, rank):
                           "length": r["length"], "area_sum": r["area_sum"], "area_min": r["area_min"], "area_max": r["area_max"],
                           "link_iou": r["link_iou"]} for r in rows]}
     out_dir = args.mask_output_imgs
-    write_json(f"{out_dir}/tracks.json", report)
+    write_json(f"{out_dir}/{name}", report)
+    if not png:
+        return
+    rgb = tr.rgb.cpu().numpy()
     for j, stem in enumerate(names):
         Image.fromarray(rgb[j]).save(f"{out_dir}/{stem}-tracks-mask.png")

@@ -1053,6 +1053,45 @@ int cgs_overlay_compose(const uint8_t* guide, const uint8_t* grey, const uint8_t
                         int32_t g, int32_t b, int32_t alpha256, int32_t thickness, int32_t layout, int32_t flags, uint8_t* out,
                         cgs_stream_t stream);
 
+/* ---- tracked objects on the overlay video (csrc/overlay_tracks.hip; -process --source-video --overlay-tracks T) ---------------------------
+ * cgs_overlay_compose_tracks: cgs_overlay_compose with a colour per tracked object in place of the one tint, and every object's bounding
+ * box and track number drawn on the overlay panel.  Integers throughout, no atomics, deterministic; the frame panel ("side", "triple")
+ * and the grey panel are exactly cgs_overlay_compose's.
+ *   guide, grey, hard, n, h, w, r, g, b, alpha256, thickness, layout, flags, out   as cgs_overlay_compose; (r, g, b) is the colour of a
+ *             pixel without an object
+ *   labels    int32 [n][64][64]: cgs_objects_label's labels of the 64 x 64 masks (a value <= 0 is background)
+ *   ids       int32 [n][K]: the track number of object l = 1..K of a frame at [l - 1], a value <= 0 meaning none (K = max_objects)
+ *   table     int32 [n][K][CGS_OBJ_FIELDS]: cgs_objects_label's table; only area, x0, y0, x1, y1 are read.  A row with area <= 0, or with
+ *             a box that is not 0 <= x0 <= x1 <= 63, 0 <= y0 <= y1 <= 63, is no object
+ *   font      uint8 [CGS_OVERLAY_FONT_GLYPHS][CGS_OVERLAY_FONT_ROWS]: the digits 0..9, one byte per glyph row, top row first, bit 4 the
+ *             leftmost of 5 pixels; read from this pointer, the library holds no digit shapes of its own
+ *   boxes     B, the thickness of a box's border, 0..CGS_OVERLAY_MAX_BOXES pixels; 0: no boxes and no numbers
+ * Colour of track t >= 1: c_k = 64 + (((t * 2654435761) mod 2^32) >> 8 k & 255) * 191 / 255 for k = 0, 1, 2 (r, g, b) -- the rgb of
+ * cgs_objects_track.  Object of pixel (y, x): with (cy, cx) its home cell, ((2 p + 1) 32) / L on an axis of length L, the label
+ * labels[cy][cx] when that is in 1..K; when it is above K the pixel has no object; when it is <= 0, the label in 1..K among the cells
+ * (c'y, c'x) of the 5 x 5 window around the home cell (CGS_FIT_RADIUS), inside the grid, that minimises in 64 bits
+ *   dxn^2 h^2 + dyn^2 w^2,  dxn = (2 x + 1) 64 - (2 c'x + 1) w,  dyn = (2 y + 1) 64 - (2 c'y + 1) h
+ * (the squared distance of the pixel's centre and the cell's in cells, over a common denominator), ties to the first in raster order, and
+ * no object when the window holds none.  The pixel's colour is that of track ids[f][l - 1] of its object l, (r, g, b) without an object or
+ * a track; tint and outline are cgs_overlay_compose's formulas with this colour.
+ * Box and number of object l (area > 0, ids[f][l - 1] = t > 0), only with B > 0: cell c of an axis of length L holds the pixels
+ * (c L + 31) / 64 .. ((c + 1) L + 31) / 64 - 1 (those whose home cell it is); the rectangle runs from the first pixel of cell x0 to the last
+ * of x1, and so in y.  Border: the pixels of the rectangle fewer than B pixels from one of its four sides, colour(t), opaque.  Plate: with
+ * s = max(1, min(h, w) / 256) and d the number of decimal digits of t, the s (6 d + 1) x 9 s pixels from the rectangle's top left corner,
+ * clipped by the frame and not by the rectangle; digit j (the most significant first) has its glyph's origin at (X0 + s (1 + 6 j), Y0 + s),
+ * glyph pixel ((x - ox) / s, (y - oy) / s) of 5 x 7 is black where the font's bit is set, the rest of the plate is colour(t), opaque.
+ * Priority at a pixel: a plate (the smallest label first), a border (the smallest label first), the outline, the tint.
+ * The search runs only where its answer shows (grey != 0 or an outline pixel).  No read or write is out of range for any int32 content
+ * of labels, ids and table.
+ * guide, grey, labels, ids, table, font, out not NULL, labels / ids / table 4-byte aligned, 1 <= n <= 65535, h, w >= 1, max_objects >= 1,
+ * colour, alpha256, thickness, boxes, layout in range, no unknown flag, else CGS_ERR_BADARG (nothing is launched); then 64 <= h, w <=
+ * CGS_FIT_MAX_SIDE and max_objects <= CGS_OVERLAY_MAX_TRACK_OBJECTS, else CGS_ERR_UNSUPPORTED.                                          */
+enum { CGS_OVERLAY_MAX_TRACK_OBJECTS = 64, CGS_OVERLAY_MAX_BOXES = 4, CGS_OVERLAY_FONT_GLYPHS = 10, CGS_OVERLAY_FONT_ROWS = 7 };
+int cgs_overlay_compose_tracks(const uint8_t* guide, const uint8_t* grey, const uint8_t* hard, const int32_t* labels, const int32_t* ids,
+                               const int32_t* table, const uint8_t* font, int32_t n, int32_t h, int32_t w, int32_t max_objects, int32_t r,
+                               int32_t g, int32_t b, int32_t alpha256, int32_t thickness, int32_t boxes, int32_t layout, int32_t flags,
+                               uint8_t* out, cgs_stream_t stream);
+
 /* ---- block-matched motion for the temporal filter (csrc/temporal_motion.hip; -process --source-video --smooth R --smooth-motion S) -------
  * cgs_temporal_smooth looks, for a tap in frame f + k, at the 3 x 3 cells around the cell's own position whatever k is; under a camera pan
  * of a few cells a frame those taps leave the object and the range term switches them off.  These two entries estimate the motion of
