@@ -25,7 +25,7 @@
 // 500 operations per lane, the rest is small.
 // LDS: 2 x 16 KiB (g2 / d2 of both sides) + 2 x 66 + 2 x 64 rows of 8 bytes = 34 KiB, four workgroups (16 waves) per CU: LDS, not the
 // 32-wave limit, bounds occupancy.
-#include "cgs_common.h"
+#include "pixel_common.h"
 
 namespace {
 
@@ -35,12 +35,6 @@ constexpr int BD_SIDE = CGS_OBJ_MAX_SIDE;             // a row is one wave-wide 
 constexpr int BD_NONE = 1 << 20;                      // "no boundary pixel in this column"; see step 4 above
 static_assert(BD_SIDE == CGS_WAVE && BD_WAVES == 4, "one lane per column; step 3 splits (side, half) over four waves");
 static_assert(BD_NONE > 2 * (BD_SIDE - 1) * (BD_SIDE - 1) && BD_NONE > CGS_BOUNDARY_MAX_TOL_PX * CGS_BOUNDARY_MAX_TOL_PX, "BD_NONE");
-
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, CGS_WAVE));
-    return v;
-}
 
 __global__ void __launch_bounds__(BD_THREADS)
 boundary_kernel(const void* __restrict__ pred, int kind, float thresh, const uint8_t* __restrict__ truth, int h, int w,
@@ -138,8 +132,8 @@ boundary_kernel(const void* __restrict__ pred, int kind, float thresh, const uin
             if ((bp >> x) & 1ull) far_p = max(far_p, s_d[1][y][x]);             // from a predicted boundary pixel to the truth's
             if ((bt >> x) & 1ull) far_t = max(far_t, s_d[0][y][x]);
         }
-        far_p = wave_max_i(far_p);
-        far_t = wave_max_i(far_t);
+        far_p = px_wave_max(far_p);
+        far_t = px_wave_max(far_t);
         if (x == 0) {
             const bool both = n_p > 0 && n_t > 0;
             cnt[0] = n_p;

@@ -27,7 +27,7 @@
 // The tap of d2_min has the weight exp2(-(ey + ex)) >= exp(-6.25 / sigma_s^2), so den > 0 for sigma_s >= 0.5, which the entry enforces.
 // No atomics; soft = num / den is the IEEE division.  About 12 VALU operations and one exponential per tap against 3 bytes read and 4 to
 // 6 written per pixel: bound by instruction issue, not by HBM.
-#include "cgs_common.h"
+#include "pixel_common.h"
 
 namespace {
 
@@ -107,14 +107,6 @@ fit_down_kernel(const uint8_t* __restrict__ frames, int H, int W, uint8_t* __res
     }
 }
 
-__device__ __forceinline__ uint32_t fit_dot3(uint32_t a, uint32_t b) {      // a.b over the three colour bytes (the fourth is 0)
-#if __has_builtin(__builtin_amdgcn_udot4)
-    return __builtin_amdgcn_udot4(a, b, 0u, false);
-#else
-    return (a & 255u) * (b & 255u) + ((a >> 8) & 255u) * ((b >> 8) & 255u) + ((a >> 16) & 255u) * ((b >> 16) & 255u);
-#endif
-}
-
 __global__ void __launch_bounds__(FIT_THREADS)
 fit_up_kernel(const void* __restrict__ map, int map_kind, const uint8_t* __restrict__ guide, const uint8_t* __restrict__ low, int H, int W,
               float cs, float cr, float inv2h, float inv2w, float thresh, int inclusive, float* __restrict__ soft,
@@ -168,7 +160,7 @@ fit_up_kernel(const void* __restrict__ map, int map_kind, const uint8_t* __restr
     for (int y = ylo; y < yhi; ++y) {
         const int64_t p = ((int64_t)f * H + y) * W + x;
         const uint32_t g = (uint32_t)guide[3 * p] | ((uint32_t)guide[3 * p + 1] << 8) | ((uint32_t)guide[3 * p + 2] << 16);
-        const uint32_t gg = fit_dot3(g, g);
+        const uint32_t gg = px_dot3(g, g);
         float ey[FIT_TAPS];
 #pragma unroll
         for (int dy = 0; dy < FIT_TAPS; ++dy) {
@@ -181,7 +173,7 @@ fit_up_kernel(const void* __restrict__ map, int map_kind, const uint8_t* __restr
         for (int dy = 0; dy < FIT_TAPS; ++dy)
 #pragma unroll
             for (int dx = 0; dx < FIT_TAPS; ++dx) {
-                d2[dy][dx] = gg + ll[dy][dx] - 2u * fit_dot3(g, lw[dy][dx]);
+                d2[dy][dx] = gg + ll[dy][dx] - 2u * px_dot3(g, lw[dy][dx]);
                 dmin = min(dmin, d2[dy][dx]);
             }
         float num = 0.0f, den = 0.0f;

@@ -20,7 +20,7 @@
 // and would make "ties go to the smallest number" a second comparison.
 //
 // LDS: 64 x 65 + 2 x 64 + 8 words = 16.8 KiB, so the 32-wave limit (eight workgroups per CU), not LDS, bounds occupancy.
-#include "cgs_common.h"
+#include "pixel_common.h"
 
 namespace {
 
@@ -31,12 +31,6 @@ constexpr int OM_MAX_K = CGS_OBJ_MATCH_MAX_OBJECTS;   // a lane is an object in 
 constexpr int OM_STRIDE = OM_MAX_K + 1;               // see "Bank conflicts" above
 constexpr int OM_CELLS = OM_MAX_K * OM_STRIDE;        // 4160, a multiple of 4
 static_assert(OM_MAX_K == CGS_WAVE && OM_MAX_SIDE == CGS_WAVE && OM_CELLS % 4 == 0, "one lane per column and per object");
-
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, CGS_WAVE));
-    return v;
-}
 
 __global__ void __launch_bounds__(OM_THREADS)
 objects_match_kernel(const int32_t* __restrict__ pred, const int32_t* __restrict__ truth, int h, int w, int K,
@@ -79,8 +73,8 @@ objects_match_kernel(const int32_t* __restrict__ pred, const int32_t* __restrict
             if (pc && tc) atomicAdd(&s_I[(pc - 1) * OM_STRIDE + tc - 1], len);
         }
     }
-    pmax = wave_max(pmax);
-    tmax = wave_max(tmax);
+    pmax = px_wave_max(pmax);
+    tmax = px_wave_max(tmax);
     if (x == 0) {
         s_max[wave][0] = pmax;
         s_max[wave][1] = tmax;

@@ -18,7 +18,7 @@
 //
 // Launches: init, match (n > 1), self-match, link, R x resolve, number, heads, table, paint: 7 + R + (n > 1), a function of n alone
 // (paint is launched also when both its outputs are NULL and then returns at once).
-#include "cgs_common.h"
+#include "pixel_common.h"
 
 namespace {
 
@@ -45,12 +45,6 @@ __host__ __device__ inline Layout layout(int64_t n, int64_t K) {
     o.base = o.heads + 2 * n;
     o.words = o.base + n;
     return o;
-}
-
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, CGS_WAVE));
-    return v;
 }
 
 __global__ void __launch_bounds__(OT_THREADS)
@@ -172,7 +166,7 @@ track_table_kernel(const int32_t* __restrict__ best, const int32_t* __restrict__
         }
     }
     if (in) track[(int64_t)f * K + lane] = t;
-    len = wave_max_i(len);
+    len = px_wave_max(len);
     if (lane == 0) s_len[wave] = len;
     __syncthreads();
     if (threadIdx.x == 0) {

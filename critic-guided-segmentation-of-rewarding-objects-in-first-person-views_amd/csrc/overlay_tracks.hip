@@ -1,6 +1,7 @@
 // The overlay video of -process --source-video --overlay-tracks (include/cgs_hip.h): cgs_overlay_compose_tracks is cgs_overlay_compose
 // with a colour per tracked object in place of the one tint, and with every object's bounding box and track number drawn on the overlay
-// panel, all in integers.  The left panel, the grey panel, the tint formula and the outline are those of csrc/overlay.hip.
+// panel, all in integers.  The left panel, the grey panel, the tint formula and the outline are those of csrc/overlay.hip: both kernels
+// are built from csrc/overlay_body.h, and what is here is what the tracked overlay stages and step 3 with its colour per pixel.
 //
 //   colour    of track t >= 1: c_k = 64 + ((t 2654435761 mod 2^32) >> 8 k & 255) 191 / 255, track_paint_kernel's (csrc/objects_track.hip);
 //             of no track: the caller's colour.
@@ -12,7 +13,7 @@
 //             left corner carries the d digits of the track number, 5 x 7 glyphs of the caller's font scaled by s = max(1, min(H, W) / 256).
 //   priority  plate (smallest label first), border (smallest label first), outline, tint.
 //
-// A workgroup takes a band of OV_BAND rows of one frame, as in csrc/overlay.hip, and stages besides the bit rows of the outline:
+// A workgroup takes a band of OV_BAND rows of one frame (csrc/overlay_body.h) and stages besides the bit rows of the outline:
 //   cells     the label rows of the band's cells and 2 rows above and below, a byte a cell (0: none, 255: above K), with 2 zero columns
 //             each side: a cell outside the grid and an unlabelled cell read the same, so the search has no bounds to check.  A second
 //             pass marks the unlabelled cells of the band's own rows that have a labelled cell among their 5 x 5 with 254: only their
@@ -25,23 +26,16 @@
 // distances are sums of a per-column and a per-row term, each one 32 x 32 -> 64 bit product.  A home cell ((2 p + 1) 32) / L is one
 // multiply-high by ceil(2^32 / L): exact for L <= 4096, where (2 p + 1) 32 < 2^18 and the multiplier's error L' < L gives a 2^18 L' < 2^32.
 // 40 KB of LDS, four workgroups a compute unit as csrc/overlay.hip.
-#include "cgs_common.h"
+#include "overlay_body.h"
 
 namespace {
 
-constexpr int OV_THREADS = 256;
-constexpr int OV_BAND = 16;                                               // rows of a band
-constexpr int OV_ROWS = OV_BAND + 2 * CGS_OVERLAY_MAX_OUTLINE;            // staged bit rows at the thickest outline
-constexpr int OV_WORDS = CGS_FIT_MAX_SIDE / 64;                           // 64-bit words of the longest row
-constexpr uint32_t OV_DEN = 65280u, OV_HALF = 32640u;
 constexpr int OT_SIDE = CGS_FIT_SIDE, OT_R = CGS_FIT_RADIUS;              // the 64-cell grid and the search radius
 constexpr int OT_CELL_ROWS = OV_BAND + 2 * OT_R;                          // H >= 64: a band of 16 rows lies in at most 16 cell rows
 constexpr int OT_CELL_COLS = OT_SIDE + 2 * OT_R;
 constexpr int OT_K = CGS_OVERLAY_MAX_TRACK_OBJECTS;
 constexpr uint8_t OT_ABOVE = 255;                                         // a label above K
 constexpr uint8_t OT_NEAR = 254;                                          // unlabelled, with a labelled cell among the 5 x 5 around it
-
-typedef uint32_t ov_u32x4 __attribute__((ext_vector_type(4)));
 
 struct OtBox {                                                            // in pixels, inclusive; all below 4096 + 16 * 61
     int16_t x0, y0, x1, y1;                                               // the rectangle
@@ -52,59 +46,13 @@ struct OtBox {                                                            // in 
 };
 
 struct OtShared {
-    unsigned long long hard[OV_ROWS][OV_WORDS];                           // E_0
-    unsigned long long e[2][OV_ROWS][OV_WORDS];                           // E_i, E_{i+1}
+    OvOutline outline;
     uint8_t cell[OT_CELL_ROWS][OT_CELL_COLS];
     uint32_t colour[OT_K + 1];
     OtBox box[OT_K];
     int nbox;
     uint8_t font[CGS_OVERLAY_FONT_GLYPHS * CGS_OVERLAY_FONT_ROWS];
 };
-
-template <bool NT, typename T>
-__device__ __forceinline__ void ov_put(T* p, const T& v) {
-    if (NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
-
-template <int PX>
-__device__ __forceinline__ void ov_load_rgb(const uint8_t* p, uint32_t* w) {
-    if constexpr (PX == 16) {
-        const ov_u32x4* q = reinterpret_cast<const ov_u32x4*>(p);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const ov_u32x4 v = q[i];
-            w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-        }
-    } else {
-        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) w[i] = q[i];
-    }
-}
-
-template <int PX, bool NT>
-__device__ __forceinline__ void ov_store_rgb(uint8_t* p, const uint32_t* w) {
-    if constexpr (PX == 16) {
-        ov_u32x4* q = reinterpret_cast<ov_u32x4*>(p);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            ov_u32x4 v;
-            v.x = w[4 * i]; v.y = w[4 * i + 1]; v.z = w[4 * i + 2]; v.w = w[4 * i + 3];
-            ov_put<NT>(q + i, v);
-        }
-    } else {
-        uint32_t* q = reinterpret_cast<uint32_t*>(p);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) ov_put<NT>(q + i, w[i]);
-    }
-}
-
-__device__ __forceinline__ uint32_t ov_tint(uint32_t fr, uint32_t tint, uint32_t q) {
-    return (fr * (OV_DEN - q) + tint * q + OV_HALF) / OV_DEN;
-}
 
 __device__ __forceinline__ uint32_t ot_track_colour(uint32_t t) {         // t >= 1; r | g << 8 | b << 16
     const uint32_t hsh = t * 2654435761u;
@@ -190,9 +138,7 @@ overlay_tracks_kernel(const uint8_t* __restrict__ guide, const uint8_t* __restri
     __shared__ OtShared sh;
     const int t = threadIdx.x, f = blockIdx.y, y0 = (int)blockIdx.x * OV_BAND;
     const int rows = min(OV_BAND, H - y0);
-    const int nwords = (W + 63) >> 6;
     const bool outline = hard != nullptr && thick > 0;                    // (the same in every thread)
-    const int last = thick & 1;                                           // the buffer that holds E_t
     const int s = max(1, min(H, W) >> 8);                                 // the scale of plate and digits
     const uint32_t inv_h = (uint32_t)((0xFFFFFFFFull + (uint32_t)H) / (uint32_t)H);      // ceil(2^32 / H)
     const uint32_t inv_w = (uint32_t)((0xFFFFFFFFull + (uint32_t)W) / (uint32_t)W);
@@ -270,46 +216,14 @@ overlay_tracks_kernel(const uint8_t* __restrict__ guide, const uint8_t* __restri
         if (any) sh.cell[lr][lc] = OT_NEAR;
     }
 
-    if (outline) {
-        const int R = rows + 2 * thick, lane = t & 63, wave = t >> 6;
-        const uint8_t* hf = hard + (int64_t)f * H * W;
-        for (int item = wave; item < R * nwords; item += OV_THREADS / 64) {      // (the same in every lane of a wave)
-            const int lr = item / nwords, j = item - lr * nwords;
-            const int y = y0 - thick + lr, x = 64 * j + lane;
-            const bool in = y >= 0 && y < H && x < W;
-            const bool on = in ? hf[(int64_t)y * W + x] != 0 : true;
-            const unsigned long long word = __ballot(on);
-            if (lane == 0) {
-                sh.hard[lr][j] = word;
-                sh.e[0][lr][j] = word;
-            }
-        }
+    // every path reaches a barrier between the pass above and the streaming below: ov_outline ends on one
+    if (outline)
+        ov_outline(sh.outline, hard, f, y0, rows, H, W, thick);
+    else
         __syncthreads();
-        const unsigned long long past = (W & 63) ? ~0ull << (W & 63) : 0ull;      // the bits past column W in the last word: they stay on
-        for (int i = 0; i < thick; ++i) {
-            const int src = i & 1, dst = src ^ 1;
-            for (int item = t; item < R * nwords; item += OV_THREADS) {
-                const int lr = item / nwords, j = item - lr * nwords;
-                const int y = y0 - thick + lr;
-                unsigned long long e = ~0ull;
-                if (y >= 0 && y < H) {
-                    const unsigned long long c = sh.e[src][lr][j];
-                    const unsigned long long up = lr > 0 ? sh.e[src][lr - 1][j] : ~0ull;
-                    const unsigned long long dn = lr + 1 < R ? sh.e[src][lr + 1][j] : ~0ull;
-                    const unsigned long long lo = j > 0 ? sh.e[src][lr][j - 1] >> 63 : 1ull;              // the pixel left of bit 0
-                    const unsigned long long hi = j + 1 < nwords ? sh.e[src][lr][j + 1] << 63 : 1ull << 63; // the pixel right of bit 63
-                    e = c & up & dn & ((c << 1) | lo) & ((c >> 1) | hi);
-                    if (j + 1 == nwords) e |= past;
-                }
-                sh.e[dst][lr][j] = e;
-            }
-            __syncthreads();
-        }
-    } else {
-        __syncthreads();
-    }
 
-    const int groups = W / PX;                                            // PX divides W (the entry chose it so)
+    const int last = thick & 1;                                           // the buffer that holds E_t
+    const int groups = W / PX;                                            // PX divides W (ov_dispatch chose it so)
     const int nbox = sh.nbox;
     const int64_t frame_px = (int64_t)f * H * W;
     const int64_t out_row = (int64_t)3 * panels * W;
@@ -321,7 +235,7 @@ overlay_tracks_kernel(const uint8_t* __restrict__ guide, const uint8_t* __restri
         uint32_t ol = 0u;                                                 // bit i: pixel x + i is on the outline
         if (outline) {
             const int lr = ry + thick, j = x >> 6, sh_ = x & 63;          // PX divides 64: the PX bits lie in one word
-            ol = (uint32_t)((sh.hard[lr][j] & ~sh.e[last][lr][j]) >> sh_);
+            ol = (uint32_t)((sh.outline.hard[lr][j] & ~sh.outline.e[last][lr][j]) >> sh_);
         }
         const int cy = ot_home(y, inv_h), lr = cy - c_lo;
         unsigned long long hits = 0ull;                                   // the boxes that touch these PX pixels
@@ -350,13 +264,13 @@ overlay_tracks_kernel(const uint8_t* __restrict__ guide, const uint8_t* __restri
             const uint32_t v = pixel(0, r, gg, b, g, ol & 1u);
             uint8_t* at = dst;
             if (panels > 1) {
-                ov_put<NT>(at, (uint8_t)r); ov_put<NT>(at + 1, (uint8_t)gg); ov_put<NT>(at + 2, (uint8_t)b);
+                px_put<NT>(at, (uint8_t)r); px_put<NT>(at + 1, (uint8_t)gg); px_put<NT>(at + 2, (uint8_t)b);
                 at += 3 * W;
             }
-            ov_put<NT>(at, (uint8_t)v); ov_put<NT>(at + 1, (uint8_t)(v >> 8)); ov_put<NT>(at + 2, (uint8_t)(v >> 16));
+            px_put<NT>(at, (uint8_t)v); px_put<NT>(at + 1, (uint8_t)(v >> 8)); px_put<NT>(at + 2, (uint8_t)(v >> 16));
             if (panels > 2) {
                 at += 3 * W;
-                ov_put<NT>(at, (uint8_t)g); ov_put<NT>(at + 1, (uint8_t)g); ov_put<NT>(at + 2, (uint8_t)g);
+                px_put<NT>(at, (uint8_t)g); px_put<NT>(at + 1, (uint8_t)g); px_put<NT>(at + 2, (uint8_t)g);
             }
         } else {
             constexpr int NW = 3 * PX / 4;
@@ -398,46 +312,22 @@ overlay_tracks_kernel(const uint8_t* __restrict__ guide, const uint8_t* __restri
     }
 }
 
-template <int PX>
-void overlay_tracks_launch(bool nt, dim3 grid, hipStream_t s, const uint8_t* guide, const uint8_t* grey, const uint8_t* hard,
-                           const int32_t* labels, const int32_t* ids, const int32_t* table, const uint8_t* font, int h, int w, int K,
-                           uint32_t tint, uint32_t alpha256, int thick, int boxes, int panels, uint8_t* out) {
-    if (nt)
-        hipLaunchKernelGGL((overlay_tracks_kernel<PX, true>), grid, dim3(OV_THREADS), 0, s, guide, grey, hard, labels, ids, table, font, h, w,
-                           K, tint, alpha256, thick, boxes, panels, out);
-    else
-        hipLaunchKernelGGL((overlay_tracks_kernel<PX, false>), grid, dim3(OV_THREADS), 0, s, guide, grey, hard, labels, ids, table, font, h, w,
-                           K, tint, alpha256, thick, boxes, panels, out);
-}
-
 }  // namespace
 
 extern "C" int cgs_overlay_compose_tracks(const uint8_t* guide, const uint8_t* grey, const uint8_t* hard, const int32_t* labels,
                                           const int32_t* ids, const int32_t* table, const uint8_t* font, int32_t n, int32_t h, int32_t w,
                                           int32_t max_objects, int32_t r, int32_t g, int32_t b, int32_t alpha256, int32_t thickness,
                                           int32_t boxes, int32_t layout, int32_t flags, uint8_t* out, cgs_stream_t stream_) {
-    if (!guide || !grey || !labels || !ids || !table || !font || !out || n < 1 || n > 65535 || h < 1 || w < 1 || max_objects < 1 || r < 0 ||
-        r > 255 || g < 0 || g > 255 || b < 0 || b > 255 || alpha256 < 0 || alpha256 > 256 || thickness < 0 ||
-        thickness > CGS_OVERLAY_MAX_OUTLINE || boxes < 0 || boxes > CGS_OVERLAY_MAX_BOXES || layout < CGS_OVERLAY_ONLY ||
-        layout > CGS_OVERLAY_TRIPLE || (flags & ~CGS_OVERLAY_NONTEMPORAL) ||
-        (((uintptr_t)labels | (uintptr_t)ids | (uintptr_t)table) & 3u))
-        return CGS_ERR_BADARG;
-    if (h < CGS_FIT_SIDE || w < CGS_FIT_SIDE || h > CGS_FIT_MAX_SIDE || w > CGS_FIT_MAX_SIDE || max_objects > OT_K) return CGS_ERR_UNSUPPORTED;
-    const uint32_t tint = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
-    const dim3 grid((unsigned)((h + OV_BAND - 1) / OV_BAND), (unsigned)n);
-    const bool nt = flags & CGS_OVERLAY_NONTEMPORAL;
-    hipStream_t s = (hipStream_t)stream_;
-    // every row of guide and out starts at a multiple of 3 w from the base, every panel 3 w further, every row of grey at a multiple of w
-    const uintptr_t a = (uintptr_t)guide | (uintptr_t)grey | (uintptr_t)out | (uintptr_t)w;
-    if (!(a & 15u))
-        overlay_tracks_launch<16>(nt, grid, s, guide, grey, hard, labels, ids, table, font, h, w, max_objects, tint, (uint32_t)alpha256,
-                                  thickness, boxes, layout, out);
-    else if (!(a & 3u))
-        overlay_tracks_launch<4>(nt, grid, s, guide, grey, hard, labels, ids, table, font, h, w, max_objects, tint, (uint32_t)alpha256,
-                                 thickness, boxes, layout, out);
-    else
-        overlay_tracks_launch<1>(nt, grid, s, guide, grey, hard, labels, ids, table, font, h, w, max_objects, tint, (uint32_t)alpha256,
-                                 thickness, boxes, layout, out);
+    const bool bad = !labels || !ids || !table || !font || max_objects < 1 || boxes < 0 || boxes > CGS_OVERLAY_MAX_BOXES ||
+                     (((uintptr_t)labels | (uintptr_t)ids | (uintptr_t)table) & 3u);
+    OvLaunch l;
+    if (const int rc = ov_prepare(guide, grey, out, n, h, w, r, g, b, alpha256, thickness, layout, flags, bad, &l)) return rc;
+    if (max_objects > OT_K) return CGS_ERR_UNSUPPORTED;
+    ov_dispatch(guide, grey, out, w, flags, [&](auto px, auto nt) {
+        hipLaunchKernelGGL((overlay_tracks_kernel<decltype(px)::value, decltype(nt)::value>), l.grid, dim3(OV_THREADS), 0, (hipStream_t)stream_,
+                           guide, grey, hard, labels, ids, table, font, (int)h, (int)w, (int)max_objects, l.tint, (uint32_t)alpha256,
+                           (int)thickness, (int)boxes, (int)layout, out);
+    });
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
 }

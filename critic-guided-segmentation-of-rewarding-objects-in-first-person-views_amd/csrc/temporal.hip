@@ -18,7 +18,7 @@
 // colour 0 and z 0; a tap on the apron gets the exponent +inf from its row or column term, so its weight is exp2(-inf) = +0 exactly and it
 // adds +0 to both sums: skipped, not clamped, without a bounds test on the reads.  A frame is 28 KB (12 KB of colour, 16 KB of z) and is
 // read by 2 radius + 1 workgroups that run at about the same time, so the repeats come out of L2.  No atomics, no allocation.
-#include "cgs_common.h"
+#include "temporal_body.h"
 
 namespace {
 
@@ -27,18 +27,6 @@ constexpr int TS_SIDE = 64;
 constexpr int TS_CELLS = TS_SIDE * TS_SIDE / TS_THREADS;      // 16 cells a thread
 constexpr int TS_PITCH = TS_SIDE + 2;                         // a plane with its apron
 static_assert(CGS_TEMPORAL_SIDE == TS_SIDE && TS_THREADS == 4 * TS_SIDE, "temporal layout");
-
-__device__ __forceinline__ uint32_t ts_dot3(uint32_t a, uint32_t b) {       // a.b over the three colour bytes (the fourth is 0)
-#if __has_builtin(__builtin_amdgcn_udot4)
-    return __builtin_amdgcn_udot4(a, b, 0u, false);
-#else
-    return (a & 255u) * (b & 255u) + ((a >> 8) & 255u) * ((b >> 8) & 255u) + ((a >> 16) & 255u) * ((b >> 16) & 255u);
-#endif
-}
-
-__device__ __forceinline__ uint32_t ts_colour(const uint8_t* __restrict__ low, int64_t cell) {
-    return (uint32_t)low[3 * cell] | ((uint32_t)low[3 * cell + 1] << 8) | ((uint32_t)low[3 * cell + 2] << 16);
-}
 
 __global__ void __launch_bounds__(TS_THREADS)
 temporal_smooth_kernel(const float* __restrict__ z, const uint8_t* __restrict__ low, int n, int f0, int radius, float cr, float ct, float cs,
@@ -60,8 +48,8 @@ temporal_smooth_kernel(const float* __restrict__ z, const uint8_t* __restrict__ 
 #pragma unroll
     for (int j = 0; j < TS_CELLS; ++j) {
         const int64_t cell = ((int64_t)f * TS_SIDE + (row0 + 4 * j)) * TS_SIDE + col;
-        c0[j] = ts_colour(low, cell);
-        cc[j] = ts_dot3(c0[j], c0[j]);
+        c0[j] = px_colour(low, cell);
+        cc[j] = px_dot3(c0[j], c0[j]);
         num[j] = z[cell];
         den[j] = 1.0f;
     }
@@ -81,11 +69,11 @@ temporal_smooth_kernel(const float* __restrict__ z, const uint8_t* __restrict__ 
         for (int j = 0; j < TS_CELLS; ++j) {
             const int r = row0 + 4 * j;
             const int64_t cell = ((int64_t)g * TS_SIDE + r) * TS_SIDE + col;
-            s_c[(r + 1) * TS_PITCH + col + 1] = ts_colour(low, cell);
+            s_c[(r + 1) * TS_PITCH + col + 1] = px_colour(low, cell);
             s_z[(r + 1) * TS_PITCH + col + 1] = z[cell];
         }
         __syncthreads();
-        const float kt = (float)(k * k) * ct;
+        const float kk = (float)(k * k);
 #pragma unroll
         for (int j = 0; j < TS_CELLS; ++j) {
             const int r = row0 + 4 * j;
@@ -96,12 +84,7 @@ temporal_smooth_kernel(const float* __restrict__ z, const uint8_t* __restrict__ 
 #pragma unroll
                 for (int dx = 0; dx < 3; ++dx) {
                     const int at = (r + dy) * TS_PITCH + col + dx;
-                    const uint32_t l = s_c[at];
-                    const uint32_t d2 = cc[j] + ts_dot3(l, l) - 2u * ts_dot3(c0[j], l);
-                    const float arg = fmaf((float)d2, cr, kt + (ey + ex[dx]));
-                    const float w = __builtin_amdgcn_exp2f(-arg);
-                    num[j] = fmaf(w, s_z[at], num[j]);
-                    den[j] += w;
+                    ts_tap(cc[j], c0[j], s_c[at], s_z[at], cr, kk, ct, ey + ex[dx], num[j], den[j]);
                 }
             }
         }
@@ -115,15 +98,10 @@ temporal_smooth_kernel(const float* __restrict__ z, const uint8_t* __restrict__ 
 
 extern "C" int cgs_temporal_smooth(const float* z, const uint8_t* low, int32_t n, int32_t f0, int32_t f1, int32_t radius, float sigma_r,
                                    float* out, cgs_stream_t stream_) {
-    if (!z || !low || !out || n < 1 || f0 < 0 || f1 <= f0 || f1 > n || radius < 1 || !(sigma_r > 0.0f) || sigma_r > 3.0e38f ||
-        ((uintptr_t)z & 3u) || ((uintptr_t)out & 3u))
-        return CGS_ERR_BADARG;
-    if (radius > CGS_TEMPORAL_MAX_RADIUS) return CGS_ERR_UNSUPPORTED;
-    const double log2e = 1.4426950408889634, sigma_t = 0.5 * (double)radius;
-    const float cr = (float)(log2e / (2.0 * (double)sigma_r * (double)sigma_r)), ct = (float)(log2e / (2.0 * sigma_t * sigma_t));
-    const float cs = (float)(log2e / 2.0);
+    TsCoef c;
+    if (const int rc = ts_prepare(z, low, out, n, f0, f1, radius, sigma_r, false, &c)) return rc;
     hipLaunchKernelGGL(temporal_smooth_kernel, dim3((unsigned)(f1 - f0)), dim3(TS_THREADS), 0, (hipStream_t)stream_, z, low, (int)n, (int)f0,
-                       (int)radius, cr, ct, cs, out);
+                       (int)radius, c.cr, c.ct, c.cs, out);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
 }

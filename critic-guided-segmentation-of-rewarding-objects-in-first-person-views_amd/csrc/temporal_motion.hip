@@ -16,14 +16,15 @@
 // cgs_temporal_smooth_mc.  The path of cell p of frame f: m_0 = 0, m_{j+1} = m_j + fwd[f + j][block of clamp(p + m_j)] (bwd[f - j - 1] for
 // k < 0); the taps of frame f + k are the 3 x 3 cells p + m_k + (dy, dx), skipped when outside the grid.  Everything else -- weights, the
 // integer d2 against low[f][p], the spatial term on (dy, dx) alone, the tap order, the two fp32 sums, the exponential, the division -- is
-// temporal_smooth_kernel's, operation for operation, so that an all-zero field gives its output bit for bit.  The tables of the 2 radius
+// temporal_smooth_kernel's: the tap itself is the one function both call (ts_tap, csrc/temporal_body.h), so that an all-zero field gives its
+// output bit for bit.  The tables of the 2 radius
 // frame pairs around f go to LDS (2 KB); a forward path is carried from k to k + 1, a backward path (k runs -radius .. -1) is walked
 // again from p for each k: |k| dependent reads of an 8 x 8 table.  A tap centre can lie anywhere, so every address is bounded: the table
 // is read at the clamped cell, and the centre's row and column are clamped to -2 .. 65 on planes of 70 x 70 with an apron of three cells
 // (colour 0, z 0).  A centre at -2 or beyond has all three of its taps outside the grid either way and a centre inside -1 .. 64 is not
 // moved, so the clamp changes no tap that counts; the taps are then nine fixed offsets from one address, and one on the apron has the
 // exponent +inf and the weight +0 exactly, as in temporal_smooth_kernel.  For any int8 content of the fields |m| <= 8 * 128.
-#include "cgs_common.h"
+#include "temporal_body.h"
 
 namespace {
 
@@ -40,14 +41,6 @@ static_assert(CGS_TEMPORAL_SIDE == TM_SIDE && TM_THREADS == 4 * TM_SIDE && TM_BL
 static_assert(TM_CAND <= 128 && 64 * 765 < (1 << 16), "the key is SAD << 7 | rank");
 static_assert(TM_THREADS == 2 * 2 * TM_BLOCKS * TM_BLOCKS, "two threads per direction and block");
 
-__device__ __forceinline__ uint32_t tm_dot3(uint32_t a, uint32_t b) {       // a.b over the three colour bytes (the fourth is 0)
-#if __has_builtin(__builtin_amdgcn_udot4)
-    return __builtin_amdgcn_udot4(a, b, 0u, false);
-#else
-    return (a & 255u) * (b & 255u) + ((a >> 8) & 255u) * ((b >> 8) & 255u) + ((a >> 16) & 255u) * ((b >> 16) & 255u);
-#endif
-}
-
 __device__ __forceinline__ uint32_t tm_sad3(uint32_t a, uint32_t b, uint32_t acc) {     // acc + sum of |a_c - b_c| over the bytes
 #if __has_builtin(__builtin_amdgcn_sad_u8)
     return __builtin_amdgcn_sad_u8(a, b, acc);
@@ -60,10 +53,6 @@ __device__ __forceinline__ uint32_t tm_sad3(uint32_t a, uint32_t b, uint32_t acc
 #endif
 }
 
-__device__ __forceinline__ uint32_t tm_colour(const uint8_t* __restrict__ low, int64_t cell) {
-    return (uint32_t)low[3 * cell] | ((uint32_t)low[3 * cell + 1] << 8) | ((uint32_t)low[3 * cell + 2] << 16);
-}
-
 __device__ __forceinline__ int tm_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // ---------------------------------------------------------------------------------------------------------------- the block motion
@@ -74,7 +63,7 @@ temporal_flow_kernel(const uint8_t* __restrict__ low, int search, int8_t* __rest
     const int t = threadIdx.x;
     const int64_t g = blockIdx.x;
 
-    for (int i = t; i < 2 * TM_SIDE * TM_SIDE; i += TM_THREADS) s_c[0][i] = tm_colour(low, g * TM_SIDE * TM_SIDE + i);
+    for (int i = t; i < 2 * TM_SIDE * TM_SIDE; i += TM_THREADS) s_c[0][i] = px_colour(low, g * TM_SIDE * TM_SIDE + i);
     if (t < TM_CAND) {
         // the order (dy^2 + dx^2, dy, dx) as one integer; the rank is the number of candidates in front
         auto order = [](int c) {
@@ -160,8 +149,8 @@ temporal_smooth_mc_kernel(const float* __restrict__ z, const uint8_t* __restrict
 #pragma unroll
     for (int j = 0; j < TM_CELLS; ++j) {
         const int64_t cell = ((int64_t)f * TM_SIDE + (row0 + 4 * j)) * TM_SIDE + col;
-        c0[j] = tm_colour(low, cell);
-        cc[j] = tm_dot3(c0[j], c0[j]);
+        c0[j] = px_colour(low, cell);
+        cc[j] = px_dot3(c0[j], c0[j]);
         num[j] = z[cell];
         den[j] = 1.0f;
         fy[j] = 0;
@@ -176,7 +165,7 @@ temporal_smooth_mc_kernel(const float* __restrict__ z, const uint8_t* __restrict
         for (int j = 0; j < TM_CELLS; ++j) {
             const int r = row0 + 4 * j;
             const int64_t cell = ((int64_t)g * TM_SIDE + r) * TM_SIDE + col;
-            s_c[(r + TM_APRON) * TM_PITCH + col + TM_APRON] = tm_colour(low, cell);
+            s_c[(r + TM_APRON) * TM_PITCH + col + TM_APRON] = px_colour(low, cell);
             s_z[(r + TM_APRON) * TM_PITCH + col + TM_APRON] = z[cell];
         }
         __syncthreads();
@@ -207,13 +196,7 @@ temporal_smooth_mc_kernel(const float* __restrict__ z, const uint8_t* __restrict
 #pragma unroll
                 for (int dx = 0; dx < 3; ++dx) {
                     const int at = centre + (dy - 1) * TM_PITCH + dx - 1;
-                    const uint32_t l = s_c[at];
-                    const uint32_t d2 = cc[j] + tm_dot3(l, l) - 2u * tm_dot3(c0[j], l);
-                    // temporal_smooth_kernel's k^2 ct + (ey + ex) is compiled to one fused multiply-add; written out here so that it is
-                    const float arg = fmaf((float)d2, cr, fmaf(kk, ct, ey[dy] + ex[dx]));
-                    const float w = __builtin_amdgcn_exp2f(-arg);
-                    num[j] = fmaf(w, s_z[at], num[j]);
-                    den[j] += w;
+                    ts_tap(cc[j], c0[j], s_c[at], s_z[at], cr, kk, ct, ey[dy] + ex[dx], num[j], den[j]);
                 }
             }
         }
@@ -235,15 +218,10 @@ extern "C" int cgs_temporal_flow(const uint8_t* low, int32_t n, int32_t search, 
 
 extern "C" int cgs_temporal_smooth_mc(const float* z, const uint8_t* low, const int8_t* fwd, const int8_t* bwd, int32_t n, int32_t f0,
                                       int32_t f1, int32_t radius, float sigma_r, float* out, cgs_stream_t stream_) {
-    if (!z || !low || !out || n < 1 || f0 < 0 || f1 <= f0 || f1 > n || radius < 1 || !(sigma_r > 0.0f) || sigma_r > 3.0e38f ||
-        ((uintptr_t)z & 3u) || ((uintptr_t)out & 3u) || (n > 1 && (!fwd || !bwd)))
-        return CGS_ERR_BADARG;
-    if (radius > CGS_TEMPORAL_MAX_RADIUS) return CGS_ERR_UNSUPPORTED;
-    const double log2e = 1.4426950408889634, sigma_t = 0.5 * (double)radius;
-    const float cr = (float)(log2e / (2.0 * (double)sigma_r * (double)sigma_r)), ct = (float)(log2e / (2.0 * sigma_t * sigma_t));
-    const float cs = (float)(log2e / 2.0);
+    TsCoef c;
+    if (const int rc = ts_prepare(z, low, out, n, f0, f1, radius, sigma_r, n > 1 && (!fwd || !bwd), &c)) return rc;
     hipLaunchKernelGGL(temporal_smooth_mc_kernel, dim3((unsigned)(f1 - f0)), dim3(TM_THREADS), 0, (hipStream_t)stream_, z, low, fwd, bwd,
-                       (int)n, (int)f0, (int)radius, cr, ct, cs, out);
+                       (int)n, (int)f0, (int)radius, c.cr, c.ct, c.cs, out);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
 }

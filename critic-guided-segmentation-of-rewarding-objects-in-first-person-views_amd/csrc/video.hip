@@ -8,7 +8,7 @@
 // row, which stays in L2) or one SOURCE row of a cell row: its lanes build each 16-byte piece once and store it to the three output
 // rows it is repeated on.  Lane j owns 16-byte piece j of the output row, so every store instruction of a wave covers 1 KB contiguous.
 // The kernel is write-bound: the source reads (3 pixels per lane, at most 8 B each) are about a tenth of the bytes written.
-#include "cgs_common.h"
+#include "pixel_common.h"
 
 namespace {
 
@@ -73,14 +73,6 @@ __device__ __forceinline__ u32x4 piece(uint32_t c0, uint32_t c1, uint32_t c2, in
 }
 
 template <bool NT>
-__device__ __forceinline__ void put(u32x4* p, const u32x4& v) {
-    if (NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
-
-template <bool NT>
 __global__ void video_compose_kernel(VideoCells cells, int cols, int cell_rows, int f0, int h_top, int h_bottom, const u32x4* __restrict__ top,
                                      const u32x4* __restrict__ bottom, u32x4* __restrict__ out) {
     const int rp = cols * VCELL_PIECES;                          // pieces per output row
@@ -88,14 +80,14 @@ __global__ void video_compose_kernel(VideoCells cells, int cols, int cell_rows, 
     const int unit = blockIdx.x;
     u32x4* frame = out + (size_t)blockIdx.y * H * rp;
     if (unit < h_top) {
-        for (int j = threadIdx.x; j < rp; j += blockDim.x) put<NT>(frame + (size_t)unit * rp + j, top[(size_t)unit * rp + j]);
+        for (int j = threadIdx.x; j < rp; j += blockDim.x) px_put<NT>(frame + (size_t)unit * rp + j, top[(size_t)unit * rp + j]);
         return;
     }
     const int u = unit - h_top;
     if (u >= cell_rows * VTILE) {
         const int b = u - cell_rows * VTILE;
         u32x4* dst = frame + (size_t)(h_top + cell_rows * VTILE * VSCALE + b) * rp;
-        for (int j = threadIdx.x; j < rp; j += blockDim.x) put<NT>(dst + j, bottom[(size_t)b * rp + j]);
+        for (int j = threadIdx.x; j < rp; j += blockDim.x) px_put<NT>(dst + j, bottom[(size_t)b * rp + j]);
         return;
     }
     const int cr = u / VTILE, sy = u % VTILE;
@@ -110,9 +102,9 @@ __global__ void video_compose_kernel(VideoCells cells, int cols, int cell_rows, 
         const uint32_t c1 = cell_pixel(d, row_pix + p0 + 1);
         const uint32_t c2 = p0 + 2 < VTILE ? cell_pixel(d, row_pix + p0 + 2) : 0u;    // (the last piece of a cell needs two pixels)
         const u32x4 v = piece(c0, c1, c2, b - 9 * p0);
-        put<NT>(dst + j, v);
-        put<NT>(dst + rp + j, v);
-        put<NT>(dst + 2 * rp + j, v);
+        px_put<NT>(dst + j, v);
+        px_put<NT>(dst + rp + j, v);
+        px_put<NT>(dst + 2 * rp + j, v);
     }
 }
 

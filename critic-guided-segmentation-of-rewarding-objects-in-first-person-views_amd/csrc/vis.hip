@@ -10,7 +10,7 @@
 // four output rows that repeat it; where an output row crosses a label cell the lane blends the cell's coverage into its registers
 // first, so every output byte is written exactly once.  The kernel is write-bound: per 64 bytes stored a lane reads two source pixels
 // (6 B, and 8 B of mask in the masked tile) or, in a plot strip, two perm / row entries that stay in L1 / L2.
-#include "cgs_common.h"
+#include "pixel_common.h"
 
 namespace {
 
@@ -24,14 +24,6 @@ constexpr int VIS_THREADS = 256;
 constexpr int VIS_LABELS = 1 + CGS_VIS_VALUES;       // the index label, then one per value row: the order the reference draws them in
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <bool NT>
-__device__ __forceinline__ void put(u32x4* p, const u32x4& v) {
-    if (NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
 
 // dword (4 s + i) of a group: bytes (m, m+1, m+2, m) mod 3 of the channels of one pixel c = R | G << 8 | B << 16, m = (4 s + i) % 3
 __device__ __forceinline__ uint32_t rotated(uint32_t c, int m) {
@@ -151,7 +143,7 @@ vis_compose_kernel(const uint8_t* __restrict__ X, const float* __restrict__ mask
                 for (int l = 0; l < VIS_LABELS; ++l)
                     if (touch[l] && y >= ly[l] && y < ly[l] + CGS_VIS_CELL_H) v = blend(v, cell[l] + (y - ly[l]) * CGS_VIS_CELL_W, lx[l], j);
             }
-            put<NT>(dst + q * VIS_PIECES, v);
+            px_put<NT>(dst + q * VIS_PIECES, v);
         }
     }
 }

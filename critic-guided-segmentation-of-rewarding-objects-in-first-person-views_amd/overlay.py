@@ -89,15 +89,14 @@ def scale(h, w):
     return max(1, min(int(h), int(w)) // 256)
 
 
-def compose(guide, grey, hard=None, color=COLOR, alpha256=128, outline=OUTLINE, layout=LAYOUT, out=None, nontemporal=NONTEMPORAL):
-    """guide: device tensor uint8 [n,H,W,3], the frames, 64 <= H, W <= 4096.  grey: uint8 [n,H,W] (fit.up's grey).  hard: uint8 / bool
-    [n,H,W], zero / non-zero, or None (no outline).  color (r, g, b); alpha256: the opacity as an integer 0..256; outline: thickness 0..4;
-    layout "overlay", "side" or "triple" (k = 1, 2, 3 panels).  Returns uint8 [n,H,k W,3] (`out` when given) on the inputs' device:
-    overlay_c = (frame_c (65280 - q) + color_c q + 32640) // 65280 with q = alpha256 grey, outline pixels the colour itself; "side" puts
-    the frame to its left, "triple" also the grey byte as RGB to its right.  No CPU path: raises CgsError without a GPU."""
+def _prepare(what, guide, grey, hard, color, alpha256, outline, layout, out, more=None):
+    """What ``compose`` and ``compose_tracks`` do before the call: the checks of the arguments both take, the GPU check under the name
+    `what`, contiguous inputs (a bool `hard` viewed as uint8) and `out`.  more(n): the caller's checks of its own tensors, run after those
+    of grey and hard; it returns the tensors that the GPU check names after grey and those it names last.  Returns guide, grey, hard, out,
+    (n, h, w), (r, g, b), outline and k."""
     n, h, w = _frames("guide", guide)
     k = panels(layout)
-    r, g, b = parse_color(color)
+    rgb = parse_color(color)
     outline = check_outline(outline)
     if isinstance(alpha256, bool) or not isinstance(alpha256, (int, np.integer)) or not 0 <= alpha256 <= 256:
         raise ValueError(f"alpha256 = {alpha256!r}: an integer 0..256 (overlay.to_alpha256 maps an opacity to it)")
@@ -107,23 +106,31 @@ def compose(guide, grey, hard=None, color=COLOR, alpha256=128, outline=OUTLINE, 
     if hard is not None and (not isinstance(hard, torch.Tensor) or hard.dtype not in (torch.uint8, torch.bool) or tuple(hard.shape) != (n, h, w)):
         raise ValueError(f"hard must be a uint8 or bool tensor [{n},{h},{w}] or None, got "
                          + (f"{hard.dtype} {tuple(hard.shape)}" if isinstance(hard, torch.Tensor) else type(hard).__name__))
+    own, own_last = more(n) if more is not None else ((), ())
     if n > 65535:
         raise ValueError(f"guide: at most 65535 frames a call, got {n}")
     if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous()
                             or tuple(out.shape) != (n, h, k * w, 3)):
         raise ValueError(f"out must be a contiguous uint8 tensor [{n},{h},{k * w},3]")
-    tensors = (guide, grey) + ((hard,) if hard is not None else ()) + ((out,) if out is not None else ())
-    _need_gpu("overlay.compose (cgs_overlay_compose)", *tensors)
-    if not guide.is_contiguous():
-        guide = guide.contiguous()
-    if not grey.is_contiguous():
-        grey = grey.contiguous()
+    _need_gpu(what, guide, grey, *own, *((hard,) if hard is not None else ()), *((out,) if out is not None else ()), *own_last)
+    guide, grey = guide.contiguous(), grey.contiguous()
     if hard is not None:
         hard = hard.contiguous()
         if hard.dtype == torch.bool:
             hard = hard.view(torch.uint8)
     if out is None:
         out = torch.empty((n, h, k * w, 3), dtype=torch.uint8, device=guide.device)
+    return guide, grey, hard, out, (n, h, w), rgb, outline, k
+
+
+def compose(guide, grey, hard=None, color=COLOR, alpha256=128, outline=OUTLINE, layout=LAYOUT, out=None, nontemporal=NONTEMPORAL):
+    """guide: device tensor uint8 [n,H,W,3], the frames, 64 <= H, W <= 4096.  grey: uint8 [n,H,W] (fit.up's grey).  hard: uint8 / bool
+    [n,H,W], zero / non-zero, or None (no outline).  color (r, g, b); alpha256: the opacity as an integer 0..256; outline: thickness 0..4;
+    layout "overlay", "side" or "triple" (k = 1, 2, 3 panels).  Returns uint8 [n,H,k W,3] (`out` when given) on the inputs' device:
+    overlay_c = (frame_c (65280 - q) + color_c q + 32640) // 65280 with q = alpha256 grey, outline pixels the colour itself; "side" puts
+    the frame to its left, "triple" also the grey byte as RGB to its right.  No CPU path: raises CgsError without a GPU."""
+    guide, grey, hard, out, (n, h, w), (r, g, b), outline, k = _prepare("overlay.compose (cgs_overlay_compose)", guide, grey, hard, color,
+                                                                        alpha256, outline, layout, out)
     with torch.cuda.device(guide.device):
         _lib.call("cgs_overlay_compose", guide.data_ptr(), grey.data_ptr(), hard.data_ptr() if hard is not None else None, n, h, w, r, g, b,
                   int(alpha256), outline, k, _lib.OVERLAY_NONTEMPORAL if nontemporal else 0, out.data_ptr(),
@@ -157,45 +164,26 @@ def compose_tracks(guide, grey, hard, labels, ids, table, font=FONT, color=COLOR
     around it; `color` where there is none.  Every object with a track gets its box on the cells' pixel tiling and, at the box's top left
     corner, a plate with the track number in digits scale(H, W) font pixels big.  Plates lie over borders, borders over the outline.
     Integers throughout (include/cgs_hip.h has every formula).  No CPU path: raises CgsError without a GPU."""
-    n, h, w = _frames("guide", guide)
-    k = panels(layout)
-    r, g, b = parse_color(color)
-    outline, boxes = check_outline(outline), check_boxes(boxes)
-    if isinstance(alpha256, bool) or not isinstance(alpha256, (int, np.integer)) or not 0 <= alpha256 <= 256:
-        raise ValueError(f"alpha256 = {alpha256!r}: an integer 0..256 (overlay.to_alpha256 maps an opacity to it)")
-    if not isinstance(grey, torch.Tensor) or grey.dtype != torch.uint8 or tuple(grey.shape) != (n, h, w):
-        raise ValueError(f"grey must be a uint8 tensor [{n},{h},{w}], got "
-                         + (f"{grey.dtype} {tuple(grey.shape)}" if isinstance(grey, torch.Tensor) else type(grey).__name__))
-    if hard is not None and (not isinstance(hard, torch.Tensor) or hard.dtype not in (torch.uint8, torch.bool) or tuple(hard.shape) != (n, h, w)):
-        raise ValueError(f"hard must be a uint8 or bool tensor [{n},{h},{w}] or None, got "
-                         + (f"{hard.dtype} {tuple(hard.shape)}" if isinstance(hard, torch.Tensor) else type(hard).__name__))
-    for name, t in (("labels", labels), ("ids", ids), ("table", table)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
-            raise ValueError(f"{name} must be an int32 tensor, got " + (str(t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
-    side = _lib.FIT_SIDE
-    if tuple(labels.shape) != (n, side, side):
-        raise ValueError(f"labels must be [{n},{side},{side}] for {n} frames, got {tuple(labels.shape)}")
-    if ids.dim() != 2 or ids.shape[0] != n or not 1 <= ids.shape[1] <= MAX_TRACK_OBJECTS:
-        raise ValueError(f"ids must be [{n},K] with K in 1..{MAX_TRACK_OBJECTS}, got {tuple(ids.shape)}")
+    boxes = check_boxes(boxes)
+
+    def tracked(n):
+        for name, t in (("labels", labels), ("ids", ids), ("table", table)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+                raise ValueError(f"{name} must be an int32 tensor, got " + (str(t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
+        side = _lib.FIT_SIDE
+        if tuple(labels.shape) != (n, side, side):
+            raise ValueError(f"labels must be [{n},{side},{side}] for {n} frames, got {tuple(labels.shape)}")
+        if ids.dim() != 2 or ids.shape[0] != n or not 1 <= ids.shape[1] <= MAX_TRACK_OBJECTS:
+            raise ValueError(f"ids must be [{n},K] with K in 1..{MAX_TRACK_OBJECTS}, got {tuple(ids.shape)}")
+        if tuple(table.shape) != (n, ids.shape[1], _lib.OBJ_FIELDS):
+            raise ValueError(f"table must be [{n},{ids.shape[1]},{_lib.OBJ_FIELDS}] beside ids {tuple(ids.shape)}, got {tuple(table.shape)}")
+        return (labels, ids, table), ((font,) if isinstance(font, torch.Tensor) else ())
+
+    guide, grey, hard, out, (n, h, w), (r, g, b), outline, k = _prepare("overlay.compose_tracks (cgs_overlay_compose_tracks)", guide, grey,
+                                                                        hard, color, alpha256, outline, layout, out, more=tracked)
     K = int(ids.shape[1])
-    if tuple(table.shape) != (n, K, _lib.OBJ_FIELDS):
-        raise ValueError(f"table must be [{n},{K},{_lib.OBJ_FIELDS}] beside ids {tuple(ids.shape)}, got {tuple(table.shape)}")
-    if n > 65535:
-        raise ValueError(f"guide: at most 65535 frames a call, got {n}")
-    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous()
-                            or tuple(out.shape) != (n, h, k * w, 3)):
-        raise ValueError(f"out must be a contiguous uint8 tensor [{n},{h},{k * w},3]")
-    tensors = (guide, grey, labels, ids, table) + ((hard,) if hard is not None else ()) + ((out,) if out is not None else ()) \
-        + ((font,) if isinstance(font, torch.Tensor) else ())
-    _need_gpu("overlay.compose_tracks (cgs_overlay_compose_tracks)", *tensors)
     font = _device_font(font, guide.device)
-    guide, grey, labels, ids, table = (t if t.is_contiguous() else t.contiguous() for t in (guide, grey, labels, ids, table))
-    if hard is not None:
-        hard = hard.contiguous()
-        if hard.dtype == torch.bool:
-            hard = hard.view(torch.uint8)
-    if out is None:
-        out = torch.empty((n, h, k * w, 3), dtype=torch.uint8, device=guide.device)
+    labels, ids, table = labels.contiguous(), ids.contiguous(), table.contiguous()
     with torch.cuda.device(guide.device):
         _lib.call("cgs_overlay_compose_tracks", guide.data_ptr(), grey.data_ptr(), hard.data_ptr() if hard is not None else None,
                   labels.data_ptr(), ids.data_ptr(), table.data_ptr(), font.data_ptr(), n, h, w, K, r, g, b, int(alpha256), outline, boxes, k,

@@ -37,7 +37,7 @@ from time_metrics import csrc_hash, device_ms  # noqa: E402
 
 SIZES = ((360, 640), (1080, 1920))
 COPY_GB_PER_S = 6300.0          # the achievable HBM copy rate of the part (8 TB/s peak)
-BAND = 16                       # rows of a workgroup's band (csrc/overlay.hip)
+BAND = 16                       # rows of a workgroup's band (OV_BAND, csrc/overlay_body.h)
 
 
 def window_ms(fn, window=50):
