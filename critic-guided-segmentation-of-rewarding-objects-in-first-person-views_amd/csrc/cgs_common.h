@@ -47,9 +47,6 @@ struct DropCtx {
     bool on;
 };
 
-#ifndef CGS_KARG_PREFETCH
-#define CGS_KARG_PREFETCH 1
-#endif
 // One scalar load per 64-byte line of the kernel arguments, all in one batch, at the top of a kernel whose set-up reads its (several hundred bytes of)
 // arguments piecemeal: those reads are scalar loads from a segment the command processor has just written -- cold in the scalar cache -- and the compiler
 // waits for each small group before the next (SMEM returns out of order: any use is an s_waitcnt lgkmcnt(0)): ~20 dependent round trips to L2 at the start
@@ -78,34 +75,34 @@ __device__ __forceinline__ DropCtx drop_ctx(const cgs_dropout& d) {
     return c;
 }
 
-// The same, branch-free: the step counter is read unconditionally (from `safe`, any readable 8-byte-aligned device address, when the
-// layer has no Dropout), so several contexts' loads are in flight together instead of one round trip per conditional block.
-__device__ __forceinline__ DropCtx drop_ctx(const cgs_dropout& d, const void* safe) {
-    DropCtx c;
-    c.on = d.p > 0.f;
-    c.p = d.p;
-    c.scale = c.on ? 1.f / (1.f - d.p) : 1.f;
-    c.site = d.site;
-    c.base = d.base;
-    c.key = make_uint2((uint32_t)d.seed, (uint32_t)(d.seed >> 32));
-    const bool have = c.on && d.step;
-    const uint64_t* sp = have ? (const uint64_t*)d.step : (const uint64_t*)safe;
-    const uint64_t s = have ? *sp : (*sp & 0ull);
-    c.step_lo = (uint32_t)s;
-    c.step_hi = (uint32_t)(s >> 32);
-    return c;
+// Three contexts at once, branch-free: the three step counters are read unconditionally (from `safe`, any readable 8-byte-aligned device address,
+// when a layer has no Dropout) and their loads (each a scalar round trip to L2 -- the counter was written by the previous step's optimiser kernel)
+// are requested back to back BEFORE anything uses one of them; written as three drop_ctx calls the loads of the second and third context sit
+// behind the waits of the first one's argument reads.
+__device__ __forceinline__ void drop_ctx3(const cgs_dropout& da, const cgs_dropout& db, const cgs_dropout& dc, const void* safe,
+                                          DropCtx& ca, DropCtx& cb, DropCtx& cc) {
+    const bool ha = da.p > 0.f && da.step, hb = db.p > 0.f && db.step, hc = dc.p > 0.f && dc.step;
+    const uint64_t* pa = ha ? (const uint64_t*)da.step : (const uint64_t*)safe;
+    const uint64_t* pb = hb ? (const uint64_t*)db.step : (const uint64_t*)safe;
+    const uint64_t* pc = hc ? (const uint64_t*)dc.step : (const uint64_t*)safe;
+    const uint64_t va = *pa, vb = *pb, vc = *pc;
+    auto fill = [](DropCtx& c, const cgs_dropout& d, bool have, uint64_t v) {
+        c.on = d.p > 0.f;
+        c.p = d.p;
+        c.scale = c.on ? 1.f / (1.f - d.p) : 1.f;
+        c.site = d.site;
+        c.base = d.base;
+        c.key = make_uint2((uint32_t)d.seed, (uint32_t)(d.seed >> 32));
+        const uint64_t s = have ? v : 0ull;
+        c.step_lo = (uint32_t)s;
+        c.step_hi = (uint32_t)(s >> 32);
+    };
+    fill(ca, da, ha, va); fill(cb, db, hb, vb); fill(cc, dc, hc, vc);
 }
 
-#ifndef CGS_DROPCTX3
-#define CGS_DROPCTX3 1
-#endif
-// Three contexts at once: the three step-counter loads (each a scalar round trip to L2 -- the counter was written by the previous step's optimiser
-// kernel) are requested back to back BEFORE anything uses one of them; written as three drop_ctx calls the loads of the second and third context
-// sit behind the waits of the first one's argument reads.
-// The same in two halves: the three step counters REQUESTED (raw values) / the contexts FILLED from them.  A kernel whose first image's
-// global loads follow calls _load before them and _fill after: the counters' round trip then flies together with the image's loads instead
-// of in front of them (tail_enc_bwd: global_load x 3 -> s_waitcnt vmcnt(0) stood at the top of every workgroup, 2.3 us before its first
-// image load by the stage stamps; round 5).
+// The same in two halves, the three step counters REQUESTED (raw values) / the contexts FILLED from them, for tail_enc_bwd_kernel, which calls one
+// right after the other (filling behind its first image's loads measured the same, r05x).  Kept beside drop_ctx3: written either way for both
+// callers, the compiler orders the set-up of one of the two kernels differently (tail_enc_bwd_kernel<true> then needs scratch).
 __device__ __forceinline__ void drop_ctx3_load(const cgs_dropout& da, const cgs_dropout& db, const cgs_dropout& dc, const void* safe,
                                                uint64_t& va, uint64_t& vb, uint64_t& vc) {
     const bool ha = da.p > 0.f && da.step, hb = db.p > 0.f && db.step, hc = dc.p > 0.f && dc.step;
@@ -128,27 +125,6 @@ __device__ __forceinline__ void drop_ctx3_fill(const cgs_dropout& da, const cgs_
         c.step_hi = (uint32_t)(s >> 32);
     };
     fill(ca, da, va); fill(cb, db, vb); fill(cc, dc, vc);
-}
-
-__device__ __forceinline__ void drop_ctx3(const cgs_dropout& da, const cgs_dropout& db, const cgs_dropout& dc, const void* safe,
-                                          DropCtx& ca, DropCtx& cb, DropCtx& cc) {
-    const bool ha = da.p > 0.f && da.step, hb = db.p > 0.f && db.step, hc = dc.p > 0.f && dc.step;
-    const uint64_t* pa = ha ? (const uint64_t*)da.step : (const uint64_t*)safe;
-    const uint64_t* pb = hb ? (const uint64_t*)db.step : (const uint64_t*)safe;
-    const uint64_t* pc = hc ? (const uint64_t*)dc.step : (const uint64_t*)safe;
-    const uint64_t va = *pa, vb = *pb, vc = *pc;
-    auto fill = [](DropCtx& c, const cgs_dropout& d, bool have, uint64_t v) {
-        c.on = d.p > 0.f;
-        c.p = d.p;
-        c.scale = c.on ? 1.f / (1.f - d.p) : 1.f;
-        c.site = d.site;
-        c.base = d.base;
-        c.key = make_uint2((uint32_t)d.seed, (uint32_t)(d.seed >> 32));
-        const uint64_t s = have ? v : 0ull;
-        c.step_lo = (uint32_t)s;
-        c.step_hi = (uint32_t)(s >> 32);
-    };
-    fill(ca, da, ha, va); fill(cb, db, hb, vb); fill(cc, dc, hc, vc);
 }
 
 // Multipliers (0 or 1/(1-p)) for the four consecutive floats whose float4 index is idx4.
@@ -196,8 +172,8 @@ __device__ __forceinline__ float act_fwd(float v) {
 #define CGS_STAMP_PTR(p) ((unsigned long long*)nullptr)
 #endif
 
-// Phase staggering (round 4; used by the fused features.3 + encoder-tail kernel -- in every other kernel of the step it measured neutral to
-// +1 us, r4p): the workgroups of such a launch are all resident at once and walk through the same sequence of
+// Phase staggering (round 4, for the fused forward and backward kernels of the tails; since round 5's A/B only tail_enc_bwd_kernel<true> still
+// uses it): the workgroups of such a launch are all resident at once and walk through the same sequence of
 // issue-bound and latency-bound phases in lockstep; delaying every other co-resident workgroup by a few microseconds at its start lets
 // the latency-bound phases of one half run under the matrix instructions of the other.  Workgroups 256 apart share a CU (8 XCDs x 32
 // CUs, round-robin dispatch), hence bit 8.  s_sleep SLEEP = SLEEP x 64 cycles.

@@ -3,18 +3,6 @@
 #pragma once
 #include "conv_tile.h"
 
-// 1: the FMA block of every 3x3 kernel runs on the matrix cores (mfma_plane, conv_tile.h); 0: on the vector ALU (fma_plane)
-#ifndef CGS_WHATIF_NO_POOL_EPI
-#define CGS_WHATIF_NO_POOL_EPI 0
-#endif
-#ifndef CGS_POOL_EPI_MAX3
-#define CGS_POOL_EPI_MAX3 2      // 0 = the running `v > m` scan; 2 = maximum first, argmax from equality (r05 A/B: -2.7 us per step); 1 = the same with the nibble
-                                 // packing as inline-asm v_lshl_or_b32 (+2.2 us: fewer instructions, slower -- the asm statements pin the schedule); 3 = opaque idx
-#endif
-#ifndef CGS_CONV_MFMA4
-#define CGS_CONV_MFMA4 1
-#endif
-
 struct ConvParams {
     const void* src_a;
     const float* src_b;
@@ -219,7 +207,7 @@ __device__ __forceinline__ void conv_compute(const ConvParams& P, const int bid,
     // of the kernel live at once.  (The x4-upsample gradient sums across lanes, so it keeps all lanes.)
     // (matrix-core path: v_mfma ignores EXEC and broadcasts its weight operand from the lanes of one block, so every lane
     //  must keep running -- and hold valid weight registers -- until the last MFMA; the stores below are guarded by `live`)
-    constexpr bool MFMA4 = CGS_CONV_MFMA4 && C::SRC != SRC_SCALAR;
+    constexpr bool MFMA4 = C::SRC != SRC_SCALAR;      // the FMA block runs on the matrix cores (mfma_plane, conv_tile.h)
     constexpr bool ALL_LANES = (C::EPI == EPI_DGRAD && C::UPS == 4) || MFMA4;
     if constexpr (!ALL_LANES && !FUSED) {
         if (!live) return;
@@ -286,8 +274,8 @@ __device__ __forceinline__ void conv_compute(const ConvParams& P, const int bid,
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int o = 0; o < C::OCB; ++o) acc[i][o] = a4[i][o / 4][o % 4];
-        } else {
-        if constexpr (C::SRC == SRC_SCALAR) {
+        } else {      // SRC_SCALAR: one channel, on the vector ALU
+            static_assert(PB == 0, "the one-channel source has no second source");
             const float* t = (const float*)ldsA;
             float pt[4][4];
             int base = (q.img_l * G::TRA + 2 * q.qy_l) * (G::W + 2) + 2 * q.qx;
@@ -296,29 +284,6 @@ __device__ __forceinline__ void conv_compute(const ConvParams& P, const int bid,
 #pragma unroll
                 for (int dx = 0; dx < 4; ++dx) pt[dy][dx] = t[base + dy * (G::W + 2) + dx];
             fma_scalar<C::OCB>(acc, pt, wf, oc0);
-        } else {
-            constexpr int PA_FULL = C::CA / 4, REM = C::CA % 4;
-#pragma unroll 1
-            for (int pa = 0; pa < PA_FULL; ++pa) {
-                float4 pt[4][4];
-                read_patch_a<G>(pt, ldsA, pa, q, pcx);
-                fma_plane<C::OCB, 4>(acc, pt, wf, 4 * pa, oc0);
-            }
-            if constexpr (REM > 0) {
-                float4 pt[4][4];
-                read_patch_a<G>(pt, ldsA, PA_FULL, q, pcx);
-                fma_plane<C::OCB, REM>(acc, pt, wf, 4 * PA_FULL, oc0);
-            }
-        }
-        if constexpr (PB > 0) {
-#pragma unroll 1
-            for (int pb = 0; pb < PB; ++pb) {
-                float4 pt[4][4];
-                if constexpr (C::UPS == 2) read_patch_b2<G>(pt, ldsB, pb, q);
-                else read_patch_b4<G>(pt, ldsB, pb, q);
-                fma_plane<C::OCB, 4>(acc, pt, wf, C::CA + 4 * pb, oc0);
-            }
-        }
         }
 
         // ---------------- epilogues ----------------
@@ -329,13 +294,7 @@ __device__ __forceinline__ void conv_compute(const ConvParams& P, const int bid,
             uint32_t nib[(C::OCB + 7) / 8];
 #pragma unroll
             for (int i = 0; i < (C::OCB + 7) / 8; ++i) nib[i] = 0;
-#if CGS_WHATIF_NO_POOL_EPI      // (experiment only: wrong results) how much of the kernel is the pooled epilogue's arithmetic?
-            if constexpr (true) {
-#pragma unroll
-                for (int o = 0; o < C::OCB; ++o) pooled[o] = (acc[0][o] + acc[1][o]) + (acc[2][o] + acc[3][o]);
-            } else
-#endif
-            if constexpr (C::ACT == CGS_ACT_RELU && CGS_POOL_EPI_MAX3) {
+            if constexpr (C::ACT == CGS_ACT_RELU) {
                 // max over the window FIRST (ReLU is monotone: max_i relu(s_i) = relu(max_i s_i)), the argmax from equality with it:
                 // the first position whose pre-activation equals a POSITIVE maximum is the first maximum of the activations (what the
                 // running `v > m` scan below picks); a window whose maximum is <= 0 is 0xF either way.  ~14 instead of 21 VALU
@@ -356,11 +315,9 @@ __device__ __forceinline__ void conv_compute(const ConvParams& P, const int bid,
                         idx = s[1][h] == mr ? 1u : idx;
                         idx = s[0][h] == mr ? 0u : idx;
                         if (!(mr > 0.f)) idx = 15u;
-                        // channels from the top down: channel o ends at bits 4 (o % 8) ..  (as an instruction: left to the compiler the shift is
-                        // folded into the selects' constants -- 0x20000000, 0x30000000, ... -- which it then has to keep moving into registers)
-                        if constexpr (CGS_POOL_EPI_MAX3 == 1) asm("v_lshl_or_b32 %0, %1, 4, %2" : "=v"(nib[o / 8]) : "v"(nib[o / 8]), "v"(idx));
-                        else if constexpr (CGS_POOL_EPI_MAX3 == 3) { asm("" : "+v"(idx)); nib[o / 8] = (nib[o / 8] << 4) | idx; }
-                        else nib[o / 8] = (nib[o / 8] << 4) | idx;
+                        // channels from the top down: channel o ends at bits 4 (o % 8) ..  (r05 A/B: -2.7 us per step against the running scan; the
+                        // packing as inline-asm v_lshl_or_b32 had fewer instructions and measured +2.2 us -- the asm statements pin the schedule)
+                        nib[o / 8] = (nib[o / 8] << 4) | idx;
                     }
                 }
             } else {
@@ -585,7 +542,7 @@ __device__ __forceinline__ void conv3x3_body_pipe(const ConvParams& P, const int
     using L = ConvLds<C>;
     constexpr int PA = L::PA, PB = L::PB, TPW = tpw_of<C>::value;
     static_assert(G::IMGS == 1, "pipelined tiles are strips of one image");
-    static_assert(CGS_CONV_MFMA4 && C::SRC != SRC_SCALAR && C::SRC != SRC_DH && C::SRC != SRC_F32C3, "matrix-core path, split loaders");
+    static_assert(C::SRC != SRC_SCALAR && C::SRC != SRC_DH && C::SRC != SRC_F32C3, "matrix-core path, split loaders");
     static_assert(PB == 0 || C::UPS == 2, "source B at half resolution");
     static_assert(C::EPI == EPI_DGRAD || !C::DROP, "no Dropout in the split fp32 loader");
     float4* const ldsA = smem;
@@ -708,9 +665,6 @@ CGS_DG_CFG(DMaskHead, 64, 128, SRC_DH, 16, 11, 16, 2, 3, 8, 4, 3, CGS_ACT_NONE, 
 // features.0 on the mixes 32.0 -> 30.8 us, features.0 + mix backward 54.1 -> 50.0, features.3 backward 30.2 -> 29.7, features.0 on the
 // frames 28.7 -> 28.4; features.3 forward, dec_model.0 forward / data gradient were neutral to slower: these kernels are bound by
 // instruction issue, their load phases already hide behind the other resident workgroups)
-#ifndef CGS_CONV_PIPE
-#define CGS_CONV_PIPE 1
-#endif
 struct FEnc0U8P : FEnc0U8 { static constexpr int TPW = 4; };
 struct FEnc0MixP : FEnc0Mix { static constexpr int TPW = 4; };
 struct DEnc1P : DEnc1 { static constexpr int TPW = 2; };

@@ -9,7 +9,7 @@
 
 template <class CWG, class CDG, bool SPARSE>
 __global__ void __launch_bounds__(CWG::G::THREADS) conv_bwd_both_kernel(WgradParams pw, ConvParams pd, int nbw) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(WgradParams) + sizeof(ConvParams) + 8>();
+    cgs_kernarg_prefetch<sizeof(WgradParams) + sizeof(ConvParams) + 8>();
     static_assert(CWG::G::THREADS == CDG::THREADS * CDG::CW, "both halves use the same workgroup size");
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     if ((int)blockIdx.x < nbw) {
@@ -46,7 +46,7 @@ static int both_slabs(int n) {
     using GW = typename CWG::G;
     int tiles = (GW::IMGS == 1) ? n * GW::STRIPS : (n + GW::IMGS - 1) / GW::IMGS;
     int cap = GW::H >= 32 ? kMaxBothWgradBlocksBig : kMaxBothWgradBlocks;
-    if (both_sparse_ok<CWG> && wgrad_sparse_enabled()) {
+    if (both_sparse_ok<CWG>) {
         cap = GW::H >= 64 ? CGS_CAP_W0MIX : CGS_CAP_W1R;      // persistent sparse workgroups (swept on the step in round 3; A/B macros round 5)
     }
     return tiles < cap ? tiles : cap;
@@ -64,16 +64,9 @@ static int launch_both(WgradParams pw, const ConvParams& pd, hipStream_t st) {
     nbd /= tpw_of<CDG>::value;
     pw.ntiles = tiles;
     const size_t ld = conv_lds_bytes<CDG>();
-    if constexpr (sparse_cfg<CWG>::ok) {
-        if (wgrad_sparse_enabled()) {
-            const size_t lw = wgrad_any_lds_bytes<CWG, true>();
-            hipLaunchKernelGGL((conv_bwd_both_kernel<CWG, CDG, true>), dim3(nbw + nbd), dim3(GW::THREADS), lw > ld ? lw : ld, st, pw, pd, nbw);
-            CGS_HIP_CHECK_LAUNCH();
-            return CGS_OK;
-        }
-    }
-    const size_t lw = wgrad_lds_bytes<CWG>();
-    hipLaunchKernelGGL((conv_bwd_both_kernel<CWG, CDG, false>), dim3(nbw + nbd), dim3(GW::THREADS), lw > ld ? lw : ld, st, pw, pd, nbw);
+    constexpr bool SPARSE = both_sparse_ok<CWG>;      // the sparse weight gradient wherever one exists
+    const size_t lw = wgrad_any_lds_bytes<CWG, SPARSE>();
+    hipLaunchKernelGGL((conv_bwd_both_kernel<CWG, CDG, SPARSE>), dim3(nbw + nbd), dim3(GW::THREADS), lw > ld ? lw : ld, st, pw, pd, nbw);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
 }
@@ -129,7 +122,7 @@ extern "C" int cgs_conv3x3_bwd_both(const cgs_conv_desc* d, const void* src_a, c
         case 2: if (d->drop_a.p > 0.f) return CGS_ERR_UNSUPPORTED; return launch_both<WEnc2, DEnc2>(pw, pd, st);
         case 3: if (d->drop_a.p > 0.f) return CGS_ERR_UNSUPPORTED; return launch_both<WDec1, DDec1>(pw, pd, st);
         case 4: if (d->drop_a.p > 0.f) return CGS_ERR_UNSUPPORTED; return launch_both<WDec2x, DDec2>(pw, pd, st);
-        case 5: if (d->drop_a.p > 0.f) return CGS_ERR_UNSUPPORTED; return CGS_CONV_PIPE ? launch_both<WEnc1, DEnc1P>(pw, pd, st) : launch_both<WEnc1, DEnc1>(pw, pd, st);
+        case 5: if (d->drop_a.p > 0.f) return CGS_ERR_UNSUPPORTED; return launch_both<WEnc1, DEnc1P>(pw, pd, st);
         case 6: if (d->drop_a.p > 0.f) return CGS_ERR_UNSUPPORTED; return launch_both<WDec0, DDec0>(pw, pd, st);
         case 7: if (d->drop_a.p > 0.f) return CGS_ERR_UNSUPPORTED; return launch_both<WDec3x, DDec3y>(pw, pd, st);
         case 8: if (d->drop_a.p > 0.f) return CGS_ERR_UNSUPPORTED; return launch_both<WEnc0F32, DEnc0>(pw, pd, st);
@@ -161,27 +154,16 @@ struct MixBwdArgs {
 // (round 5) nbw1 > 0: features.3's sparse weight gradient (pw1; the role conv_bwd_both_kernel<WEnc1, ...> gave it) as nbw1 more workgroups
 // behind features.0's -- its data gradient now runs inside the tail backward launch (cgs_tail_enc_bwd_enc1), and only the step's final
 // reduction waits for this slab.
-#ifndef CGS_R1_MIX
-#define CGS_R1_MIX 1
-#endif
-#ifndef CGS_MIX_WAVES
-#define CGS_MIX_WAVES 0
-#endif
-#if CGS_MIX_WAVES
-#define CGS_MIX_OCC __attribute__((amdgpu_waves_per_eu(CGS_MIX_WAVES, CGS_MIX_WAVES)))
-#else
-#define CGS_MIX_OCC
-#endif
 template <class CWG, bool SPARSE, bool R1>       // R1: the instance that carries the features.3 rider role (a role's registers are the whole launch's)
-__global__ void __launch_bounds__(256) CGS_MIX_OCC enc0_bwd_mix_kernel(WgradParams pw, ConvParams pd, MixBwdArgs M, int nbw, WgradParams pw1, int nbw1) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<2 * sizeof(WgradParams) + sizeof(ConvParams) + sizeof(MixBwdArgs) + 16>();
+__global__ void __launch_bounds__(256) enc0_bwd_mix_kernel(WgradParams pw, ConvParams pd, MixBwdArgs M, int nbw, WgradParams pw1, int nbw1) {
+    cgs_kernarg_prefetch<2 * sizeof(WgradParams) + sizeof(ConvParams) + sizeof(MixBwdArgs) + 16>();
     using G = Geo<DEnc0::H, DEnc0::W, DEnc0::THREADS, DEnc0::CW>;
     static_assert(CWG::G::THREADS == 256 && DEnc0::THREADS * DEnc0::CW == 256 && G::IMGS == 1, "workgroup shape");
     static_assert(WEnc1::G::THREADS == 256, "workgroup shape");
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
-    // block order (A/B: CGS_R1_MIX): 0 = [riders | features.0 weight gradient | data gradient], 1 = [w | riders | d], 2 = [w | d | riders]
-    const int gx = (int)gridDim.x, bx = (int)blockIdx.x;
-    const int r_lo = CGS_R1_MIX == 0 ? 0 : (CGS_R1_MIX == 1 ? nbw : gx - nbw1);
+    // block order: [features.0 weight gradient | riders | data gradient] (A/B against the riders first or last)
+    const int bx = (int)blockIdx.x;
+    const int r_lo = nbw;
     if constexpr (R1) {
         if (bx >= r_lo && bx < r_lo + nbw1) {
             constexpr int SLAB1 = (9 * 8 + 1) * 8;
@@ -193,21 +175,14 @@ __global__ void __launch_bounds__(256) CGS_MIX_OCC enc0_bwd_mix_kernel(WgradPara
     const int bm = bx - ((R1 && bx >= r_lo) ? nbw1 : 0);       // index among the launch's own roles
     if (bm < nbw) {
         constexpr int SLAB = (9 * 3 + 1) * 8;
-#ifdef CGS_WHATIF_MIX_NOW      // (timing experiments only: wrong results) one role of the launch compiled out
-        if (pw.n >= 0) return;
-#endif
         wgrad_dispatch<CWG, SPARSE>(pw, bm, nbw, pw.ntiles, pw.slab + (size_t)bm * SLAB, smem);
         return;
     }
-#ifdef CGS_WHATIF_MIX_NOD
-    if (pw.n >= 0) return;
-#endif
     const int bid = bm - nbw;
     pd.mix_a = M.a; pd.mix_b = M.b; pd.mix_z = M.z; pd.mix_dz = M.dzpre; pd.mix_l1s = M.l1s; pd.mix_l2s = M.l2s; pd.mix_vf_pred = M.vf_pred;
     pd.mix_inject = M.inject;
     pd.mix_n_a = M.n_a;
-    if constexpr (CGS_CONV_PIPE) conv3x3_body_pipe<DEnc0DP>(pd, bid * DEnc0DP::TPW, smem);
-    else conv3x3_body<DEnc0D, true>(pd, bid, smem);
+    conv3x3_body_pipe<DEnc0DP>(pd, bid * DEnc0DP::TPW, smem);
 }
 
 extern "C" int cgs_enc0_bwd_mix_slabs(int32_t n_mix) { return n_mix < 0 ? CGS_ERR_BADARG : both_slabs<WEnc0F32>(n_mix); }
@@ -236,8 +211,7 @@ extern "C" int cgs_enc0_bwd_mix_enc1(int32_t n_a, int32_t inject, const float* m
     pd.src_a = dy; pd.amask_in = amask; pd.w = w; pd.n = n_mix;
     MixBwdArgs M{a, b, z, dzpre, n_a, inject ? 1 : 0, l1_scale, l2_scale, valuefak_pred};
     const int nbw = slab ? both_slabs<WEnc0F32>(n_mix) : 0;
-    const int nbd = CGS_CONV_PIPE ? n_a * GD::STRIPS / DEnc0DP::TPW : n_a * GD::STRIPS;
-    const bool sp = wgrad_sparse_enabled() != 0;
+    const int nbd = n_a * GD::STRIPS / DEnc0DP::TPW;
     WgradParams pw1{};
     int nbw1 = 0;
     size_t lw1 = 0;
@@ -246,18 +220,16 @@ extern "C" int cgs_enc0_bwd_mix_enc1(int32_t n_a, int32_t inject, const float* m
         pw1.src_a = e0_1; pw1.dy = dy1; pw1.amask = am1; pw1.slab = slab1; pw1.n = n_mix;
         pw1.ntiles = (GW1::IMGS == 1) ? n_mix * GW1::STRIPS : (n_mix + GW1::IMGS - 1) / GW1::IMGS;
         nbw1 = both_slabs<WEnc1>(n_mix);
-        lw1 = sp ? wgrad_any_lds_bytes<WEnc1, true>() : wgrad_lds_bytes<WEnc1>();
+        lw1 = wgrad_any_lds_bytes<WEnc1, true>();
     }
-    const size_t lw = sp ? wgrad_any_lds_bytes<WEnc0F32, true>() : wgrad_lds_bytes<WEnc0F32>(), ld = conv_lds_bytes<DEnc0>();
+    const size_t lw = wgrad_any_lds_bytes<WEnc0F32, true>(), ld = conv_lds_bytes<DEnc0>();
     size_t lds = lw > ld ? lw : ld;                    // 41 KB (data-gradient tile): three workgroups per CU
     if (lw1 > lds) lds = lw1;
     const dim3 grid(nbw + nbd + nbw1);
     const bool r1 = nbw1 > 0;
     auto k = (mixed || !slab)       // materialised mixes (or no weight gradient at all) / mixes recomputed in the tile loader
-                 ? (sp ? (r1 ? enc0_bwd_mix_kernel<WEnc0F32, true, true> : enc0_bwd_mix_kernel<WEnc0F32, true, false>)
-                       : (r1 ? enc0_bwd_mix_kernel<WEnc0F32, false, true> : enc0_bwd_mix_kernel<WEnc0F32, false, false>))
-                 : (sp ? (r1 ? enc0_bwd_mix_kernel<WEnc0Mix, true, true> : enc0_bwd_mix_kernel<WEnc0Mix, true, false>)
-                       : (r1 ? enc0_bwd_mix_kernel<WEnc0Mix, false, true> : enc0_bwd_mix_kernel<WEnc0Mix, false, false>));
+                 ? (r1 ? enc0_bwd_mix_kernel<WEnc0F32, true, true> : enc0_bwd_mix_kernel<WEnc0F32, true, false>)
+                 : (r1 ? enc0_bwd_mix_kernel<WEnc0Mix, true, true> : enc0_bwd_mix_kernel<WEnc0Mix, true, false>);
     hipLaunchKernelGGL(k, grid, dim3(256), lds, (hipStream_t)stream, pw, pd, M, nbw, pw1, nbw1);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;

@@ -73,12 +73,11 @@ extern "C" int cgs_conv3x3_fwd(const cgs_conv_desc* d, const void* src_a, const 
               d->drop_a.p == 0.f))
             return CGS_ERR_UNSUPPORTED;
         P.src_a = nullptr; P.mix_a = m->a; P.mix_b = m->b; P.mix_z = m->z; P.mix_n_a = m->n_a;
-        return CGS_CONV_PIPE ? launch_conv_pipe<FEnc0MixP>(P, st) : launch_conv<FEnc0Mix>(P, st);
+        return launch_conv_pipe<FEnc0MixP>(P, st);
     }
     const int R = CGS_ACT_RELU, L = CGS_ACT_LRELU, S = CGS_ACT_SIGMOID, NO = CGS_ACT_NONE;
     if (d->drop_a.p > 0.f && !(desc_is(d, 8, 8, 0, 16, CGS_SRC_F32, 2, R, 1))) return CGS_ERR_UNSUPPORTED;
-    if (desc_is(d, 64, 3, 0, 8, CGS_SRC_U8, 2, R, 1))
-        return CGS_CONV_PIPE ? launch_conv_pipe<FEnc0U8P>(P, st) : launch_conv<FEnc0U8>(P, st);
+    if (desc_is(d, 64, 3, 0, 8, CGS_SRC_U8, 2, R, 1)) return launch_conv_pipe<FEnc0U8P>(P, st);
     if (desc_is(d, 64, 3, 0, 8, CGS_SRC_F32, 2, R, 1)) return launch_conv<FEnc0F32>(P, st);
     if (desc_is(d, 32, 8, 0, 8, CGS_SRC_F32, 2, R, 1))
         return launch_conv<FEnc1>(P, st);      // (pipelined form: 17.9 vs 17.7 us, r4b)

@@ -310,23 +310,16 @@ __device__ __forceinline__ void static_for(F&& f) {
 // instructions of tile t run, and only the LDS stores sit between two tiles' compute phases.  Same element maps, clamping and
 // select-to-zero as the one-piece loaders above (bit-identical tiles).  The halo columns are zeroed once per workgroup by the caller.
 // ------------------------------------------------------------------------------------------------
-#ifndef CGS_ELEMS_GUARD
-#define CGS_ELEMS_GUARD 1
-#endif
 template <int E, int THREADS, class F>
 __device__ __forceinline__ void for_elems_it(int tid, F f) {
     constexpr int IT = (E + THREADS - 1) / THREADS;
     static_for<IT>([&](auto I) {
         constexpr int it = decltype(I)::value;
         int e = tid + it * THREADS;
-#if CGS_ELEMS_GUARD
         // the partial last round (features.0's strips: 288 groups = one full round + 32 threads) is skipped by the waves that have no element in it --
         // run with clamped indices by every wave it was half of the staging instructions of three waves in four (round 5)
         if constexpr ((it + 1) * THREADS <= E) f(std::integral_constant<int, it>{}, e);
         else if (e < E) f(std::integral_constant<int, it>{}, e);
-#else
-        f(std::integral_constant<int, it>{}, e < E ? e : E - 1);
-#endif
     });
 }
 
@@ -510,46 +503,14 @@ __device__ __forceinline__ void commit_b_half(const FetchBHalf<G, PB>& R, float4
 }
 
 // ------------------------------------------------------------------------------------------------
-// Compute core: accumulate one float4 plane (4 input channels) of a 4x4 receptive field into the
-// 2x2 x OCB accumulator block.  WF(tap, ci, oc) returns the (wave-uniform) weight.
-// ------------------------------------------------------------------------------------------------
-template <int OCB, int NCH, class WF>
-__device__ __forceinline__ void fma_plane(float (&acc)[4][OCB], const float4 (&pt)[4][4], WF wf, int ci0, int oc0) {
-    // 9*NCH steps of (one tap, one input channel): OCB weights -> 4*OCB FMAs.  The weights of step s+1 are
-    // read (LDS broadcast) before the FMAs of step s are issued; the compiler barrier after each step keeps
-    // the reads of step s+2 from being hoisted further (bounded registers, one step of latency cover).
-    constexpr int NS = 9 * NCH;
-    float w[2][OCB];
-#pragma unroll
-    for (int o = 0; o < OCB; ++o) w[0][o] = wf(0, ci0, oc0 + o);
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int tap = s / NCH, c = s % NCH, ky = tap / 3, kx = tap % 3;
-        if (s + 1 < NS) {
-#pragma unroll
-            for (int o = 0; o < OCB; ++o) w[(s + 1) & 1][o] = wf((s + 1) / NCH, ci0 + (s + 1) % NCH, oc0 + o);
-        }
-#pragma unroll
-        for (int oy = 0; oy < 2; ++oy)
-#pragma unroll
-            for (int ox = 0; ox < 2; ++ox) {
-                float x = f4get(pt[oy + ky][ox + kx], c);
-#pragma unroll
-                for (int o = 0; o < OCB; ++o) acc[oy * 2 + ox][o] = fmaf(x, w[s & 1][o], acc[oy * 2 + ox][o]);
-            }
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same step on the matrix cores: v_mfma_f32_4x4x1_16B_f32 with the A operand broadcast from one of its 16 blocks
+// Compute core: accumulate one float4 plane (4 input channels) of a 4x4 receptive field into the 2x2 x OCB accumulator
+// block, on the matrix cores: v_mfma_f32_4x4x1_16B_f32 with the A operand broadcast from one of its 16 blocks
 // (cbsz = 4, abid = block) computes   D[lane][r] += A[4*abid + r] * B[lane]   (r = 0..3): with B = the lane's input value of
 // one (tap, input channel) and A = the four weights of one output-channel group, ONE instruction is the quad position's 4
 // FMAs of that step for all 64 lanes, at the full fp32 rate (tools/mfma4_peak.hip: 150 TFLOP/s sustained vs 115 for
 // v_fma_f32) with no padding rows or columns at 8 (or 3) channels.  A weight REGISTER holds 16 blocks = 16 (tap, channel)
 // steps of a channel group: lane 4*b + i of register k carries w[step 16*k + b][group's channel i]; the whole 8 -> 8 layer
-// is 9 registers.  An exact fp32 FMA chain in the same (tap, channel) order as fma_plane.
+// is 9 registers.  An exact fp32 FMA chain in (tap, channel) order, as the vector-ALU form it replaced ran it.
 // ------------------------------------------------------------------------------------------------
 typedef float frag4 __attribute__((ext_vector_type(4)));
 

@@ -43,7 +43,7 @@ static constexpr int kMaxSparseBlocks = 512;
 template <class C>
 static int wg_blocks_any(int n) {
     using G = typename C::G;
-    if (sparse_cfg<C>::ok && wgrad_sparse_enabled()) {
+    if (sparse_cfg<C>::ok) {
         const int cap = G::H >= 64 ? CGS_CAP_W0U8 : kMaxSparseBlocks;      // measured: 1024 / 512
         int t = wg_tiles<G>(n);
         return t < cap ? t : cap;
@@ -56,16 +56,9 @@ static int launch_wgrad(WgradParams P, hipStream_t st) {
     using G = typename C::G;
     P.ntiles = wg_tiles<G>(P.n);
     if (P.ntiles == 0) return CGS_OK;
-    if constexpr (sparse_cfg<C>::ok) {
-        if (wgrad_sparse_enabled()) {
-            const size_t lds = wgrad_any_lds_bytes<C, true>();
-            hipLaunchKernelGGL((wgrad_any_kernel<C, true>), dim3(wg_blocks_any<C>(P.n)), dim3(G::THREADS), lds, st, P);
-            CGS_HIP_CHECK_LAUNCH();
-            return CGS_OK;
-        }
-    }
-    const size_t lds = wgrad_lds_bytes<C>();
-    hipLaunchKernelGGL((wgrad_any_kernel<C, false>), dim3(wg_blocks<G>(P.n)), dim3(G::THREADS), lds, st, P);
+    constexpr bool SPARSE = sparse_cfg<C>::ok;      // the sparse form wherever one exists
+    const size_t lds = wgrad_any_lds_bytes<C, SPARSE>();
+    hipLaunchKernelGGL((wgrad_any_kernel<C, SPARSE>), dim3(wg_blocks_any<C>(P.n)), dim3(G::THREADS), lds, st, P);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
 }
@@ -75,28 +68,17 @@ static int launch_wgrad(WgradParams P, hipStream_t st) {
 // launch it disappears behind the sparse gather (round 3: one dependent launch less on the critical path).
 // (round 5) nbw1 > 0: features.3's sparse weight gradient of the same pass (P1) as nbw1 more workgroups between the two roles -- its data
 // gradient runs inside the tail backward launch (cgs_tail_enc_bwd_enc1).
-#ifndef CGS_R1_U8
-#define CGS_R1_U8 1
-#endif
 // four waves per SIMD = 128 registers: what the kernel's own two roles need (114 + 4), so the launch keeps four workgroups per CU
 // (-Rpass-analysis=kernel-resource-usage)
-#ifndef CGS_U8_WAVES
-#define CGS_U8_WAVES 4
-#endif
-#if CGS_U8_WAVES
-#define CGS_U8_OCC __attribute__((amdgpu_waves_per_eu(CGS_U8_WAVES, CGS_U8_WAVES)))
-#else
-#define CGS_U8_OCC
-#endif
 // R1: does this instance carry the features.3 rider role -- a role's registers are the whole launch's (the general features.3 body took this
 // kernel from 114 to 256 VGPRs), so a launch without the rider runs the instance without its code.
 template <bool R1>
-__global__ void __launch_bounds__(256) CGS_U8_OCC wgrad_enc0u8_head_kernel(WgradParams P, HeadWgradParams H, int nbw, WgradParams P1, int nbw1) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<2 * sizeof(WgradParams) + sizeof(HeadWgradParams) + 16>();
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) wgrad_enc0u8_head_kernel(WgradParams P, HeadWgradParams H, int nbw, WgradParams P1, int nbw1) {
+    cgs_kernarg_prefetch<2 * sizeof(WgradParams) + sizeof(HeadWgradParams) + 16>();
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
-    // block order (A/B: CGS_R1_U8): 0 = [riders | features.0 | head], 1 = [features.0 | riders | head], 2 = [features.0 | head | riders]
-    const int gx = (int)gridDim.x, bx = (int)blockIdx.x;
-    const int r_lo = CGS_R1_U8 == 0 ? 0 : (CGS_R1_U8 == 1 ? nbw : gx - nbw1);
+    // block order: [features.0 | riders | head] (A/B against the riders first or last)
+    const int bx = (int)blockIdx.x;
+    const int r_lo = nbw;
     if constexpr (R1) {
         if (bx >= r_lo && bx < r_lo + nbw1) {
             constexpr int SLAB1 = (9 * 8 + 1) * 8;
@@ -126,7 +108,6 @@ extern "C" int cgs_enc0_wgrad_u8_with_head_enc1(int32_t n, const uint8_t* x_u8, 
     if (n0 < 0 || n1 < 0 || n0 + n1 == 0 || !slab_head || (n0 > 0 && (!hvec0 || !e4_0)) || (n1 > 0 && (!hvec1 || !e4_1))) return CGS_ERR_BADARG;
     if ((d_o4_0 || d_o4_1) && !slab_pw) return CGS_ERR_BADARG;
     if (slab1 && (n1w <= 0 || !e0_1 || !dy1 || !am1 || nslab1 <= 0)) return CGS_ERR_BADARG;
-    if (slab1 && !(sparse_cfg<WEnc1>::ok && wgrad_sparse_enabled())) return CGS_ERR_UNSUPPORTED;
     WgradParams P{};
     P.src_a = x_u8; P.dy = dy; P.amask = amask; P.slab = slab; P.n = n;
     P.ntiles = wg_tiles<WEnc0U8::G>(n);

@@ -519,9 +519,6 @@ __device__ __forceinline__ void phase2_loss_values(const LossArgs& L) {
     }
 }
 
-#ifndef CGS_REDUCE_DEEP
-#define CGS_REDUCE_DEEP 0
-#endif
 #ifndef CGS_REDUCE_COLS
 #define CGS_REDUCE_COLS 32      // columns per workgroup (64: a wave reads 256 contiguous bytes of a slab row instead of two rows' 128; A/B round 5)
 #endif
@@ -557,18 +554,7 @@ __global__ void __launch_bounds__(COLS * SL) reduce_adam_kernel(const cgs_reduce
         if (i < j.count) {
             const float* p = j.slab + i;
             int b = sl;
-#if CGS_REDUCE_DEEP
-            // (A/B round 5) 32 loads in flight per thread for the 512- and 1024-row jobs: half as many dependent memory round trips
-            for (; b + 31 * SL < j.nslab; b += 32 * SL) {
-                float t[32];
-#pragma unroll
-                for (int u = 0; u < 32; ++u) t[u] = p[(size_t)(b + u * SL) * j.stride];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) s[u] += t[u];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) s[u] += t[16 + u];
-            }
-#endif
+            // (A/B round 5: 32 loads in flight per thread for the 512- and 1024-row jobs, half as many dependent round trips, was not kept)
             for (; b + 15 * SL < j.nslab; b += 16 * SL) {
 #pragma unroll
                 for (int u = 0; u < 16; ++u) s[u] += p[(size_t)(b + u * SL) * j.stride];

@@ -123,14 +123,8 @@ __global__ void __launch_bounds__(256) gen4_pack_batch_kernel(Gen4PackBatch B) {
 // VEC = 1 (round 6; launcher: FOLD = 0, NG >= 8, a vector source -- fp32 with ca % 4 == 0, or the pooled map + argmax): only those loaders are
 // instantiated and the chunk loop is peeled (every chunk but the last has 16 channels: ONE tap nest in the loop body, the accumulators stay in one
 // register set) -- the instance fits 128 registers, FOUR workgroups per CU with one tile buffer.
-#ifndef G4_VEC
-#define G4_VEC 1
-#endif
 #ifndef G4_VEC_BATCH
 #define G4_VEC_BATCH 3
-#endif
-#ifndef G4_VEC_S2D
-#define G4_VEC_S2D 1
 #endif
 #ifndef G4_WPE_VEC
 #define G4_WPE_VEC 4
@@ -143,7 +137,7 @@ constexpr bool g4_tiny(int ng, int fold) { return ng <= 4 && fold >= 1; }
 template <int NG, int FOLD, bool VEC> constexpr int g4_wpe() { return VEC ? G4_WPE_VEC : (NG >= 8 ? G4_WPE_BIG : (g4_tiny(NG, FOLD) ? G4_WPE_TINY : G4_WPE_SMALL)); }
 template <int NG, int FOLD, bool VEC = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(g4_wpe<NG, FOLD, VEC>(), g4_wpe<NG, FOLD, VEC>()))) gen4_conv3x3_kernel(Gen4Params P) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(Gen4Params)>();
+    cgs_kernarg_prefetch<sizeof(Gen4Params)>();
     extern __shared__ __attribute__((aligned(16))) float4 g4sm[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const GenSrc& S = P.src;
@@ -617,8 +611,7 @@ int gen4_conv_launch(const Gen4Launch& L, hipStream_t st) {
     // the epilogue reuses the area for 256 pixels x (4 ng + 4) floats (pooling included: the cells' maxima are taken by the copy-out threads)
     const size_t tile_bytes = (size_t)4 * P.rows * P.pw * sizeof(float4);
     const int cp = ((L.src.ca + 3) & ~3) + L.src.cb;
-    const bool vec = G4_VEC && ng >= 8 &&
-                     ((!L.fold && (L.src.mode == GEN_SRC_POOLEXP || (L.src.mode == GEN_SRC_F32 && !(L.src.ca & 3)))) || (L.fold == 2 && G4_VEC_S2D));
+    const bool vec = ng >= 8 && ((!L.fold && (L.src.mode == GEN_SRC_POOLEXP || (L.src.mode == GEN_SRC_F32 && !(L.src.ca & 3)))) || L.fold == 2);
     const int wpe = vec ? G4_WPE_VEC : (ng >= 8 ? G4_WPE_BIG : (g4_tiny(ng, L.fold) ? G4_WPE_TINY : G4_WPE_SMALL));
     const size_t budget = vec && wpe == 4 ? (size_t)40960 : (size_t)(160 * 1024) / wpe - 512;
     P.dbuf = ((cp > GEN_KC || L.fold) && 2 * tile_bytes <= budget) ? 1 : 0;

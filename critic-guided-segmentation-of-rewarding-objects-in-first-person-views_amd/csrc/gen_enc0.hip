@@ -235,9 +235,6 @@ struct GEnc0WgParams {
     int n, a_is_u8, nstrips;
 };
 
-#ifndef GC0W_UNROLL
-#define GC0W_UNROLL 1
-#endif
 template <class F, int... Is>
 __device__ __forceinline__ void genc0_static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
 template <int N, class F>
@@ -266,7 +263,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
 
     for (int e = tid; e < TROWS * 2; e += 256) tile[(e >> 1) * TW + ((e & 1) ? TW - 1 : 0)] = f4zero();      // halo columns
     __syncthreads();
-#if GC0W_UNROLL
     // per-lane operand bases of step 0 (pixel b of tile row 0): the steps add compile-time offsets
     const float* apx[7];
     const float* dpx[NQW];
@@ -279,7 +275,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
         dpx[q] = des + col0; mpx[q] = ams + col0;
     }
     const uint32_t pos_even = (uint32_t)(b & 1), pos_odd = 2u + (uint32_t)(b & 1);
-#endif
 
     for (int strip = blockIdx.x; strip < P.nstrips; strip += gridDim.x) {
         const int img = strip >> 3, row0 = (strip & 7) * TH;
@@ -341,7 +336,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
                 }
             }
         };
-#if GC0W_UNROLL
         // (round 6) The 32 steps of a strip as straight-line code: a step's place in the strip is a compile-time constant, so every LDS read is
         // a per-lane base register (set once per workgroup) + an IMMEDIATE offset and the select's position code one of two per-lane registers --
         // 6 vector instructions per step beside its <= 21 matrix instructions where the loop form spent 30 on addresses (fp32 matrix and vector
@@ -371,38 +365,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
                 __builtin_amdgcn_sched_barrier(0);
             });
         }
-#else
-        auto load_ops = [&](int s, float (&av)[7], float (&bv)[NQW], uint32_t (&bm)[NQW + 1]) __attribute__((always_inline)) {
-            const int y = s >> 2, x = (s & 3) * 16 + b;
-            const float* px = (const float*)(tile + y * TW + x);    // tap (0,0) of the pixel's 3x3 window (tile row 0 = image row row0 - 1)
-#pragma unroll
-            for (int rq = 0; rq < 7; ++rq) av[rq] = px[aoff[rq]];
-            const int cell = (y >> 1) * 32 + (x >> 1);
-            bm[NQW] = 2 * (y & 1) + (x & 1);
-#pragma unroll
-            for (int q = 0; q < NQW; ++q) {
-                const int cq = wave + 4 * q;                        // this wave's column quad (past NG: a valid address, never multiplied)
-                const int col = cell * CO + 4 * (cq < NG ? cq : 0) + i;
-                bv[q] = des[col]; bm[q] = ams[col];
-            }
-        };
-        {
-            float a0[7], a1[7], b0[NQW], b1[NQW];
-            uint32_t m0[NQW + 1], m1[NQW + 1];
-            load_ops(0, a0, b0, m0);
-#pragma unroll 1
-            for (int s = 0; s < TH * 4; s += 2) {
-                load_ops(s + 1, a1, b1, m1);
-                __builtin_amdgcn_sched_barrier(0);
-                mfmas(a0, b0, m0);
-                __builtin_amdgcn_sched_barrier(0);
-                load_ops(s + 2 < TH * 4 ? s + 2 : s, a0, b0, m0);
-                __builtin_amdgcn_sched_barrier(0);
-                mfmas(a1, b1, m1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#endif
         __syncthreads();
     }
     // ---- add the 16 blocks (lanes with equal lane & 3), one slab row per workgroup: D_b[r][j] -> row 4 rq + r, column 4 cq + j (j = lane & 3) ----

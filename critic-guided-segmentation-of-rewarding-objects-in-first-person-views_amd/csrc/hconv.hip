@@ -16,24 +16,8 @@
 // config 5 therefore write fp32.  OPT-IN precisions: never used by the fp32 training path or the parity-gated fp32 paths.
 #include "tail_common.h"
 
-#ifndef H5_PREFETCH
-#define H5_PREFETCH 0             // h5conv: 1 = the next strip's loads issued before the current strip's matrix loop; 0 = right before their commit
-                                  // (r4 A/B at config 5: 1.035 vs 1.048 ms per step -- the 40 more live registers cost more than the overlap returns;
-                                  // what pays is issuing a strip's loads back to back: one memory round trip per strip either way)
-#endif
 #ifndef H5_PER_CU
 #define H5_PER_CU 4               // h5conv: persistent workgroups per CU (at most; LDS may allow fewer)
-#endif
-#ifndef H5_PAIR16
-#define H5_PAIR16 0              // h5conv: 1 = tile pairing also for 16-channel pixels with 8 outputs (20 more weight registers; r4 A/B: 0.8 % slower per config-5 step)
-#endif
-#ifndef H5_QUAD
-#define H5_QUAD 0                // h5conv: 1 = three-channel outputs share an accumulator between four pixel tiles (r4 A/B: the four weight sets push the
-                                  // kernel past 128 registers -- three instead of four workgroups per CU: 81 vs 64 us for the fused mix backward)
-#endif
-#ifndef H5_XCD
-#define H5_XCD 1                 // h5conv: XCD-contiguous strip order (0: round-robin; r4 A/B: no difference -- the halo rows two strips share come out of
-                                  // the memory-side cache either way)
 #endif
 
 namespace {
@@ -103,12 +87,9 @@ struct H5Cfg {
 // (round 6, config 4) uint8 frames into an fp16 tile WITHOUT conversions: v_perm_b32 places a byte under the exponent byte 0x3C (= 1 + b / 1024, exact),
 // one packed subtract of 1 leaves b / 1024 (as mask_infer_f16_kernel stages its frame tile, round 5); the 1024 / 255 goes into the layer's image
 // weights.  18 vector instructions per four pixels instead of ~60 (12 x byte extract + int -> float + scale + fp16 conversion, 4 packs).
-#ifndef H5_U8_PERM
-#define H5_U8_PERM 1
-#endif
 template <class C>
 __global__ void __launch_bounds__(256) h5conv_kernel(H5Params P) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(H5Params)>();
+    cgs_kernarg_prefetch<sizeof(H5Params)>();
     using EL = typename C::EL;
     using v8 = typename EL::V8; using v4 = typename EL::V4; using S = typename EL::S;
     constexpr int HW = C::HW, TH = C::TH, CA = C::CA, CB = C::CB, CO = C::CO, CIN = C::CIN, TPM = C::TPM, NM = C::NM, PW = C::PW, PH = C::PH;
@@ -121,10 +102,11 @@ __global__ void __launch_bounds__(256) h5conv_kernel(H5Params P) {
     //      PAIR (8 output channels, short K): the 16-wide output side of the instruction holds TWO pixel tiles -- tile h of a pair is
     //      multiplied by the weight set whose rows 8 h .. 8 h + 7 are the layer's (the other rows zero) into the SAME accumulator, so every
     //      lane of the epilogue carries a real output (the per-tile instruction count, not the matrix rate, bounds these kernels) ----
-    constexpr bool PAIR = CO == 8 && (CIN <= 8 || H5_PAIR16);
-    constexpr bool QUAD = CO == 3 && !C::POOL && H5_QUAD;           // three outputs: FOUR tiles per accumulator (tile h = rows 4 h .. 4 h + 2)
-    constexpr int NP = PAIR ? 2 : (QUAD ? 4 : 1);
-    const int ocl = PAIR ? (l15 & 7) : (QUAD ? (l15 & 3) : l15);
+    //      (r4 A/B: pairing also at 16-channel pixels costs 20 more weight registers and 0.8 % per config-5 step; three-channel outputs sharing an
+    //      accumulator between FOUR tiles push the kernel past 128 registers -- three instead of four workgroups per CU: 81 vs 64 us for the fused mix backward)
+    constexpr bool PAIR = CO == 8 && CIN <= 8;
+    constexpr int NP = PAIR ? 2 : 1;
+    const int ocl = PAIR ? (l15 & 7) : l15;
     v8 wa[NP][NM];
 #pragma unroll
     for (int h = 0; h < NP; ++h)
@@ -134,7 +116,7 @@ __global__ void __launch_bounds__(256) h5conv_kernel(H5Params P) {
         for (int j = 0; j < 8; ++j) {
             const int k = 8 * kq + j, tap = g * TPM + k / CIN, c = k % CIN;
             int idx = -1;
-            if (tap < 9 && (PAIR ? (l15 >> 3) == h : (QUAD ? (l15 >> 2) == h && ocl < CO : l15 < CO))) {
+            if (tap < 9 && (PAIR ? (l15 >> 3) == h : l15 < CO)) {
                 if constexpr (C::DGRAD) {       // d x[ci = O0 + oc] = sum over (tap', co) of dY[p + off(tap')][co] W[8 - tap'][ci][co]
                     if (c < C::COL) idx = ((8 - tap) * C::CIL + C::O0 + ocl) * C::COL + c;
                 } else {
@@ -145,8 +127,8 @@ __global__ void __launch_bounds__(256) h5conv_kernel(H5Params P) {
             // (unconditional load + select: `idx >= 0 ? P.w[idx] : 0` is a branch around the load, and every one of the 8 NM NP loads is then
             //  waited for before the next is issued -- up to 72 dependent L1 / L2 round trips at the start of every workgroup)
             const float wv = P.w[idx >= 0 ? idx : 0];
-            // (H5_U8_PERM: the uint8 frame's tile holds b / 1024, not b / 255)
-            const float wsc = (H5_U8_PERM && EL::IS_F16 && CA == 4 && CIN == 4 && !C::DGRAD && c < CA) ? 1024.f / 255.f : 1.f;
+            // (the fp16 instance's uint8 frame tile holds b / 1024, not b / 255)
+            const float wsc = (EL::IS_F16 && CA == 4 && CIN == 4 && !C::DGRAD && c < CA) ? 1024.f / 255.f : 1.f;
             wa[h][g][j] = EL::cvt(idx >= 0 ? wv * wsc : 0.f);
         }
     float br[4] = {0.f, 0.f, 0.f, 0.f};
@@ -154,7 +136,7 @@ __global__ void __launch_bounds__(256) h5conv_kernel(H5Params P) {
     if (P.bias) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int ch = PAIR ? (4 * kq + r) & 7 : (QUAD ? r : 4 * kq + r);
+            const int ch = PAIR ? (4 * kq + r) & 7 : 4 * kq + r;
             const float bv = P.bias[ch < CO ? ch : 0];
             br[r] = ch < CO ? bv : 0.f;
         }
@@ -171,8 +153,8 @@ __global__ void __launch_bounds__(256) h5conv_kernel(H5Params P) {
 
     for (int e = tid; e < XT / 8; e += 256) ((float4*)tile)[e] = f4zero();       // halo columns + padding channels: zero for every strip
 
-    // ---- staging, split: fetch = every global load of a strip issued back to back into registers (ONE memory round trip per strip, in
-    //      optionally -- H5_PREFETCH -- in flight while the previous strip multiplies), commit = conversion + LDS stores.  Items: source A = 4 frame pixels (3 dwords /
+    // ---- staging, split: fetch = every global load of a strip issued back to back into registers (ONE memory round trip per strip; issued a strip
+    //      ahead, r4 A/B at config 5: 1.048 vs 1.035 ms per step -- 40 more live registers), commit = conversion + LDS stores.  Items: source A = 4 frame pixels (3 dwords /
     //      3 float4), 4 fp32 pixels or 8 bf16 channels; source B = one low-resolution pixel (8 channels) -> the two tile pixels above it.
     constexpr int GW = HW / 4;
     constexpr int HP = HW / 2, PR = TH / 2 + 2;                                  // APOOL: pooled rows under a strip's tile
@@ -206,7 +188,7 @@ __global__ void __launch_bounds__(256) h5conv_kernel(H5Params P) {
                 const int g = e % GW, r = e / GW, y = row0 + r - 1;
                 const bool in = r < PH && y >= 0 && y < HW;
                 const size_t gi = in ? (((size_t)img * HW + y) * HW + g * 4) * 3 / 4 : 0;
-                if constexpr (H5_U8_PERM && EL::IS_F16 && CIN == 4) {      // (the fp16 instance: uint8 frames only, see commit below)
+                if constexpr (EL::IS_F16 && CIN == 4) {      // (the fp16 instance: uint8 frames only, see commit below)
                     const uint32_t* su = (const uint32_t*)P.a;
                     ra[i][0] = make_float4(__uint_as_float(su[gi]), __uint_as_float(su[gi + 1]), __uint_as_float(su[gi + 2]), 0.f);
                 } else if (P.a_f32 == 2) {             // virtual mixes (main.py:395,406): image img < n / 2 = A (1 - Z) + Z B of frame pair img, else B (1 - Z) + Z A
@@ -301,7 +283,7 @@ __global__ void __launch_bounds__(256) h5conv_kernel(H5Params P) {
                 const int g = e % GW, r = e / GW, y = row0 + r - 1;
                 if (r >= PH) continue;
                 const bool in = y >= 0 && y < HW;
-                if constexpr (H5_U8_PERM && EL::IS_F16 && CIN == 4) {
+                if constexpr (EL::IS_F16 && CIN == 4) {
                     {          // four uint8 pixels = three dwords -> four (r, g, b, 0) half quadruples (the fp16 instance only ever reads uint8 frames:
                                // cgs_f16_enc0_fwd; a run-time test of P.a_f32 here kept both forms' registers alive: 128 instead of 120, three waves per SIMD)
                         typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
@@ -386,15 +368,13 @@ __global__ void __launch_bounds__(256) h5conv_kernel(H5Params P) {
         }
     };
 
-    const int vb = H5_XCD ? cgs_xcd_contiguous(blockIdx.x, gridDim.x) : (int)blockIdx.x;   // neighbouring strips (shared halo rows) on one XCD's L2
-    if (H5_PREFETCH && vb < P.nstrips) fetch(vb);
+    const int vb = cgs_xcd_contiguous(blockIdx.x, gridDim.x);   // neighbouring strips (shared halo rows) on one XCD's L2 (r4 A/B against round-robin: no difference)
     __syncthreads();                                                             // (the zeroes above, before other threads stage the same addresses)
     for (int strip = vb; strip < P.nstrips; strip += gridDim.x) {
     const int img = strip / STRIPS, row0 = (strip % STRIPS) * TH;
-    if (!H5_PREFETCH) fetch(strip);
+    fetch(strip);
     commit(strip);
     __syncthreads();
-    if (H5_PREFETCH && strip + (int)gridDim.x < P.nstrips) fetch(strip + gridDim.x);   // in flight while this strip multiplies
 
     // ---- tiles: 16 pixels = 4 pool windows adjacent in x (lane = 4 window + position), or 16 consecutive pixels of a row ----
     auto tile_pixel = [&](int t, int& y, int& x) {      // strip-local pixel of this lane in tile t
@@ -460,8 +440,8 @@ __global__ void __launch_bounds__(256) h5conv_kernel(H5Params P) {
             }
         } else if (NP > 1 || 4 * kq < CO) {
             int y, x;
-            tile_pixel(t + (PAIR ? kq >> 1 : (QUAD ? kq : 0)), y, x);            // the tile this lane's rows belong to
-            const size_t o = ((((size_t)img * HW + row0 + y) * HW + x) * CO) + (PAIR ? 4 * (kq & 1) : (QUAD ? 0 : 4 * kq));
+            tile_pixel(t + (PAIR ? kq >> 1 : 0), y, x);            // the tile this lane's rows belong to
+            const size_t o = ((((size_t)img * HW + row0 + y) * HW + x) * CO) + (PAIR ? 4 * (kq & 1) : 4 * kq);
             float v[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -545,7 +525,7 @@ using H5Dec1DL = H5Cfg< 32, 32,  8, 0,  8, 16,  8, 8, true,  EPI_POOLSUM,   CGS_
 
 extern "C" int cgs_f16_enc0_fwd(int32_t n, const uint8_t* x_u8, const float* w_hwio, const float* bias, void* e0_f16, cgs_stream_t stream) {
     if (n < 0 || !x_u8 || !w_hwio || !bias || !e0_f16) return CGS_ERR_BADARG;
-    return h5_launch<H4Enc0F>(H5Params{x_u8, nullptr, w_hwio, bias, e0_f16, nullptr, nullptr, n, 0, 0 /* a_f32: this instance reads uint8 frames only (H5_U8_PERM) */}, (hipStream_t)stream);
+    return h5_launch<H4Enc0F>(H5Params{x_u8, nullptr, w_hwio, bias, e0_f16, nullptr, nullptr, n, 0, 0 /* a_f32: this instance reads uint8 frames only */}, (hipStream_t)stream);
 }
 
 extern "C" int cgs_f16_enc1_fwd(int32_t n, const void* e0_f16, const float* w_hwio, const float* bias, float* e1_f32, cgs_stream_t stream) {

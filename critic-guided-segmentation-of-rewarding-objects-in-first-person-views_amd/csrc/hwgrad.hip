@@ -13,9 +13,6 @@
 // No reference counterpart (the reference cannot run 128x128 frames): parity unpinned, see hourglass128.py.
 #include "tail_common.h"
 
-#ifndef HWG_XCD
-#define HWG_XCD 1                // XCD-contiguous strip order (0: round-robin; r4 A/B)
-#endif
 
 namespace {
 
@@ -47,7 +44,7 @@ struct HWgParams {
 // DYPOOL: dY = a pooled gradient re-expanded while it is staged (the gradient goes where the forward maximum was): replaces cgs_bf16_pool_expand
 template <int HW, int CA, int CB, int CO, int TH, bool DYPOOL = false>
 __global__ void __launch_bounds__(256) hwgrad_kernel(HWgParams P) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(HWgParams)>();
+    cgs_kernarg_prefetch<sizeof(HWgParams)>();
     constexpr int CIN = CA + CB <= 4 ? 4 : (CA + CB <= 8 ? 8 : 16);             // channels of the LDS pixel
     constexpr int TPB = 16 / CIN, NB = (9 + TPB - 1) / TPB;                     // taps per 16-row block, row blocks
     constexpr int CA_REAL = CA == 4 ? 3 : CA, CI = CA_REAL + CB;
@@ -77,7 +74,7 @@ __global__ void __launch_bounds__(256) hwgrad_kernel(HWgParams P) {
     for (int e = tid; e < XT / 8; e += 256) ((float4*)xt)[e] = f4zero();        // halo columns + padding channels: zero for every strip
     __syncthreads();                                                            // (before other threads stage the same addresses)
 
-    for (int strip = HWG_XCD ? cgs_xcd_contiguous(blockIdx.x, gridDim.x) : (int)blockIdx.x; strip < P.nstrips; strip += gridDim.x) {   // (neighbouring strips on one XCD's L2)
+    for (int strip = cgs_xcd_contiguous(blockIdx.x, gridDim.x); strip < P.nstrips; strip += gridDim.x) {   // (neighbouring strips on one XCD's L2)
         const int img = strip / STRIPS, row0 = (strip % STRIPS) * TH;
         // ---- staging: EVERY global load of the strip is issued back to back into registers (compile-time trip counts), then converted and stored
         //      to LDS: one memory round trip per strip instead of one per 256 items (these kernels multiply for well under a microsecond per

@@ -11,7 +11,7 @@ extern "C" int dbg_maskfwd_stamps(unsigned long long* stamps) { g_maskfwd_stamps
 
 template <int SRC>     // SRC_U8C3 / SRC_F32C3
 __global__ void __launch_bounds__(256, SRC == SRC_U8C3 ? 2 : 1) mask_fwd_kernel(MaskFwdParams P) {     // (fp32 frames: 9 more staging registers per pixel group than uint8 -- at two workgroups per SIMD they spilled 16 VGPRs)
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(MaskFwdParams)>();
+    cgs_kernarg_prefetch<sizeof(MaskFwdParams)>();
     __shared__ __attribute__((aligned(16))) float4 stage4[kMaskStageF4];
     __shared__ float win[kMaskWinFloats];      // [slot][window element][quad column]: lane-contiguous, conflict-free
     __shared__ float zred[8];

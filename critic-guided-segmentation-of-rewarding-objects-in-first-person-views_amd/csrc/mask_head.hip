@@ -8,8 +8,8 @@
 //                  = sum_{u,v in 0..3} sum_oc dH[2q + (u-1, v-1)][oc] * W4[u][v][oc][c],
 //       W4[u][v][oc][c] = sum_{a in {0,1}, ky = a+2-u in 0..2} sum_{b in {0,1}, kx = b+2-v in 0..2} W[ky][kx][3+c][oc]
 //     i.e. one stride-2 4x4 convolution (16 taps per output) instead of four 3x3 ones (36 taps): 2.25x fewer MACs;
-//     GEMM: M = 16 PAIRS of horizontally adjacent low-res pixels, N = 2 x 8 channels (one column block per pixel of the
-//     pair, no padding columns), K = 4 x 6 window positions (the union of the two 4x4 windows) x 16 channels,
+//     on v_mfma_f32_4x4x1 with lane = low-resolution pixel: 16 window positions x 16 channels x 2 output-channel groups
+//     (mask_head_matrix, round 6; the earlier GEMM over PAIRS of pixels multiplied a third zero weights),
 //   * masker.0 weight gradient (optional): implicit GEMM over the pixels with dH read straight from the LDS tile it was
 //     rebuilt into.  Rows: 27 image (tap, channel) rows + the bias row, and for the 8 upsampled channels the FOLDED rows:
 //     per pixel parity (py, px) the 9 taps over the upsampled o0 hit only a 2x2 neighbourhood (a, b) of o0 itself, so
@@ -48,26 +48,11 @@ extern "C" int dbg_mask_head_stamps(unsigned long long* stamps) { g_mh_stamps = 
 #endif
 
 // (round 5's MH_IMG4 / MH_CVT32 staging variants of the matrix waves -- each measured +1 us -- went out with round 6's move of the staging to the builder waves)
-#ifndef MH_WACC_PK
-#define MH_WACC_PK 1
-#endif
-#ifndef MH_APK
-#define MH_APK 1       // (round 6) builder: dH's four channel sums as v_pk_fma_f32 pairs
-#endif
-#ifndef MH_INTERLEAVE
-#define MH_INTERLEAVE 1
-#endif
-#ifndef MH_DGRAD4
-#define MH_DGRAD4 1    // (round 6) masker.0's data gradient on v_mfma_f32_4x4x1 with lane = low-resolution pixel (no padded window positions): see mask_head_matrix
-#endif
-#ifndef MH_DZWIN
-#define MH_DZWIN 1     // (round 6) builder: rolling 3x3 dzpre window in registers (36 instead of 100 LDS reads per tile and thread)
-#endif
 template <int TH, bool W0>
 struct MHeadGeo {
     static constexpr int H = 64, W = 64, TRA = TH + 2, PW = W + 2, PS = 17, DZW = W + 4, DZR = TH + 4, STRIPS = H / TH;
     static constexpr int XT = TRA * PW * PS, DZ = DZR * DZW;
-    static constexpr int W4P = MH_DGRAD4 ? 16 * 16 * 8 : 24 * 16 * 16;  // folded masker.0 weights: [4x4 pos][oc][8] (MH_DGRAD4) / pair-folded [4x6 pos][oc][2x8]
+    static constexpr int W4P = 16 * 16 * 8;                            // folded masker.0 weights: [4x4 pos][oc][8]
     static constexpr int LR = TH / 2 + 2, LC = W / 2 + 2;              // o0 tile at its own resolution
     static constexpr int XIMG = W0 ? TRA * PW * 4 : 0, XO = W0 ? LR * LC * 8 : 0;   // masker.0 inputs (image [r,g,b,0])
     // (round 6) ONE workgroup barrier per tile: the dzpre tile and masker.0's input tiles are double buffered like the dH tile, so the builder
@@ -100,21 +85,11 @@ __device__ __forceinline__ void mask_head_builder(const MHeadParams& P, const MH
     const int bx = btid >> 2, bx4 = btid;      // this thread's pixel column (every item) and its float4 index within a row (= 4 bx + pl)
     auto tile_of = [&](int i) { return bid + (i < T ? i : T - 1) * grid; };   // clamped: prefetches past the end re-read
 
-    float w2r[9][4];
-#if MH_APK
     typedef float mh_f2 __attribute__((ext_vector_type(2)));
-    mh_f2 w2p[9][2];
-#endif
-    // masker.2 weight-gradient partials of this thread (plane pl).  MH_WACC_PK: held as register PAIRS and pinned as pairs, so that their FMAs are
-    // v_pk_fma_f32 (the per-scalar pins below left them as 288 v_fmac_f32 per tile; round 5)
-#if MH_WACC_PK
-#if !MH_APK
-    typedef float mh_f2 __attribute__((ext_vector_type(2)));
-#endif
+    mh_f2 w2p[9][2];       // masker.2's weights of plane pl, as register pairs
+    // masker.2 weight-gradient partials of this thread (plane pl): held as register PAIRS and pinned as pairs, so that their FMAs are
+    // v_pk_fma_f32 (pinned per scalar they were 288 v_fmac_f32 per tile; round 5)
     mh_f2 wacc[9][2];
-#else
-    float wacc[9][4];
-#endif
     float bacc = 0.f;
     float4 hvs[IT];
     float dzr[DIT];
@@ -122,15 +97,8 @@ __device__ __forceinline__ void mask_head_builder(const MHeadParams& P, const MH
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            w2r[t][c] = P.w2[t * 16 + 4 * pl + c];
-#if MH_APK
-            w2p[t][c >> 1][c & 1] = w2r[t][c];
-#endif
-#if MH_WACC_PK
+            w2p[t][c >> 1][c & 1] = P.w2[t * 16 + 4 * pl + c];
             wacc[t][c >> 1][c & 1] = 0.f;
-#else
-            wacc[t][c] = 0.f;
-#endif
         }
 
     // loads = address arithmetic + the load only; masking happens where the value is consumed (a select here would
@@ -249,11 +217,6 @@ __device__ __forceinline__ void mask_head_builder(const MHeadParams& P, const MH
             load_dz(tile_of(i + 1));      // in flight during the rebuild
             if constexpr (W0) fetch_x(tile);               // committed in the next phase 1
             __builtin_amdgcn_sched_barrier(0);
-#ifdef MH_WHATIF_NOBUILD
-            if (P.n < 0)
-#endif
-            {
-#if MH_DZWIN
             // (round 6) the 3x3 dzpre window of item `it` is rows it .. it+2, columns x+1 .. x+3 of the dz tile: consecutive items share two of the
             // three rows.  All 12 x 3 values of the tile are read up front (36 LDS reads instead of 100, ONE latency instead of one per item; the
             // compiler cannot do this itself: the dH stores between the items may alias dz).
@@ -263,7 +226,6 @@ __device__ __forceinline__ void mask_head_builder(const MHeadParams& P, const MH
 #pragma unroll
                 for (int cc = 0; cc < 3; ++cc) dzw[rr][cc] = dz[rr * DZW + bx + 1 + cc];
             __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
             for (int it = 0; it < IT; ++it) {
                 const int r = it;
@@ -273,64 +235,31 @@ __device__ __forceinline__ void mask_head_builder(const MHeadParams& P, const MH
                 const float4 hv = hvs[it];
                 const bool own = it >= 1 && it <= TH;       // rows owned by this strip (halo rows: the neighbours')
                 const float4 hw_ = own ? hv : f4zero();
-#if MH_APK
                 // (round 6) the four channel sums as two register pairs: v_pk_fma_f32 (same fused arithmetic per component: same bits)
                 mh_f2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
-#else
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#endif
 #pragma unroll
                 for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
                     for (int kx = 0; kx < 3; ++kx) {
-#if MH_DZWIN
-                        float d = dzw[r + 2 - ky][2 - kx];
-#else
-                        float d = dz[(r + 2 - ky) * DZW + x + 3 - kx];
-#endif
-#if MH_APK
-                        {
-                            const mh_f2 dd = {d, d};
-                            a01 = __builtin_elementwise_fma(dd, w2p[ky * 3 + kx][0], a01);
-                            a23 = __builtin_elementwise_fma(dd, w2p[ky * 3 + kx][1], a23);
-                        }
-#else
-                        a0 = fmaf(d, w2r[ky * 3 + kx][0], a0); a1 = fmaf(d, w2r[ky * 3 + kx][1], a1);
-                        a2 = fmaf(d, w2r[ky * 3 + kx][2], a2); a3 = fmaf(d, w2r[ky * 3 + kx][3], a3);
-#endif
+                        const float d = dzw[r + 2 - ky][2 - kx];
+                        const mh_f2 dd = {d, d};
+                        a01 = __builtin_elementwise_fma(dd, w2p[ky * 3 + kx][0], a01);
+                        a23 = __builtin_elementwise_fma(dd, w2p[ky * 3 + kx][1], a23);
                         if (WG && it != 0 && it != IT - 1) {     // items 0 and IT-1 are the halo rows: never owned
-#if MH_WACC_PK
-                            const mh_f2 dd = {d, d};
                             wacc[ky * 3 + kx][0] = __builtin_elementwise_fma(dd, mh_f2{hw_.x, hw_.y}, wacc[ky * 3 + kx][0]);
                             wacc[ky * 3 + kx][1] = __builtin_elementwise_fma(dd, mh_f2{hw_.z, hw_.w}, wacc[ky * 3 + kx][1]);
-#else
-                            wacc[ky * 3 + kx][0] = fmaf(d, hw_.x, wacc[ky * 3 + kx][0]);
-                            wacc[ky * 3 + kx][1] = fmaf(d, hw_.y, wacc[ky * 3 + kx][1]);
-                            wacc[ky * 3 + kx][2] = fmaf(d, hw_.z, wacc[ky * 3 + kx][2]);
-                            wacc[ky * 3 + kx][3] = fmaf(d, hw_.w, wacc[ky * 3 + kx][3]);
-#endif
                         }
                     }
-#if MH_APK
                 const float a0 = a01[0], a1 = a01[1], a2 = a23[0], a3 = a23[1];
-#endif
                 static_assert(IT == TH + 2, "one item per tile row: item index == row index");
                 if (WG && it != 0 && it != IT - 1) {
-#if MH_DZWIN
                     bacc += (own && pl == 0) ? dzw[r + 1][1] : 0.f;
-#else
-                    bacc += (own && pl == 0) ? dz[(r + 1) * DZW + x + 2] : 0.f;
-#endif
                     // pin the accumulators here: otherwise their FMAs are sunk past the whole item loop and every dz / h
                     // value of all items stays live (hundreds of registers)
 #pragma unroll
                     for (int t = 0; t < 9; ++t)
 #pragma unroll
-#if MH_WACC_PK
                         for (int c = 0; c < 2; ++c) asm volatile("" : "+v"(wacc[t][c]));
-#else
-                        for (int c = 0; c < 4; ++c) asm volatile("" : "+v"(wacc[t][c]));
-#endif
                 }
                 float4 v = make_float4(a0 * (hv.x > 0.f ? 1.f : 0.01f), a1 * (hv.y > 0.f ? 1.f : 0.01f),
                                        a2 * (hv.z > 0.f ? 1.f : 0.01f), a3 * (hv.w > 0.f ? 1.f : 0.01f));
@@ -339,7 +268,6 @@ __device__ __forceinline__ void mask_head_builder(const MHeadParams& P, const MH
                 d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
                 if (own && P.dh) ((float4*)P.dh)[gi] = v;
                 __builtin_amdgcn_sched_barrier(0);
-            }
             }
             load_h(tile_of(i + 1));       // in flight until the next rebuild (requested at the START of this rebuild into a second register set, it
                                           // measured no faster: the rebuild does not wait for memory)
@@ -367,11 +295,7 @@ __device__ __forceinline__ void mask_head_builder(const MHeadParams& P, const MH
         for (int t = 0; t < 9; ++t)
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-#if MH_WACC_PK
                 float v = wacc[t][c >> 1][c & 1];
-#else
-                float v = wacc[t][c];
-#endif
                 v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
                 if (lane < 4) red2[(wave * 4 + lane) * 37 + t * 4 + c] = v;
             }
@@ -411,19 +335,17 @@ __device__ __forceinline__ void mask_head_matrix(const MHeadParams& P, const MHe
     }
     const float m1 = (16 + l15 < 27) ? 1.f : 0.f, m0 = (16 + l15 == 27) ? 1.f : 0.f;   // second row block: valid / bias / pad
 
-    // MH_DGRAD4 (round 6): the data gradient  d_o0[q][c] = sum_{u,v < 4} sum_oc dH[2 q + (u - 1, v - 1)][oc] W4[u][v][oc][c]  with lane = low-resolution
+    // (round 6) the data gradient  d_o0[q][c] = sum_{u,v < 4} sum_oc dH[2 q + (u - 1, v - 1)][oc] W4[u][v][oc][c]  with lane = low-resolution
     // pixel q on v_mfma_f32_4x4x1 (A = four output-channel weights broadcast from block abid = oc of weight register (u, v), B = the lane's dH value):
     // 256 (position, oc) steps x 2 channel groups = 512 instructions of 8 cycles per 64 pixels = 2048 matrix cycles per low-resolution row, where the
     // pair form (16 pairs x 2 x 8 columns, K = the 4 x 6 union window: a third of it zero weights) ran 96 x 32 = 3072.  Waves 0 / 1 take two
     // low-resolution rows each (64 lanes = 64 pixels) and a smaller share of the weight gradient's chunks, waves 2 / 3 the larger share.
-    [[maybe_unused]] float w4r[2][16];
-    if constexpr (MH_DGRAD4) {
-        if (mwave < 2) {
+    float w4r[2][16];
+    if (mwave < 2) {
 #pragma unroll
-            for (int g = 0; g < 2; ++g)
+        for (int g = 0; g < 2; ++g)
 #pragma unroll
-                for (int k = 0; k < 16; ++k) w4r[g][k] = L.w4p[(k * 16 + (lane >> 2)) * 8 + 4 * g + (lane & 3)];
-        }
+            for (int k = 0; k < 16; ++k) w4r[g][k] = L.w4p[(k * 16 + (lane >> 2)) * 8 + 4 * g + (lane & 3)];
     }
     [[maybe_unused]] unsigned long long tp = MH_T(), s_p1 = 0, s_w1 = 0, s_dg = 0, s_wg = 0, s_w2 = 0, tm = 0;
     __syncthreads();                                       // (the builders' once-per-workgroup barrier behind tile 0's dzpre)
@@ -441,94 +363,32 @@ __device__ __forceinline__ void mask_head_matrix(const MHeadParams& P, const MHe
             // in order, so reads placed after a group's MFMAs would only start once the last of them has issued and the
             // matrix pipe would idle for a full LDS round trip per group.  A group must stay below 16 LDS instructions:
             // s_waitcnt lgkmcnt counts to 15, so "wait for the previous group only" is not expressible beyond that.
-#ifdef MH_WHATIF_NODGRAD
-            if (P.n < 0)
-#endif
-            if constexpr (MH_DGRAD4) {
-                if (mwave < 2) {
-                    const int qyl = 2 * mwave + (lane >> 5), qx = lane & 31;
-                    const float* bp = xt + ((2 * qyl) * PW + 2 * qx) * PS;      // window position (0, 0) of this lane's pixel, channel 0
-                    frag4 d0 = frag4{0.f, 0.f, 0.f, 0.f}, d1 = frag4{0.f, 0.f, 0.f, 0.f};
-                    float bv[2][16];
-                    auto ldp = [&](int k, int buf) {                           // the 16 channels of window position k = (u, v)
+            if (mwave < 2) {
+                const int qyl = 2 * mwave + (lane >> 5), qx = lane & 31;
+                const float* bp = xt + ((2 * qyl) * PW + 2 * qx) * PS;      // window position (0, 0) of this lane's pixel, channel 0
+                frag4 d0 = frag4{0.f, 0.f, 0.f, 0.f}, d1 = frag4{0.f, 0.f, 0.f, 0.f};
+                float bv[2][16];
+                auto ldp = [&](int k, int buf) {                           // the 16 channels of window position k = (u, v)
 #pragma unroll
-                        for (int oc = 0; oc < 16; ++oc) bv[buf][oc] = bp[((k >> 2) * PW + (k & 3)) * PS + oc];
-                    };
-                    ldp(0, 0);
-                    static_for<16>([&](auto K) {
-                        constexpr int k = decltype(K)::value;
-                        if constexpr (k + 1 < 16) ldp(k + 1, (k + 1) & 1);
-                        __builtin_amdgcn_sched_barrier(0);
-                        static_for<16>([&](auto OC) {
-                            constexpr int oc = decltype(OC)::value;
-                            d0 = __builtin_amdgcn_mfma_f32_4x4x1f32(w4r[0][k], bv[k & 1][oc], d0, 4, oc, 0);
-                            d1 = __builtin_amdgcn_mfma_f32_4x4x1f32(w4r[1][k], bv[k & 1][oc], d1, 4, oc, 0);
-                        });
-                        __builtin_amdgcn_sched_barrier(0);
-                    });
-                    float4* o = (float4*)(P.d_o0 + ((size_t)(n0 * 32 + row0 / 2 + qyl) * 32 + qx) * 8);
-                    o[0] = make_float4(d0[0], d0[1], d0[2], d0[3]);
-                    o[1] = make_float4(d1[0], d1[1], d1[2], d1[3]);
-                }
-            } else {
-                // data gradient of low-res row qyl = mwave: lane pair i = l15 covers low-res pixels 2i (columns 0-7 of the
-                // tile) and 2i+1 (columns 8-15); window = rows 2qyl-1..2qyl+2, columns 4i-1..4i+4 of dH
-                const int qyl = mwave;
-                const int abase = ((2 * qyl) * PW + 4 * l15) * PS + kq;
-                const float* wb = L.w4p + kq * 16 + l15;          // B: w4p[(pos*16 + 4*plane + kq)*16 + l15]
-                // TWO accumulation chains (even / odd k-steps, added once at the end): v_mfma_f32_16x16x4_f32 issues every 32 cycles but a
-                // dependent one only after 40 (cdna_hip_programming.md, "FP32-input MFMA"), and this role is the SIMD's only MFMA wave
-                // (round 6: 96 x 8 cycles per tile)
-                frag4 d = frag4{0.f, 0.f, 0.f, 0.f}, d1 = frag4{0.f, 0.f, 0.f, 0.f};
-                constexpr int GS = 12, NG = 96 / GS;              // 24 dwords = 12 ds_read2 per group
-                float av[2][GS], bw[2][GS];
-                auto ld = [&](int g, int buf) {
-#pragma unroll
-                    for (int j = 0; j < GS; ++j) {
-                        const int s = g * GS + j, pos = s >> 2, u = pos / 6, v6 = pos % 6;
-                        av[buf][j] = xt[abase + (u * PW + v6) * PS + 4 * (s & 3)];
-                        bw[buf][j] = wb[s * 64];
-                    }
+                    for (int oc = 0; oc < 16; ++oc) bv[buf][oc] = bp[((k >> 2) * PW + (k & 3)) * PS + oc];
                 };
-                ld(0, 0);
-                __builtin_amdgcn_sched_barrier(0);        // (group 0's reads all issue before its first MFMA: they must not be dealt out between them)
-#pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    if (g + 1 < NG) ld(g + 1, (g + 1) & 1);
-#if !MH_INTERLEAVE
+                ldp(0, 0);
+                static_for<16>([&](auto K) {
+                    constexpr int k = decltype(K)::value;
+                    if constexpr (k + 1 < 16) ldp(k + 1, (k + 1) & 1);
                     __builtin_amdgcn_sched_barrier(0);
-#endif
-#pragma unroll
-                    for (int j = 0; j < GS; j += 2) {
-                        d = __builtin_amdgcn_mfma_f32_16x16x4f32(av[g & 1][j], bw[g & 1][j], d, 0, 0, 0);
-                        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[g & 1][j + 1], bw[g & 1][j + 1], d1, 0, 0, 0);
-                    }
-#if MH_INTERLEAVE
-                    // (round 6) the next group's operand reads are issued BETWEEN this group's MFMAs (one LDS instruction per matrix instruction:
-                    // a matrix instruction keeps the pipe busy for 32 cycles, the wave is free to issue meanwhile) instead of in front of them,
-                    // where their issue time was a gap in the matrix pipe once per group
-                    if (g + 1 < NG) {
-#pragma unroll
-                        for (int j = 0; j < GS; ++j) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                        }
-                    } else {
-                        __builtin_amdgcn_sched_group_barrier(0x008, GS, 0);
-                    }
-#endif
+                    static_for<16>([&](auto OC) {
+                        constexpr int oc = decltype(OC)::value;
+                        d0 = __builtin_amdgcn_mfma_f32_4x4x1f32(w4r[0][k], bv[k & 1][oc], d0, 4, oc, 0);
+                        d1 = __builtin_amdgcn_mfma_f32_4x4x1f32(w4r[1][k], bv[k & 1][oc], d1, 4, oc, 0);
+                    });
                     __builtin_amdgcn_sched_barrier(0);
-                }
-                d += d1;
-                // D[row = pair 4kq + j][col = l15 = 8*(pixel of the pair) + channel]: 16 contiguous floats per pair
-                float* o = P.d_o0 + ((size_t)(n0 * 32 + row0 / 2 + qyl) * 32 + 2 * (4 * kq)) * 8 + l15;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j * 16] = d[j];
+                });
+                float4* o = (float4*)(P.d_o0 + ((size_t)(n0 * 32 + row0 / 2 + qyl) * 32 + qx) * 8);
+                o[0] = make_float4(d0[0], d0[1], d0[2], d0[3]);
+                o[1] = make_float4(d1[0], d1[1], d1[2], d1[3]);
             }
             if (CGS_STAMP_PTR(P.dbg)) tm = MH_T();
-#ifdef MH_WHATIF_NOWGRAD
-            if (P.n < 0)
-#endif
             if constexpr (W0) {
                 // weight gradient: this wave's rows 2*mwave (py = 0) and 2*mwave + 1 (py = 1); a k-step = 4 same-parity
                 // pixels x = 2*(4s + kq) + px of one row.  Chunk = (py, px, two k-steps): 5 ds_read2 + 8 MFMAs.
@@ -538,8 +398,8 @@ __device__ __forceinline__ void mask_head_matrix(const MHeadParams& P, const MHe
                 const int ob = kq * 8 + l15;                               // o0: ((rp+a+py)*LC + 4s + kq + b + px)*8 + cb
                 float ai[2][UU][2], ao[2][UU][2], b[2][UU];
                 // A HALF = the 8 chunks (px = 0 / 1, s0 = 0, 2, 4, 6) of one row (row pair rp, row parity py): 64 matrix instructions.  The tile's 8
-                // halves hh = 2 rp + py are dealt to the waves: two each, or -- MH_DGRAD4: waves 0 / 1 also carry the data gradient (4096 matrix
-                // cycles) -- 1 / 1 / 3 / 3, so every wave issues 6144 matrix cycles per tile.  py is a template value of the half (the accumulator
+                // halves hh = 2 rp + py are dealt to the waves 1 / 1 / 3 / 3 -- waves 0 / 1 also carry the data gradient (4096 matrix cycles) --
+                // so every wave issues 6144 matrix cycles per tile.  py is a template value of the half (the accumulator
                 // arrays must be indexed statically), chosen by a wave-uniform branch.
                 auto do_half = [&](int rp, auto PY) {
                     constexpr int py = decltype(PY)::value;
@@ -576,8 +436,8 @@ __device__ __forceinline__ void mask_head_matrix(const MHeadParams& P, const MHe
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 };
-                const int h_lo = MH_DGRAD4 ? (mwave < 2 ? mwave : 2 + 3 * (mwave - 2)) : 2 * mwave;
-                const int h_n = MH_DGRAD4 ? (mwave < 2 ? 1 : 3) : 2;
+                const int h_lo = mwave < 2 ? mwave : 2 + 3 * (mwave - 2);
+                const int h_n = mwave < 2 ? 1 : 3;
 #pragma unroll 1
                 for (int hh = h_lo; hh < h_lo + h_n; ++hh) {
                     if (hh & 1) do_half(hh >> 1, std::integral_constant<int, 1>{});
@@ -617,7 +477,7 @@ __device__ __forceinline__ void mask_head_matrix(const MHeadParams& P, const MHe
 // WG: produce slab2; W0: produce slab0 (needs img/o0); SRC: WSRC_U8 / WSRC_F32 image
 template <int TH, bool WG, bool W0, int SRC>
 __global__ void __launch_bounds__(512) mask_head_kernel(MHeadParams P) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(MHeadParams)>();
+    cgs_kernarg_prefetch<sizeof(MHeadParams)>();
     using G = MHeadGeo<TH, W0>;
     constexpr int TRA = G::TRA, PW = G::PW, PS = G::PS;
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
@@ -625,7 +485,7 @@ __global__ void __launch_bounds__(512) mask_head_kernel(MHeadParams P) {
     L.xt0 = (float*)smem;              // dH tiles [2][TRA][PW][PS]
     L.ximg = L.xt0 + 2 * G::XT;        // masker.0 image tiles [2][TRA][PW][r,g,b,0] (W0)
     L.xo = L.ximg + 2 * G::XIMG;       // masker.0 low-resolution input tiles [2][LR][LC][8] (W0)
-    L.w4p = L.xo + 2 * G::XO;          // pair-folded weights [u 0..3][v6 0..5][oc][8*g + c]
+    L.w4p = L.xo + 2 * G::XO;          // folded weights [u 0..3][v 0..3][oc][c]
     L.dz = L.w4p + G::W4P;             // dzpre tiles [2] with a 2-pixel halo
     const int tid = threadIdx.x;
     [[maybe_unused]] const unsigned long long t_start = MH_T();
@@ -636,12 +496,8 @@ __global__ void __launch_bounds__(512) mask_head_kernel(MHeadParams P) {
     static_assert(G::W4P % 512 == 0 && G::W4P / 512 <= 12, "table rounds");
     {
         float wv[G::W4P / 512][4];
-        // entry e -> (window position (u, v), oc, output column): MH_DGRAD4: [pos 4x4][oc][c];  else pair-folded [pos 4x6][oc][8 g + c], pixel g of the
-        // pair sees window column v6 as v = v6 - 2 g
-        auto decode = [&](int e, int& u, int& v, int& oc, int& c) {
-            if constexpr (MH_DGRAD4) { c = e & 7; oc = (e >> 3) & 15; const int pos = e >> 7; u = pos >> 2; v = pos & 3; }
-            else { const int col = e & 15, pos = e >> 8; oc = (e >> 4) & 15; u = pos / 6; c = col & 7; v = pos % 6 - 2 * (col >> 3); }
-        };
+        // entry e -> (window position (u, v), oc, output column): [pos 4x4][oc][c]
+        auto decode = [&](int e, int& u, int& v, int& oc, int& c) { c = e & 7; oc = (e >> 3) & 15; const int pos = e >> 7; u = pos >> 2; v = pos & 3; };
 #pragma unroll
         for (int k = 0; k < G::W4P / 512; ++k) {
             int u, v, oc, c;

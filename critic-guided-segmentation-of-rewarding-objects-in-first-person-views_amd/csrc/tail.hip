@@ -81,20 +81,6 @@ extern "C" int dbg_tail_stamps(unsigned long long* stamps) { g_tail_stamps = sta
 // ------------------------------------------------------------------------------------------------
 // encoder tail + critic head, forward
 // ------------------------------------------------------------------------------------------------
-// s_sleep units (x 64 cycles) of the phase stagger in the fused critic forward, the fused decoder forward and the fused decoder backward (cgs_stagger;
-// 0 = none).  Round 4 shipped 127 in all three (-5 us then); after round 5's instruction-level passes the same A/B reads the other way.
-#ifndef CGS_TAIL_STAGGER
-#define CGS_TAIL_STAGGER 0
-#endif
-#ifndef CGS_STAGGER_ENC_FWD
-#define CGS_STAGGER_ENC_FWD CGS_TAIL_STAGGER
-#endif
-#ifndef CGS_STAGGER_DEC_FWD
-#define CGS_STAGGER_DEC_FWD CGS_TAIL_STAGGER
-#endif
-#ifndef CGS_STAGGER_DEC_BWD
-#define CGS_STAGGER_DEC_BWD CGS_TAIL_STAGGER
-#endif
 struct TailEncFwdParams {
     cgs_tail_enc_weights w;
     const float* e1;
@@ -127,7 +113,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     __shared__ __attribute__((aligned(16))) float xs[256];               // dropout(e3), flat NHWC
     __shared__ __attribute__((aligned(16))) float red[8][32];          // (also: the 64 float4 Dropout multipliers of e3 between stages 3 and 4)
     __shared__ float es[32], hs[32];                                    // hs: the 32 Dropout multipliers of h1 (stage 3 -> stage 10)
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailEncFwdParams) + 2 * sizeof(ConvParams)>();
+    cgs_kernarg_prefetch<sizeof(TailEncFwdParams) + 2 * sizeof(ConvParams)>();
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if constexpr (FUSED && ENC0 == 1) {
         if ((int)blockIdx.x == P.nblocks) {          // the rider workgroup (launched only when m0_pack is given): see tail_dec_fwd_kernel
@@ -143,22 +129,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     if constexpr (!FUSED) {
         if (img < P.n) { pe[0] = ((const float4*)P.e1)[(size_t)img * 512 + tid]; pe[1] = ((const float4*)P.e1)[(size_t)img * 512 + tid + 256]; }
     }
-#if CGS_DROPCTX3
     DropCtx d2, d3, dh;
     drop_ctx3(P.drop_e2, P.drop_e3, P.drop_h1, P.w.b6, d2, d3, dh);
-#else
-    const DropCtx d2 = drop_ctx(P.drop_e2, P.w.b6), d3 = drop_ctx(P.drop_e3, P.w.b6), dh = drop_ctx(P.drop_h1, P.w.b6);
-#endif
 
     // ---- once per workgroup: halos -> 0, conv weights -> registers (features.6: both channel groups; features.10: this wave's
     //      four output channels), head weights -> registers ----
     tilep_zero<X1P>(x1, tid);
     tilep_zero<X2P>(x2, tid);
     if constexpr (FUSED) {
-        // every other co-resident workgroup starts ~4 us late: its neighbours' latency-bound tail stages then run under its matrix
-        // instructions instead of all four workgroups of a CU moving through the phases in lockstep (r4 A/B, five runs each:
-        // 0.590-0.593 ms/step against 0.596-0.607 without; the un-staggered step is bimodal)
-        cgs_stagger<8, CGS_STAGGER_ENC_FWD>();      // (sweep r4: 64 x 64 cycles is too short -- the step stays bimodal --, 190 / 254 and bit 9 measure the same)
+        // (round 4 shipped a late start of every other co-resident workgroup here, -5 us then; round 5's A/B reversed it: no stagger)
         if constexpr (ENC0 == 1) { conv3x3_body_pipe<FEnc0U8P>(PC0, 4 * (int)blockIdx.x, conv_smem); __syncthreads(); }
         if constexpr (ENC0 == 2) { conv3x3_body_pipe<FEnc0MixP>(PC0, 4 * (int)blockIdx.x, conv_smem); __syncthreads(); }
         // features.3 of image blockIdx.x (strips 2 b, 2 b + 1); its first barrier separates the zeroing above from the epilogue's tile writes.
@@ -453,7 +432,7 @@ __device__ __forceinline__ void mask0_pack_weights(const float* __restrict__ w0,
 using T1F = TileP<16, 16, 16, 16, 292>;     // cat(e1, up(o2)) of the forward decoder tail (2-way conflicts on the b128 reads accepted)
 
 // FUSED (round 4): one workgroup per image; after the tail stages (o1 written) the same workgroup runs dec_model.0 of ITS image
-// (conv3x3_body_pipe<FDec0P>: cat(e0, up(o1)) -> o0), every other co-resident workgroup ~4 us late (cgs_stagger).
+// (conv3x3_body_pipe<FDec0P>: cat(e0, up(o1)) -> o0).
 // The LDS of the decoder tail forward, handed to its body by the kernel that runs it (tail_dec_fwd_kernel: static arrays + the dynamic block;
 // dec_mask_fwd_kernel: slices of the one block it shares with the mask head forward).
 struct DecFwdLds {
@@ -594,7 +573,7 @@ __device__ __forceinline__ void tail_dec_fwd_body(const TailDecFwdParams& P, con
 
 template <bool FUSED>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) tail_dec_fwd_kernel(TailDecFwdParams P, ConvParams PC) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailDecFwdParams) + sizeof(ConvParams)>();
+    cgs_kernarg_prefetch<sizeof(TailDecFwdParams) + sizeof(ConvParams)>();
     extern __shared__ __attribute__((aligned(16))) float4 dec_conv_smem[];     // FUSED: dec_model.0's tiles + weights
     __shared__ __attribute__((aligned(16))) float t1[T1F::FLOATS];
     __shared__ __attribute__((aligned(16))) float t2[T8x24::FLOATS];
@@ -605,7 +584,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
         if (threadIdx.x < 64) mask0_pack_weights(P.m0_w, P.m0_pack, threadIdx.x);
         return;
     }
-    if constexpr (FUSED) cgs_stagger<8, CGS_STAGGER_DEC_FWD>();
     tail_dec_fwd_body<FUSED>(P, PC, DecFwdLds{dec_conv_smem, t1, t2, t3, w2s, part});
 }
 
@@ -651,15 +629,9 @@ extern "C" int cgs_tail_dec_fwd_dec0(int32_t n, const cgs_tail_dec_weights* w, c
 //             (__syncthreads waits for the stores: the same hand-over as o1 -> dec_model.0 inside phase D).
 // Both phases are one workgroup per image at two per CU, so neither loses occupancy; their LDS is ONE block, aliased.  Same operands in the same
 // order as the two kernels: bit-identical outputs (tests/test_gpu_dec_mask_fused.py).
-// CGS_DEC_MASK_HOIST: phase M's prologue that does not depend on o0 (40 weight registers, w2, the first strip's frame fetch) is requested BEFORE
-// phase D.  CGS_STAGGER_DEC_MASK: s_sleep units of the phase stagger (cgs_stagger; 0 = none).
+// Phase M's prologue that does not depend on o0 (40 weight registers, w2, the first strip's frame fetch) is requested BEFORE phase D
+// (mask_fwd_body's HOIST).
 // ------------------------------------------------------------------------------------------------
-#ifndef CGS_DEC_MASK_HOIST
-#define CGS_DEC_MASK_HOIST 1
-#endif
-#ifndef CGS_STAGGER_DEC_MASK
-#define CGS_STAGGER_DEC_MASK 0
-#endif
 namespace {
 constexpr int kDmConvF4 = (int)(conv_lds_bytes<FDec0P>() / sizeof(float4));
 static_assert(T1F::FLOATS % 4 == 0 && T8x24::FLOATS % 4 == 0 && T4x48::FLOATS % 4 == 0, "16-byte aligned slices");
@@ -673,7 +645,7 @@ extern "C" int dbg_dec_mask_stamps(unsigned long long* stamps) { g_dec_mask_stam
 #endif
 
 __global__ void __launch_bounds__(256, 2) dec_mask_fwd_kernel(TailDecFwdParams P, ConvParams PC, MaskFwdParams M) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailDecFwdParams) + sizeof(ConvParams) + sizeof(MaskFwdParams)>();
+    cgs_kernarg_prefetch<sizeof(TailDecFwdParams) + sizeof(ConvParams) + sizeof(MaskFwdParams)>();
     __shared__ __attribute__((aligned(16))) float4 lds[kDmF4];
     float* const f = (float*)lds;
     float* const t1 = f + 4 * kDmConvF4;
@@ -682,17 +654,11 @@ __global__ void __launch_bounds__(256, 2) dec_mask_fwd_kernel(TailDecFwdParams P
     float* const w2s = t3 + T4x48::FLOATS;
     const DecFwdLds S{lds, t1, t2, t3, w2s, (float (*)[16][16])(w2s + kDecW2sFloats)};
     float* const win = f + 4 * kMaskStageF4;
-    cgs_stagger<8, CGS_STAGGER_DEC_MASK>();
     auto phase_d = [&] {
         tail_dec_fwd_body<true>(P, PC, S);
         __syncthreads();        // o0 of this image is in memory, and phase D's LDS is free
     };
-    if constexpr (CGS_DEC_MASK_HOIST) {
-        mask_fwd_body<SRC_U8C3, true, true>(M, lds, win, win + kMaskWinFloats, phase_d);
-    } else {
-        phase_d();
-        mask_fwd_body<SRC_U8C3, false, true>(M, lds, win, win + kMaskWinFloats, [] {});
-    }
+    mask_fwd_body<SRC_U8C3, true, true>(M, lds, win, win + kMaskWinFloats, phase_d);
 }
 
 // cgs_tail_dec_fwd_dec0 + cgs_mask_train_fwd_packed in ONE launch (uint8 frames; fp32 frames and n > 1024: CGS_ERR_UNSUPPORTED, the caller keeps the two
@@ -767,15 +733,9 @@ struct TailEncBwdParams {
 #ifndef CGS_ENC1_STAGGER
 #define CGS_ENC1_STAGGER 64
 #endif
-#ifndef CGS_DROPCTX_SPLIT
-#define CGS_DROPCTX_SPLIT 0      // (r05x A/B: 0.5570 ms either way; the split form spills 9 more SGPRs)
-#endif
-#ifndef CGS_ENC1_WGRAD_STAGES
-#define CGS_ENC1_WGRAD_STAGES 1
-#endif
 template <bool ENC1>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) tail_enc_bwd_kernel(TailEncBwdParams P, ConvParams PC, WgradParams PW1) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailEncBwdParams) + (ENC1 ? sizeof(ConvParams) + sizeof(WgradParams) : 0)>();
+    cgs_kernarg_prefetch<sizeof(TailEncBwdParams) + (ENC1 ? sizeof(ConvParams) + sizeof(WgradParams) : 0)>();
     // The chain of one image is latency-bound, so: every global load of an image is issued at the top of its iteration (one
     // memory latency instead of one per stage), the head runs redundantly in all waves on shuffles (no single-wave sections),
     // four barriers per image.
@@ -811,13 +771,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
     const int l15 = lane & 15;
     const int o = tid & 31, kg = tid >> 5, half = lane & 32;
     const int hk = tid >> 3, part = tid & 7;          // d e4 mapping: row k = hk, columns 4*part .. +3
-    // the three Dropout step counters are REQUESTED here and consumed after the first image's loads have been issued (drop_ctx3_fill below)
+    // the three Dropout contexts (r05x A/B: filled behind the first image's loads instead, 0.5570 ms either way and 9 more SGPRs spilled)
     DropCtx d2_{}, d3_{}, dh_{};
     uint64_t sv2, sv3, svh;
     drop_ctx3_load(P.drop_e2, P.drop_e3, P.drop_h1, P.w.w6, sv2, sv3, svh);
-#if !CGS_DROPCTX_SPLIT
-    drop_ctx3_fill(P.drop_e2, P.drop_e3, P.drop_h1, sv2, sv3, svh, d2_, d3_, dh_);      // (A/B: the round-4 placement)
-#endif
+    drop_ctx3_fill(P.drop_e2, P.drop_e3, P.drop_h1, sv2, sv3, svh, d2_, d3_, dh_);
     const bool has_pw = P.d_o4 != nullptr;
 
     // (the once-per-workgroup LDS set-up -- zero halos, convolution weights -- runs inside the first iteration, BEHIND the first
@@ -870,9 +828,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
         const float4 w1v = *(const float4*)(P.w.wl1 + hk * 32 + 4 * part);
         const float4 wpv = has_pw ? *(const float4*)(P.w.wpw + hk * 32 + 4 * part) : f4zero();
         const float wl2 = P.w.wl2[o];
-#if CGS_DROPCTX_SPLIT
-        if (img == (int)blockIdx.x) drop_ctx3_fill(P.drop_e2, P.drop_e3, P.drop_h1, sv2, sv3, svh, d2_, d3_, dh_);
-#endif
         // (the Philox round keys: 3 contexts x 20 loop-invariant scalars otherwise live across the loop -> SGPR spills)
         DropCtx d2 = d2_, d3 = d3_, dh = dh_;
         asm volatile("" : "+s"(d2.key.x), "+s"(d2.key.y), "+s"(d3.key.x), "+s"(d3.key.y), "+s"(dh.key.x), "+s"(dh.key.y));
@@ -1040,7 +995,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
             asm volatile("" : "+v"(tz));
             const int nb = P.nblocks;
             const int nimg = b0 < P.n ? (P.n - b0 + nb - 1) / nb : 0;
-            wgrad_sparse8_body_seq<CGS_ENC1_WGRAD_STAGES>(
+            wgrad_sparse8_body_seq(
                 PW1, [=](int k) { return 2 * (b0 + (k >> 1) * nb) + (k & 1); }, 2 * nimg, PW1.slab + (size_t)b0 * ((9 * 8 + 1) * 8),
                 (float4*)lds_all, tz, [&]() { enc1_dgrad(); __syncthreads(); });
         } else {
@@ -1180,11 +1135,10 @@ struct TailDecBwdLds {
 
 // FUSED (round 4): one workgroup per image first runs dec_model.0's data gradient of ITS image (conv3x3_body_pipe<DDec0P>: the skip
 // gradient d e0 and the cell-summed d o1 go to memory as cgs_conv3x3_bwd_data writes them; the tile region of this kernel is its
-// scratch), then the tail stages read that d o1 back (same workgroup: visible after the barrier).  Every other co-resident workgroup
-// starts ~4 us late, so the latency-bound chains of one half run under the matrix instructions of the other (cgs_stagger).
+// scratch), then the tail stages read that d o1 back (same workgroup: visible after the barrier).
 template <bool FUSED>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) tail_dec_bwd_kernel(TailDecBwdParams P, ConvParams PC) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailDecBwdParams) + sizeof(ConvParams)>();
+    cgs_kernarg_prefetch<sizeof(TailDecBwdParams) + sizeof(ConvParams)>();
     using L = TailDecBwdLds;
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     if (CGS_STAMP_PTR(P.dbg) && threadIdx.x == 0) CGS_STAMP_PTR(P.dbg)[(size_t)blockIdx.x * 16 + 14] = __builtin_amdgcn_s_memtime();      // kernel entry
@@ -1200,7 +1154,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             for (int sx = 0; sx < 4; ++sx) w3b[tap * 4 + sx] = wp[(size_t)(8 - tap) * 48 * 16 + 4 * sx];
     }
     if constexpr (FUSED) {
-        cgs_stagger<8, CGS_STAGGER_DEC_BWD>();
         conv3x3_body_pipe<DDec0P>(PC, 2 * (int)blockIdx.x, smem4);
         __syncthreads();            // d o1 of this image is in memory; the convolution's tiles are dead
     }

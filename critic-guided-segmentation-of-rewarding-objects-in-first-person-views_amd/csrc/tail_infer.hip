@@ -132,9 +132,6 @@ struct TailInferParams {
     int n, nblocks;
 };
 
-#ifndef CGS_TAIL_INFER_W6_LDS
-#define CGS_TAIL_INFER_W6_LDS 0   // features.6's operands in an LDS table instead of 10 registers (for the 128-register build)
-#endif
 #ifndef CGS_TAIL_INFER_OCC
 #define CGS_TAIL_INFER_OCC 3      // workgroups per CU (waves per SIMD) the kernel is compiled for.  Measured (r06_ti*.ab.txt, config 4 at batch 2048): 3 (168
                                   // registers, no spills) 0.1578 ms; 4 (128 registers: 13 .. 28 spilled, with the operands of features.6 in LDS, the constants in
@@ -144,12 +141,11 @@ struct TailInferParams {
 // DEC = false: the critic alone (infer(want_mask = False)).
 template <bool DEC>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CGS_TAIL_INFER_OCC, CGS_TAIL_INFER_OCC))) tail_infer_h16_kernel(TailInferParams P) {
-    if (CGS_KARG_PREFETCH) cgs_kernarg_prefetch<sizeof(TailInferParams)>();
+    cgs_kernarg_prefetch<sizeof(TailInferParams)>();
     __shared__ __attribute__((aligned(16))) _Float16 t1[HT1::HALVES];
     __shared__ __attribute__((aligned(16))) _Float16 t2[HT2::HALVES];
     __shared__ __attribute__((aligned(16))) _Float16 t3[HT3::HALVES];
     __shared__ __attribute__((aligned(16))) th4_t w10t[5 * 64];                 // features.10's operands (one tile per wave and image)
-    __shared__ __attribute__((aligned(16))) th4_t w6t[CGS_TAIL_INFER_W6_LDS ? 5 * 64 : 1];
     __shared__ __attribute__((aligned(16))) th4_t w2t[DEC ? 14 * 64 : 1];       // dec_model.2's (one tile per wave and image)
     __shared__ __attribute__((aligned(16))) th4_t w1t[DEC ? 9 * 64 : 1];        // dec_model.1's (four tiles per wave and image: 18 registers otherwise)
     __shared__ float part[DEC ? 4 : 1][16][16];                                 // dec_model.3: the waves split K, partial [pixel][co]
@@ -175,13 +171,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CGS_TA
         return tap_hi ? ob : oa;
     };
     {
-        th4_t tab10[2], tab6[2], tab2[DEC ? 4 : 1], tab1[DEC ? 3 : 1];
+        th4_t tab10[2], tab2[DEC ? 4 : 1], tab1[DEC ? 3 : 1];
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const int e = tid + 256 * r, i = e >> 6, ln = e & 63;
             tab10[r] = h16_w1<8>(i, ln >> 4, true, [&](int tap, int c) { return P.we.w10[(tap * 8 + c) * 16 + (ln & 15)]; });
-            if constexpr (CGS_TAIL_INFER_W6_LDS)
-                tab6[r] = h16_w1<8>(i, ln >> 4, (ln & 15) < 8, [&](int tap, int c) { return P.we.w6[(tap * 8 + c) * 8 + (ln & 7)]; });
         }
         if constexpr (DEC) {
 #pragma unroll
@@ -200,10 +194,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CGS_TA
         htile_zero<HT3>(t3, tid);
 #pragma unroll
         for (int r = 0; r < 2; ++r)
-            if (tid + 256 * r < 5 * 64) {
-                w10t[tid + 256 * r] = tab10[r];
-                if constexpr (CGS_TAIL_INFER_W6_LDS) w6t[tid + 256 * r] = tab6[r];
-            }
+            if (tid + 256 * r < 5 * 64) w10t[tid + 256 * r] = tab10[r];
         if constexpr (DEC) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -214,11 +205,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CGS_TA
         }
     }
     __builtin_amdgcn_sched_barrier(0);
-    [[maybe_unused]] th4_t w6h[CGS_TAIL_INFER_W6_LDS ? 1 : 5];
+    th4_t w6h[5];      // features.6's operands in 10 registers (in an LDS table they served the 128-register build, measured slower: see above)
     th4_t w14h[4][2];
     [[maybe_unused]] th4_t w3h[7];
-    if constexpr (!CGS_TAIL_INFER_W6_LDS)
-        h16_fill_w<8, 5, 1>(w6h, lane, 0, l15 < 8, [&](int tap, int c) { return P.we.w6[(tap * 8 + c) * 8 + (l15 & 7)]; });
+    h16_fill_w<8, 5, 1>(w6h, lane, 0, l15 < 8, [&](int tap, int c) { return P.we.w6[(tap * 8 + c) * 8 + (l15 & 7)]; });
 #pragma unroll
     for (int ii = 0; ii < 4; ++ii)
 #pragma unroll
@@ -269,7 +259,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CGS_TA
             int y, x;
             h16_tile_px<16>(t, l15, y, x);
             const frag4 acc = hh_conv<5>(t1 + HT1::at(y - 1, x - 1) + cq8, [&](int n) { return off8(HT1{}, n); },
-                                         [&](int n) { if constexpr (CGS_TAIL_INFER_W6_LDS) return w6t[n * 64 + lane_i]; else return w6h[n]; }, frag4{0.f, 0.f, 0.f, 0.f});
+                                         [&](int n) { return w6h[n]; }, frag4{0.f, 0.f, 0.f, 0.f});
             uint32_t idx;
             const float m = pool_quad(acc, b6v, idx);
             const int q = 4 * t + kq;

@@ -32,19 +32,10 @@ struct SpCfg {
 // that fit the X tile's 19.9 KB (round 5): as a rider of another launch its dynamic LDS size is the WHOLE launch's, and 75 KB would cut
 // every role of that launch to two workgroups per CU (measured: wgrad_enc0u8_head 24.5 -> 56.8 us with the un-chunked rider).  The sums
 // and their order are unchanged.  features.0 (28 rows = 28.7 KB against an 11 KB tile) keeps the one-pass form it was tuned with.
-#ifndef CGS_SPRED_CHUNKED
-#define CGS_SPRED_CHUNKED 1
-#endif
-#ifndef CGS_SPARSE8_LEAN
-#define CGS_SPARSE8_LEAN 1
-#endif
-#ifndef CGS_SP8_GROUP
-#define CGS_SP8_GROUP 1
-#endif
 template <class C>
 struct SpRed {
     static constexpr size_t TILE = (size_t)C::TRA * C::RS * 4 + 16, FULL = (size_t)C::NACC * 256 * 4;
-    static constexpr bool CHUNKED = (CGS_SPRED_CHUNKED != 0) && (C::CA == 8) && FULL > TILE;
+    static constexpr bool CHUNKED = (C::CA == 8) && FULL > TILE;
     static constexpr int RCH = CHUNKED ? (int)(TILE / 1024) : C::NACC;       // rows per chunk (1 KB per row)
     static constexpr size_t BYTES = CHUNKED ? TILE : (TILE > FULL ? TILE : FULL);
 };
@@ -289,11 +280,9 @@ __device__ __forceinline__ void wgrad_sparse_body_seq(const WgradParams& P, cons
 // ------------------------------------------------------------------------------------------------
 struct SpNoBetween { __device__ __forceinline__ void operator()() const {} };
 
-// NSTG = prefetch stages (tiles in flight): 1 as a role of another launch (130 VGPRs), 2 inside the tail backward kernel, where a workgroup
-// has only 2 - 4 tiles and the FIRST tiles' load latency is what it waits for.  `between` runs after the first NSTG tiles' global loads have
-// been issued and before anything of this body touches LDS (the caller's own LDS epilogue hides the loads' round trip); it must end with
-// the LDS region free and the workgroup synchronised.
-template <int NSTG = 1, class SEQ, class BETWEEN = SpNoBetween>
+// `between` runs after the first tile's global loads have been issued and before anything of this body touches LDS (the caller's own LDS
+// epilogue hides the loads' round trip); it must end with the LDS region free and the workgroup synchronised.
+template <class SEQ, class BETWEEN = SpNoBetween>
 __device__ __forceinline__ void wgrad_sparse8_body_seq(const WgradParams& P, const SEQ seq, const int cnt, float* slab, float4* smem,
                                                        const int tid_bias = 0, const BETWEEN between = BETWEEN{}) {
     using C = SpCfg<32, 8, WSRC_F32>;
@@ -304,6 +293,7 @@ __device__ __forceinline__ void wgrad_sparse8_body_seq(const WgradParams& P, con
     auto slot_store = [&](int r, int slot, const float4& v) { *(float4*)(xt + r * RS + 4 * slot) = v; };      // RS = 276: rows 16-byte aligned
     constexpr int NF = C::TRA * W * S, ITF = (NF + 255) / 256;      // 1152 float4 per tile: 4.5 per thread
     struct Stage { float4 gf[ITF]; float pval[8]; uint32_t pnibs; };
+    constexpr int NSTG = 1;      // prefetch stages (tiles in flight)
     Stage stg[NSTG];
     auto fetch = [&](int tile, Stage& R) {
         const int n = tile / C::STRIPS, row0 = (tile % C::STRIPS) * TH, crow0 = (tile % C::STRIPS) * C::CROWS;
@@ -373,8 +363,7 @@ __device__ __forceinline__ void wgrad_sparse8_body_seq(const WgradParams& P, con
                 acc[t][2] = fmaf(x.z, v, acc[t][2]);
                 acc[t][3] = fmaf(x.w, v, acc[t][3]);
             }
-            if ((k % CGS_SP8_GROUP) == CGS_SP8_GROUP - 1)
-                __builtin_amdgcn_sched_barrier(0);         // CGS_SP8_GROUP half-pairs at a time: each one interleaved costs 36 more registers
+            __builtin_amdgcn_sched_barrier(0);         // one half-pair at a time: each one interleaved costs 36 more registers
         }
         __syncthreads();
     };
@@ -416,7 +405,7 @@ template <class C>
 __device__ __forceinline__ void wgrad_sparse_body(const WgradParams& P, const int tile0, const int tstride, const int tend,
                                                   float* slab, float4* smem) {
     const int cnt = tile0 < tend ? (tend - tile0 + tstride - 1) / tstride : 0;
-    if constexpr (C::CA == 8 && C::SRC == WSRC_F32 && CGS_SPARSE8_LEAN) wgrad_sparse8_body_seq(P, [=](int k) { return tile0 + k * tstride; }, cnt, slab, smem);
+    if constexpr (C::CA == 8 && C::SRC == WSRC_F32) wgrad_sparse8_body_seq(P, [=](int k) { return tile0 + k * tstride; }, cnt, slab, smem);
     else wgrad_sparse_body_seq<C>(P, [=](int k) { return tile0 + k * tstride; }, cnt, slab, smem);
 }
 
@@ -428,7 +417,7 @@ template <> struct sparse_cfg<WEnc0Mix> { static constexpr bool ok = true; using
 template <> struct sparse_cfg<WEnc1> { static constexpr bool ok = true; using type = SpCfg<32, 8, WSRC_F32>; };
 
 // SPARSE is a compile-time choice per kernel instance (a kernel that carries both bodies pays the registers and the LDS of the
-// bigger one); the host picks the instance (CGS_WGRAD_SPARSE, default on where a sparse form exists).
+// bigger one); the host launches the sparse instance wherever a sparse form exists (round 2 kept the dense MFMA form behind a switch).
 template <class CWG, bool SPARSE>
 __device__ __forceinline__ void wgrad_dispatch(const WgradParams& P, const int tile0, const int tstride, const int tend,
                                                float* slab, float4* smem) {
@@ -445,5 +434,3 @@ static constexpr size_t wgrad_any_lds_bytes() {
     if constexpr (SPARSE) return wgrad_sparse_lds_bytes<typename sparse_cfg<CWG>::type>();
     else return wgrad_lds_bytes<CWG>();
 }
-
-static inline int wgrad_sparse_enabled() { return 1; }     // (round 2 kept the dense MFMA form behind an environment switch)

@@ -205,6 +205,28 @@ def test_build_headers_list_every_quoted_include():
     assert not missing, f"headers included under csrc/ but missing from build.HEADERS (header: first includer): {missing}"
 
 
+def test_build_switches_are_the_documented_tuning_knobs():
+    """Every `#ifndef NAME` / `#define NAME value` default in the library's sources is a row of DESIGN.md's table "Build-time tuning knobs", and
+    every row is such a default: a new build switch has to be written down to get in.  (An include guard defines its name without a value.)"""
+    from cgs_amd import build
+    found = {}
+    for f in build.SOURCES + build.HEADERS:
+        path = f if os.path.isabs(f) else os.path.join(build.CSRC, f)
+        with open(path) as fp:
+            for name, again in re.findall(r"^[ \t]*#[ \t]*ifndef[ \t]+(\w+)[^\n]*\n[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+\S", fp.read(), re.M):
+                if name == again:
+                    found.setdefault(name, os.path.basename(path))
+    assert found, "no build switch found: the pattern is wrong"
+    with open(os.path.join(REPO, "DESIGN.md")) as fp:
+        section = re.search(r"^#+ Build-time tuning knobs\n(.*?)(?=^#)", fp.read(), re.M | re.S)
+    assert section, "DESIGN.md has no section 'Build-time tuning knobs'"
+    rows = re.findall(r"^\| `(\w+)` \| `([\w.]+)` \|", section.group(1), re.M)
+    documented = dict(rows)
+    assert len(rows) == len(documented), "a knob is listed twice"
+    assert set(found) == set(documented), f"undocumented: {sorted(set(found) - set(documented))}, documented but gone: {sorted(set(documented) - set(found))}"
+    assert found == documented, "a knob is listed under the wrong file"
+
+
 def test_c_abi_library_exports_every_declared_symbol():
     """libcgs_hip.so loads (no GPU needed for dlopen) and exports exactly the entry points include/cgs_hip.h
     declares; the ctypes signature table covers all of them.  No compute call is made here."""

@@ -1,7 +1,6 @@
 #!/bin/bash
 # usage (GPU box): tools/whatif.sh TAG KERNEL-SUBSTRING VARIANT...   -> per variant library (tools/build_variant.py; "prod" = the product library) the
-# per-step time of the matching kernels under rocprofv3 --kernel-trace --stats and the step's kernel sum (timing experiments: what-if builds compute
-# wrong results on purpose)
+# per-step time of the matching kernels under rocprofv3 --kernel-trace --stats and the step's kernel sum
 tag=$1; pat=$2; shift 2
 root=${GRAFT_REPO_ROOT:-/root/repo}
 cd $root
