@@ -17,7 +17,8 @@ struct SpCfg {
     static constexpr int CPR = W / 2, CROWS = 128 / CPR;       // pool cells per row; cell rows per tile (128 cells = 1024 pairs)
     static constexpr int TH = 2 * CROWS, STRIPS = H / TH, TRA = TH + 2;
     static constexpr int PW = (S == 1) ? W + 4 : W + 2;        // pixel slots per row
-    // row stride in dwords.  CA = 3: 274 = 2 (mod 8): the lanes of a wave read the slots of 8 neighbouring cells (8 dwords apart),
+    // row stride in dwords, chosen for the patch READS (the staging stores are a separate matter: commit() below; tools/lds_banks.py
+    // models both).  CA = 3: 274 = 2 (mod 8): the lanes of a wave read the slots of 8 neighbouring cells (8 dwords apart),
     // either pixel column of the window (+4) and either row (+274 = 18 mod 64): all 32 addresses fall into different banks for
     // each of the 3 dwords read; rows are then 8-byte aligned (reads: b64 + b32).  CA = 8: 276 = 20 (mod 64), 16-byte aligned: the b128
     // reads of a 16-lane group (2 cells x 2 columns x 2 rows) cover banks 0-3, 8-11, 16-19, 24-27 | 20-23, 28-31, 36-39, 44-47 (272 put
@@ -68,21 +69,24 @@ __device__ __forceinline__ void wgrad_sparse_body_seq(const WgradParams& P, cons
     }
 
     // ---- X tile: fetch (global -> registers) / commit (registers -> LDS); interior columns 1..W of rows row0-1 .. row0+TH ----
-    constexpr int NG = C::TRA * W / 4;                         // CA = 3: groups of 4 pixels (12 bytes / 3 dwords)
-    constexpr int ITG = (NG + 255) / 256;
-    constexpr int NF = C::TRA * W * S, ITF = (NF + 255) / 256; // CA = 8 (or fp32 images): float4 elements
+    constexpr int NPX = C::TRA * W;                            // CA = 3: ONE pixel per lane and pass, e = tid + 256 * it: a wave takes one tile
+    constexpr int ITP = (NPX + 255) / 256;                     // row per pass (640 pixels: waves 0 and 1 take rows 8 and 9 in the third pass)
+    constexpr int NF = C::TRA * W * S, ITF = (NF + 255) / 256; // CA = 8: float4 elements
     // what is fetched for a tile: its X rows (raw) and its pairs (gradient at the pooled output, argmax nibble).  TWO tiles are in
     // flight: a tile's FMA phase is much shorter than a memory round trip, one tile ahead leaves the loop latency-bound.
+    // uint8 sources: a pixel's 3 bytes lie in the aligned dwords (3 pix) / 4 and (3 pix + 2) / 4 (the same one for x = 0, 3 (mod 4)), at
+    // byte (3 x) mod 4 of the pair: the row length in bytes is a multiple of 4.
     struct Stage {
-        uint32_t ga[ITG][3], gb[ITG][3];
-        float4 gz[ITG];
-        float4 gf[(C::SRC == WSRC_F32) ? ITF : 1];
+        uint32_t ga[ITP][2], gb[ITP][2];
+        float gz[ITP];
+        float gx[(C::SRC == WSRC_F32 && CA == 3) ? ITP : 1][3];
+        float4 gf[(C::SRC == WSRC_F32 && CA == 8) ? ITF : 1];
         float pval[4];
         uint32_t pnib[4];
     };
     Stage stg[2];
     auto fetch = [&](int tile, Stage& R) {
-        auto& ga = R.ga; auto& gb = R.gb; auto& gz = R.gz; auto& gf = R.gf; auto& pval = R.pval; auto& pnib = R.pnib;
+        auto& ga = R.ga; auto& gb = R.gb; auto& gz = R.gz; auto& gx = R.gx; auto& gf = R.gf; auto& pval = R.pval; auto& pnib = R.pnib;
         const int n = tile / C::STRIPS, row0 = (tile % C::STRIPS) * TH;
         {
             const int crow0 = (tile % C::STRIPS) * C::CROWS;
@@ -104,36 +108,33 @@ __device__ __forceinline__ void wgrad_sparse_body_seq(const WgradParams& P, cons
             }
         } else {
 #pragma unroll
-            for (int it = 0; it < ITG; ++it) {
-                int e = tid + 256 * it; e = e < NG ? e : NG - 1;
-                const int g = e % (W / 4), r = e / (W / 4), y = row0 + r - 1;
+            for (int it = 0; it < ITP; ++it) {
+                int e = tid + 256 * it; e = e < NPX ? e : NPX - 1;
+                const int x = e % W, r = e / W, y = row0 + r - 1;
                 const bool in = y >= 0 && y < H;
                 int nn = n;
                 if constexpr (C::SRC == WSRC_MIX) nn = n >= P.mix_n_a ? n - P.mix_n_a : n;       // mixes of A-image nn
-                const int pix = in ? (nn * H + y) * W + 4 * g : 0;
+                const int pix = in ? (nn * H + y) * W + x : 0;
+                const int d0 = (pix * 3) >> 2, d1 = (pix * 3 + 2) >> 2;
                 if constexpr (C::SRC == WSRC_MIX) {
-                    const uint32_t* a32 = (const uint32_t*)P.mix_a + (pix * 3) / 4;
-                    const uint32_t* b32 = (const uint32_t*)P.mix_b + (pix * 3) / 4;
-#pragma unroll
-                    for (int d = 0; d < 3; ++d) { ga[it][d] = a32[d]; gb[it][d] = b32[d]; }
-                    gz[it] = *(const float4*)(P.mix_z + pix);
+                    ga[it][0] = ((const uint32_t*)P.mix_a)[d0]; ga[it][1] = ((const uint32_t*)P.mix_a)[d1];
+                    gb[it][0] = ((const uint32_t*)P.mix_b)[d0]; gb[it][1] = ((const uint32_t*)P.mix_b)[d1];
+                    gz[it] = P.mix_z[pix];
                 } else if constexpr (C::SRC == WSRC_U8) {
-                    const uint32_t* a32 = (const uint32_t*)P.src_a + (pix * 3) / 4;
+                    ga[it][0] = ((const uint32_t*)P.src_a)[d0]; ga[it][1] = ((const uint32_t*)P.src_a)[d1];
+                } else {      // fp32 image, 3 channels
+                    const float* f = (const float*)P.src_a + (size_t)pix * 3;
 #pragma unroll
-                    for (int d = 0; d < 3; ++d) ga[it][d] = a32[d];
-                } else {      // fp32 image, 3 channels: 12 floats = 3 float4
-                    const float4* f = (const float4*)((const float*)P.src_a + (size_t)pix * 3);
-                    const float4 v0 = f[0], v1 = f[1], v2 = f[2];
-                    ga[it][0] = __float_as_uint(v0.x); ga[it][1] = __float_as_uint(v0.y); ga[it][2] = __float_as_uint(v0.z);
-                    gb[it][0] = __float_as_uint(v0.w); gb[it][1] = __float_as_uint(v1.x); gb[it][2] = __float_as_uint(v1.y);
-                    gz[it] = make_float4(v1.z, v1.w, v2.x, v2.y);
-                    gf[0] = make_float4(v2.z, v2.w, 0.f, 0.f);
+                    for (int c = 0; c < 3; ++c) gx[it][c] = f[c];
                 }
             }
         }
     };
+    // Staging stores (CA = 3).  The 16 consecutive lanes that one ds_write_b64 services together hold 16 neighbouring pixels of a row,
+    // slots 4 dwords apart: the same half of every slot would fall on 8 bank pairs twice over.  Lanes 8-15 of each such group therefore
+    // store the halves of their slot in the other order ({z, 0} first, {x, y} second): each store then covers all 32 banks once.
     auto commit = [&](int tile, const Stage& R) {
-        auto& ga = R.ga; auto& gb = R.gb; auto& gz = R.gz; auto& gf = R.gf;
+        auto& ga = R.ga; auto& gb = R.gb; auto& gz = R.gz; auto& gx = R.gx; auto& gf = R.gf;
         const int n = tile / C::STRIPS, row0 = (tile % C::STRIPS) * TH;
         if constexpr (C::SRC == WSRC_F32 && CA == 8) {
 #pragma unroll
@@ -145,43 +146,42 @@ __device__ __forceinline__ void wgrad_sparse_body_seq(const WgradParams& P, cons
                 }
             }
         } else {
+            const bool swp = (tid >> 3) & 1;
 #pragma unroll
-            for (int it = 0; it < ITG; ++it) {
+            for (int it = 0; it < ITP; ++it) {
                 const int e = tid + 256 * it;
-                if (e < NG) {
-                    const int g = e % (W / 4), r = e / (W / 4), y = row0 + r - 1;
+                if (e < NPX) {
+                    const int x = e % W, r = e / W, y = row0 + r - 1;
                     const bool in = y >= 0 && y < H;
-                    float4 px[4];
+                    float m[3];
                     if constexpr (C::SRC == WSRC_F32) {
-                        static_assert(ITG == 1, "fp32 images: one group of 4 pixels per thread");
-                        px[0] = make_float4(__uint_as_float(ga[it][0]), __uint_as_float(ga[it][1]), __uint_as_float(ga[it][2]), 0.f);
-                        px[1] = make_float4(__uint_as_float(gb[it][0]), __uint_as_float(gb[it][1]), __uint_as_float(gb[it][2]), 0.f);
-                        px[2] = make_float4(gz[it].x, gz[it].y, gz[it].z, 0.f);
-                        px[3] = make_float4(gz[it].w, gf[0].x, gf[0].y, 0.f);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) m[c] = gx[it][c];
                     } else {
                         const float sc = 1.f / 255.f;
                         const bool inj = C::SRC == WSRC_MIX && n >= P.mix_n_a;
+                        const uint32_t sh = (3 * x) & 3;
+                        const uint32_t wa = __builtin_amdgcn_alignbyte(ga[it][1], ga[it][0], sh);
+                        uint32_t wb = 0;
+                        if constexpr (C::SRC == WSRC_MIX) wb = __builtin_amdgcn_alignbyte(gb[it][1], gb[it][0], sh);
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            float m[3];
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) {
-                                const int byte = 3 * k + c;
-                                float av = ((ga[it][byte >> 2] >> (8 * (byte & 3))) & 255u) * sc;
-                                if constexpr (C::SRC == WSRC_MIX) {
-                                    float bv = ((gb[it][byte >> 2] >> (8 * (byte & 3))) & 255u) * sc;
-                                    if (inj) { const float t = av; av = bv; bv = t; }
-                                    const float zi = f4get(gz[it], k);
-                                    m[c] = av * (1.f - zi) + zi * bv;
-                                } else {
-                                    m[c] = av;
-                                }
+                        for (int c = 0; c < 3; ++c) {
+                            float av = ((wa >> (8 * c)) & 255u) * sc;
+                            if constexpr (C::SRC == WSRC_MIX) {
+                                float bv = ((wb >> (8 * c)) & 255u) * sc;
+                                if (inj) { const float t = av; av = bv; bv = t; }
+                                const float zi = gz[it];
+                                m[c] = av * (1.f - zi) + zi * bv;
+                            } else {
+                                m[c] = av;
                             }
-                            px[k] = make_float4(m[0], m[1], m[2], 0.f);
                         }
                     }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) slot_store(r, 4 * g + k + 1, in ? px[k] : f4zero());
+                    if (!in) m[0] = m[1] = m[2] = 0.f;
+                    float* q = xt + r * RS + 4 * (x + 1);
+                    const float2 lo = make_float2(m[0], m[1]), hi = make_float2(m[2], 0.f);
+                    *(float2*)(q + (swp ? 2 : 0)) = swp ? hi : lo;
+                    *(float2*)(q + (swp ? 0 : 2)) = swp ? lo : hi;
                 }
             }
         }
