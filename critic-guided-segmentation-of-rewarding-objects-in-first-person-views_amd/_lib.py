@@ -64,6 +64,7 @@ SHEET_ROWS, SHEET_MAX_N = 7, 1 << 20                                            
 OBJ_U8, OBJ_F32_GT, OBJ_F32_GE, OBJ_FIELDS, OBJ_MAX_SIDE = 0, 1, 2, 8, 64       # cgs_objects_label (include/cgs_hip.h)
 OBJ_MATCH_MAX_OBJECTS, OBJ_MATCH_MAX_IOU = 64, 16                               # cgs_objects_match (include/cgs_hip.h)
 OBJ_TRACK_FIELDS, OBJ_TRACK_MAX_FRAMES = 8, 1 << 17                             # cgs_objects_track (include/cgs_hip.h)
+OBJ_TRACK_MAX_GAP = 8                                                           # cgs_objects_track_gap: a judgement, not a measured value
 SALIENCY_SIDE, SALIENCY_MAX_T = 64, 1024                                        # cgs_saliency_sweep (include/cgs_hip.h)
 BOUNDARY_MAX_TOL, BOUNDARY_MAX_TOL_PX = 16, 128                                 # cgs_boundary_score (include/cgs_hip.h)
 FIT_SIDE, FIT_MAX_SIDE, FIT_RADIUS, FIT_MAP_F32, FIT_MAP_U8 = 64, 4096, 2, 0, 1 # cgs_fit_down_u8 / cgs_fit_up_joint (include/cgs_hip.h)
@@ -219,6 +220,8 @@ SIGNATURES = {
     "cgs_objects_track_scratch_bytes": (i64, [i32, i32]),
     "cgs_objects_track": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "cgs_objects_track_switches": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "cgs_objects_track_gap_scratch_bytes": (i64, [i32, i32, i32]),
+    "cgs_objects_track_gap": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "cgs_saliency_sweep": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "cgs_boundary_score": (i32, [vp, i32, f32, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
     "cgs_fit_down_u8": (i32, [vp, i32, i32, i32, vp, vp]),

@@ -18,6 +18,9 @@
 //
 // Launches: init, match (n > 1), self-match, link, R x resolve, number, heads, table, paint: 7 + R + (n > 1), a function of n alone
 // (paint is launched also when both its outputs are NULL and then returns at once).
+//
+// cgs_objects_track_gap bridges gaps of up to G missing frames: the path above as level 1, then per level g = 2 .. G + 1 one launch of
+// track_level_kernel over the frame pairs (f - g, f); see "bridged gaps" below and DESIGN.md.
 #include "pixel_common.h"
 
 namespace {
@@ -233,6 +236,197 @@ track_switches_kernel(const int32_t* __restrict__ truth_prev, const int32_t* __r
     if (threadIdx.x < 3 * T && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
 }
 
+// ---- bridged gaps (cgs_objects_track_gap) ---------------------------------------------------------------------------------------------
+// Level 1 is the path above, untouched.  `prepare` then turns its result into what the levels and the table need: gap (0 / 1), each
+// link's (inter, union) beside its object, and per frame the 64-bit word of open tails (objects without a successor) next to the link
+// kernel's word of heads, which is the word of open heads.  Level g >= 2 is one launch of track_level_kernel; the heads words it leaves
+// are the tracks' heads, so resolve, number, heads and paint run as they are, and a table kernel that reads `gap` replaces the table.
+constexpr int OT_STRIDE = OT_MAX_K + 1;               // objects_match.hip, "Bank conflicts": the same table, the same two scans
+constexpr int OT_CELLS = OT_MAX_K * OT_STRIDE;
+static_assert(OT_CELLS % 4 == 0 && CGS_OBJ_MAX_SIDE == CGS_WAVE, "a row is one wave-wide ballot");
+
+struct GapLayout {
+    int64_t tails, link, words;
+};
+__host__ __device__ inline GapLayout gap_layout(int64_t n, int64_t K) {
+    GapLayout o;
+    o.tails = (layout(n, K).words + 1) & ~(int64_t)1;                    // 64-bit words
+    o.link = o.tails + 2 * n;
+    o.words = o.link + 2 * n * K;
+    return o;
+}
+
+__global__ void __launch_bounds__(OT_THREADS)
+track_gap_prepare_kernel(const int32_t* __restrict__ best, const int32_t* __restrict__ prev, int n, int K, int32_t* __restrict__ gap,
+                         int32_t* __restrict__ link, unsigned long long* __restrict__ tails, int32_t* __restrict__ gap_links, int levels,
+                         int32_t* __restrict__ extra, int64_t extra_words) {
+    const int64_t step = (int64_t)gridDim.x * OT_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * OT_THREADS + threadIdx.x; i < extra_words; i += step) extra[i] = 0;
+    if (blockIdx.x == 0 && threadIdx.x < levels) gap_links[threadIdx.x] = 0;
+    const int lane = threadIdx.x & (CGS_WAVE - 1);
+    const int f = blockIdx.x * OT_WAVES + threadIdx.x / CGS_WAVE;
+    const bool in = f < n && lane < K;
+    bool open = false;
+    if (in) {
+        const int32_t* own = best + (((int64_t)f * 2 + 0) * K + lane) * 4;          // (partner in f + 1, inter, own area, partner's area)
+        const int64_t i = (int64_t)f * K + lane;
+        const int p = prev[i];
+        gap[i] = p > 0;
+        if (p > 0) {
+            const int32_t* row = best + (((int64_t)(f - 1) * 2 + 1) * K + lane) * 4;
+            link[2 * i] = row[1];
+            link[2 * i + 1] = row[2] + row[3] - row[1];
+        }
+        const int q = f + 1 < n ? own[0] : 0;
+        open = own[2] > 0 && !(q >= 1 && q <= K && prev[(int64_t)(f + 1) * K + q - 1] == lane + 1);
+    }
+    const unsigned long long word = __ballot(open);
+    if (lane == 0 && f < n) tails[f] = word;
+}
+
+// One workgroup, one frame pair (a, a + g): objects_match_kernel's count and its two scans over the open tails of a and the open heads
+// of a + g, every other label read as 0.  The words of frame a + g's heads and frame a's tails belong to this workgroup alone within
+// the launch.  A pair with no open tail or no open head has nothing to link and reads no pixel.
+__global__ void __launch_bounds__(OT_THREADS)
+track_level_kernel(const int32_t* __restrict__ labels, int h, int w, int K, int g, int iou, int32_t* __restrict__ prev,
+                   int32_t* __restrict__ gap, int32_t* __restrict__ root, int32_t* __restrict__ link, unsigned long long* __restrict__ heads,
+                   unsigned long long* __restrict__ tails, int32_t* __restrict__ totals) {
+    __shared__ __attribute__((aligned(16))) int s_I[OT_CELLS];           // [tail - 1][head - 1], row stride 65
+    __shared__ int s_A[2][OT_MAX_K];                                     // area of the tails, of the heads
+    __shared__ int s_best[2][OT_MAX_K];
+    const int a = blockIdx.x, f = a + g;
+    const unsigned long long tmask = tails[a], hmask = heads[f];
+    if (!tmask || !hmask) return;                                        // uniform over the workgroup
+    const int x = threadIdx.x & (CGS_WAVE - 1), wave = threadIdx.x / CGS_WAVE;
+    const bool live = x < w;
+    const int64_t fa = (int64_t)a * h * w, ff = (int64_t)f * h * w;
+    const unsigned long long upto = (2ull << x) - 1ull;
+
+    for (int j = threadIdx.x; j < OT_CELLS / 4; j += OT_THREADS) reinterpret_cast<int4*>(s_I)[j] = make_int4(0, 0, 0, 0);
+    if (threadIdx.x < 2 * OT_MAX_K) (&s_A[0][0])[threadIdx.x] = 0;
+    __syncthreads();
+
+    int pn = 0, tn = 0;
+    if (live && wave < h) {
+        pn = labels[fa + wave * w + x];
+        tn = labels[ff + wave * w + x];
+    }
+    for (int y = wave; y < h; y += OT_WAVES) {
+        const int p = pn, t = tn;
+        if (live && y + OT_WAVES < h) {
+            pn = labels[fa + (y + OT_WAVES) * w + x];
+            tn = labels[ff + (y + OT_WAVES) * w + x];
+        }
+        const int pc = (p >= 1 && p <= K && ((tmask >> (p - 1)) & 1ull)) ? p : 0;
+        const int tc = (t >= 1 && t <= K && ((hmask >> (t - 1)) & 1ull)) ? t : 0;
+        const int key = live ? ((pc << 8) | tc) : -1;
+        const int left = __shfl_up(key, 1, CGS_WAVE);
+        const unsigned long long starts = __ballot(x == 0 || key != left);
+        const bool last = x == CGS_WAVE - 1 || ((starts >> (x + 1)) & 1ull);
+        if (live && last && key != 0) {
+            const int len = x - (63 - __clzll((long long)(starts & upto))) + 1;
+            if (pc) atomicAdd(&s_A[0][pc - 1], len);
+            if (tc) atomicAdd(&s_A[1][tc - 1], len);
+            if (pc && tc) atomicAdd(&s_I[(pc - 1) * OT_STRIDE + tc - 1], len);
+        }
+    }
+    __syncthreads();
+
+    const int side = wave & 1;                                           // waves 0 and 1 scan, 2 and 3 only keep the barriers
+    const int n_other = 64 - __clzll((long long)(side ? tmask : hmask));
+    const int own_step = side ? 1 : OT_STRIDE, other_step = side ? OT_STRIDE : 1;
+    const int own_area = s_A[side][x];
+    const int* other_areas = s_A[side ^ 1];
+    int bi = 0, bu = 1, bj = 0;
+    if (wave < 2) {
+        for (int j = 0; j < n_other; ++j) {
+            const int inter = s_I[x * own_step + j * other_step], oa = other_areas[j];
+            const int uni = own_area + oa - inter;
+            if (inter > 0 && inter * bu > bi * uni) {
+                bi = inter;
+                bu = uni;
+                bj = j + 1;
+            }
+        }
+        s_best[side][x] = bj;
+    }
+    __syncthreads();
+    if (wave >= 2) return;
+    const bool linked = bj > 0 && s_best[side ^ 1][bj - 1] == x + 1 && 1000 * bi >= iou * bu;       // the same on both ends of a pair
+    if (linked && side) {
+        const int64_t i = (int64_t)f * K + x;
+        prev[i] = bj;
+        gap[i] = g;
+        root[i] = a * K + bj - 1;
+        link[2 * i] = bi;
+        link[2 * i + 1] = bu;
+    }
+    const unsigned long long closed = __ballot(linked);
+    if (x == 0 && closed) {
+        if (side) {
+            heads[f] = hmask & ~closed;
+            atomicAdd(&totals[1], __popcll(closed));
+        } else {
+            tails[a] = tmask & ~closed;
+        }
+    }
+}
+
+// track_table_kernel with links of any gap: the link's sums lie beside the object, a bridged link adds to the track's extras, and the
+// links are counted by gap.
+__global__ void __launch_bounds__(OT_THREADS)
+track_gap_table_kernel(const int32_t* __restrict__ best, const int32_t* __restrict__ root, const unsigned long long* __restrict__ heads,
+                       const int32_t* __restrict__ base, const int32_t* __restrict__ gap, const int32_t* __restrict__ link, int n, int K,
+                       int levels, int32_t* __restrict__ track, int32_t* __restrict__ tracks, int32_t* __restrict__ extra, int max_tracks,
+                       int32_t* __restrict__ totals, int32_t* __restrict__ gap_links) {
+    __shared__ int s_len[OT_WAVES];
+    __shared__ int s_gap[CGS_OBJ_TRACK_MAX_GAP + 1];
+    const int lane = threadIdx.x & (CGS_WAVE - 1), wave = threadIdx.x / CGS_WAVE;
+    const int f = blockIdx.x * OT_WAVES + wave;
+    const bool in = f < n && lane < K;
+    if (threadIdx.x < levels) s_gap[threadIdx.x] = 0;
+    __syncthreads();
+    const int area = in ? best[(((int64_t)f * 2 + 0) * K + lane) * 4 + 2] : 0;
+    int t = 0, len = 0, g = 0;
+    if (area > 0) {
+        const int64_t i = (int64_t)f * K + lane;
+        const int r = root[i], fr = r / K, lr = r - fr * K;
+        t = track_number(heads, base, fr, lr);
+        len = f - fr + 1;
+        g = gap[i];
+        if (t <= max_tracks) {
+            if (tracks) {
+                int32_t* row = tracks + (int64_t)(t - 1) * CGS_OBJ_TRACK_FIELDS;
+                atomicAdd(row + 2, 1);
+                atomicAdd(row + 3, area);
+                atomicMin(row + 4, area);
+                atomicMax(row + 5, area);
+                if (g > 0) {
+                    atomicAdd(row + 6, link[2 * i]);
+                    atomicAdd(row + 7, link[2 * i + 1]);
+                }
+            }
+            if (extra && g > 1) {
+                atomicAdd(extra + 2 * (int64_t)(t - 1), 1);
+                atomicAdd(extra + 2 * (int64_t)(t - 1) + 1, g - 1);
+            }
+        }
+    }
+    if (in) track[(int64_t)f * K + lane] = t;
+    for (int k = 1; k <= levels; ++k) {
+        const unsigned long long b = __ballot(g == k);
+        if (lane == 0 && b) atomicAdd(&s_gap[k - 1], __popcll(b));
+    }
+    len = px_wave_max(len);
+    if (lane == 0) s_len[wave] = len;
+    __syncthreads();
+    if (threadIdx.x < levels && s_gap[threadIdx.x]) atomicAdd(gap_links + threadIdx.x, s_gap[threadIdx.x]);
+    if (threadIdx.x == 0) {
+        const int longest = max(max(s_len[0], s_len[1]), max(s_len[2], s_len[3]));
+        if (longest > 0) atomicMax(totals + 3, longest);
+    }
+}
+
 inline unsigned blocks_for(int64_t items, int per) { return (unsigned)((items + per - 1) / per); }
 
 }  // namespace
@@ -312,6 +506,85 @@ extern "C" int cgs_objects_track_switches(const int32_t* truth_prev, const int32
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(track_switches_kernel, dim3(blocks_for(n, OT_WAVES)), dim3(OT_THREADS), 0, stream, truth_prev, pred_track,
                        match_best, iou_milli, (int)T, (int)n, (int)max_objects, counts);
+    CGS_HIP_CHECK_LAUNCH();
+    return CGS_OK;
+}
+
+extern "C" int64_t cgs_objects_track_gap_scratch_bytes(int32_t n, int32_t max_objects, int32_t max_gap) {
+    if (n < 1 || max_objects < 1 || max_gap < 0 || max_gap > CGS_OBJ_TRACK_MAX_GAP) return 0;
+    // gap_layout().words: layout().words rounded up to even, then 2 n + 2 n K
+    const unsigned __int128 N = (unsigned __int128)n, K = (unsigned __int128)max_objects;
+    const unsigned __int128 words = ((N * (7u + 10u * K) + 4u + 1u) & ~(unsigned __int128)1) + 2u * N + 2u * N * K;
+    return words * 4u > (unsigned __int128)INT64_MAX ? INT64_MAX : (int64_t)(words * 4u);
+}
+
+// Launches: init, match (n > 1), self-match, link, prepare, min(G, n - 1) levels, R x resolve, number, heads, table, paint:
+// 8 + R + (n > 1) + min(G, n - 1), a function of n and G alone.
+extern "C" int cgs_objects_track_gap(const int32_t* labels, int32_t n, int32_t h, int32_t w, int32_t max_objects, int32_t iou_milli,
+                                     int32_t max_gap, int32_t max_tracks, int32_t* prev, int32_t* gap, int32_t* track, int32_t* totals,
+                                     int32_t* gap_links, int32_t* tracks, int32_t* tracks_extra, int32_t* track_labels, uint8_t* rgb,
+                                     void* scratch, int64_t scratch_bytes, cgs_stream_t stream_) {
+    if (!labels || !prev || !gap || !track || !totals || !gap_links || !scratch || n < 1 || h < 1 || w < 1 || max_objects < 1 ||
+        max_tracks < 1 || iou_milli < 1 || iou_milli > 1000 || max_gap < 0 || max_gap > CGS_OBJ_TRACK_MAX_GAP ||
+        ((uintptr_t)labels & 3u) || ((uintptr_t)prev & 3u) || ((uintptr_t)gap & 3u) || ((uintptr_t)track & 3u) ||
+        ((uintptr_t)totals & 3u) || ((uintptr_t)gap_links & 3u) || ((uintptr_t)tracks & 3u) || ((uintptr_t)tracks_extra & 3u) ||
+        ((uintptr_t)track_labels & 3u) || ((uintptr_t)scratch & 7u) ||
+        scratch_bytes < cgs_objects_track_gap_scratch_bytes(n, max_objects, max_gap))
+        return CGS_ERR_BADARG;
+    if (h > CGS_OBJ_MAX_SIDE || w > CGS_OBJ_MAX_SIDE || max_objects > OT_MAX_K || n > CGS_OBJ_TRACK_MAX_FRAMES) return CGS_ERR_UNSUPPORTED;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int K = max_objects, hw = h * w, levels = max_gap + 1;
+    const Layout o = layout(n, K);
+    const GapLayout go = gap_layout(n, K);
+    int32_t* s = static_cast<int32_t*>(scratch);
+    int32_t *milli = s + o.milli, *counts = s + o.counts, *best = s + o.best, *root_a = s + o.root_a, *root_b = s + o.root_b,
+            *base = s + o.base, *link = s + go.link;
+    unsigned long long* heads = reinterpret_cast<unsigned long long*>(s + o.heads);
+    unsigned long long* tails = reinterpret_cast<unsigned long long*>(s + go.tails);
+    const unsigned frames4 = blocks_for(n, OT_WAVES);
+
+    const int64_t words = tracks ? (int64_t)max_tracks * CGS_OBJ_TRACK_FIELDS : 0;
+    const int64_t want_blocks = (words + OT_THREADS - 1) / OT_THREADS;
+    const unsigned init_blocks = (unsigned)(want_blocks < 1 ? 1 : want_blocks > 4096 ? 4096 : want_blocks);
+    hipLaunchKernelGGL(track_init_kernel, dim3(init_blocks), dim3(OT_THREADS), 0, stream, tracks, words, totals, milli, (int)iou_milli);
+    CGS_HIP_CHECK_LAUNCH();
+    if (n > 1) {
+        const int rc = cgs_objects_match(labels, labels + hw, n - 1, h, w, K, milli, 1, counts, best, stream_);
+        if (rc != CGS_OK) return rc;
+    }
+    const int32_t* last = labels + (int64_t)(n - 1) * hw;
+    const int rc = cgs_objects_match(last, last, 1, h, w, K, milli, 1, counts + 4 * (int64_t)(n - 1), best + 8 * (int64_t)(n - 1) * K, stream_);
+    if (rc != CGS_OK) return rc;
+    hipLaunchKernelGGL(track_link_kernel, dim3(frames4), dim3(OT_THREADS), 0, stream, best, (int)n, K, (int)iou_milli, prev, root_a, heads,
+                       totals);
+    CGS_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(track_gap_prepare_kernel, dim3(frames4), dim3(OT_THREADS), 0, stream, best, prev, (int)n, K, gap, link, tails,
+                       gap_links, levels, tracks_extra, tracks_extra ? 2 * (int64_t)max_tracks : (int64_t)0);
+    CGS_HIP_CHECK_LAUNCH();
+    for (int g = 2; g <= levels && g <= n - 1; ++g) {                     // a level with no frame pair launches nothing
+        hipLaunchKernelGGL(track_level_kernel, dim3((unsigned)(n - g)), dim3(OT_THREADS), 0, stream, labels, (int)h, (int)w, K, g,
+                           (int)iou_milli, prev, gap, root_a, link, heads, tails, totals);
+        CGS_HIP_CHECK_LAUNCH();
+    }
+    const int total = n * K;
+    for (int reach = 1; reach < n - 1; reach <<= 1) {                     // R rounds, 2^R >= n - 1: a bridged root points further back
+        hipLaunchKernelGGL(track_resolve_kernel, dim3(blocks_for(total, OT_THREADS)), dim3(OT_THREADS), 0, stream, root_a, root_b, total);
+        CGS_HIP_CHECK_LAUNCH();
+        int32_t* swap = root_a;
+        root_a = root_b;
+        root_b = swap;
+    }
+    hipLaunchKernelGGL(track_number_kernel, dim3(1), dim3(OT_SCAN_THREADS), 0, stream, heads, (int)n, base, totals);
+    CGS_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(track_heads_kernel, dim3(frames4), dim3(OT_THREADS), 0, stream, best, heads, base, (int)n, K,
+                       tracks, tracks ? (int)max_tracks : 0);
+    CGS_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(track_gap_table_kernel, dim3(frames4), dim3(OT_THREADS), 0, stream, best, root_a, heads, base, gap, link, (int)n, K,
+                       levels, track, tracks, tracks_extra, (int)max_tracks, totals, gap_links);
+    CGS_HIP_CHECK_LAUNCH();
+    const int64_t pixels = (int64_t)n * hw;
+    hipLaunchKernelGGL(track_paint_kernel, dim3(blocks_for(pixels, OT_THREADS)), dim3(OT_THREADS), 0, stream, labels, track, pixels, hw, K,
+                       track_labels, rgb);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
 }

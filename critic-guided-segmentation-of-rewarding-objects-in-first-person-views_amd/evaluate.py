@@ -159,32 +159,44 @@ def match_report(args, st):
         f"{b['truth_objects']} truth objects, f1 {fmt(first(b)['f1'])}, pq {fmt(first(b)['pq'])}" for pre, b in _blocks(st, report))
 
 
-def _tracked(labelled, iou):
+def _tracked(labelled, iou, gap=0):
     """(Tracks, one side of eval_tracks.json) of a labelled stack: tracked on the GPU, the length histogram and the link sums formed
-    there; only the totals, 7 counts and 3 sums come back."""
+    there; only the totals, 7 counts and 3 sums come back (with --track-gap also the links by gap and the missed frames)."""
     K = MATCH_MAX_OBJECTS
-    tr = objects.track(labelled.labels, iou=iou, max_objects=K)
+    tr = objects.track(labelled.labels, iou=iou, max_objects=K, max_gap=gap)
     totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
+    more = {"max_gap": gap, "gap_links": tr.gap_links, "missed": tr.extra[:, 1].sum(dtype=torch.int64)} if gap else {}
     return tr, objects.track_report(totals, tr.table[:, 2], tr.table[:, 6].sum(dtype=torch.int64), tr.table[:, 7].sum(dtype=torch.int64),
-                                    (labelled.kept - K).clamp(min=0).sum())
+                                    (labelled.kept - K).clamp(min=0).sum(), **more)
 
 
 def tracks_report(args, st):
     """--track-iou: the same objects followed from frame to frame on the GPU; with --match-iou the identity switches at its thresholds,
-    from the matches eval_match.json reports."""
+    from the matches eval_match.json reports.  --track-gap G tracks truth and predictions with the same G (objects.track's max_gap);
+    the switches then follow the truth's adjacent links only, and every threshold's entry gains "fragments" (objects.fragments)."""
     t_iou = objects.parse_track_iou(args.track_iou)
+    gap = int(getattr(args, "track_gap", 0) or 0)
     m_iou = objects.parse_match_iou(args.match_iou) if getattr(args, "match_iou", "") else None
-    truth_tr, truth_side = _tracked(st.labelled("truth"), t_iou)
+    truth_tr, truth_side = _tracked(st.labelled("truth"), t_iou, gap)
     report = _head(args, max_objects=MATCH_MAX_OBJECTS, track_iou=t_iou, truth=truth_side)
+    truth_prev = torch.where(truth_tr.gap == 1, truth_tr.prev, 0) if gap else truth_tr.prev
     for name in st.names(("mask", "crf")):
-        pred_tr, side = _tracked(st.labelled(name), t_iou)
+        pred_tr, side = _tracked(st.labelled(name), t_iou, gap)
         report[name] = {"pred": side}
         if m_iou is not None:
-            counts = objects.switches(truth_tr.prev, pred_tr.track, st.matched(name, m_iou).best, m_iou).cpu().numpy()
+            best = st.matched(name, m_iou).best
+            counts = objects.switches(truth_prev, pred_tr.track, best, m_iou).cpu().numpy()
             report[name]["switches"] = [{"iou": t, "covered": int(c[0]), "continued": int(c[1]), "switches": int(c[2]),
                                          "switch_rate": int(c[2]) / int(c[1]) if c[1] else None} for t, c in zip(m_iou, counts)]
+            if gap:
+                for entry, v in zip(report[name]["switches"], objects.fragments(truth_tr.track, pred_tr.track, best, m_iou).cpu().numpy()):
+                    entry["fragments"] = int(v)
     report = _json_safe(report)
     p = report["mask"]["pred"]
+    if gap:
+        return report, (f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g} gap<={gap}: {p['tracks']} tracks over "
+                        f"{p['objects']} objects ({p['bridged_links']} of {p['links']} links bridged), mean length {fmt(p['mean_length'])}, "
+                        f"longest {p['max_length']}; truth {truth_side['tracks']} tracks over {truth_side['objects']} objects")
     return report, (f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g}: {p['tracks']} tracks over {p['objects']} "
                     f"objects, mean length {fmt(p['mean_length'])}, longest {p['max_length']}; truth {truth_side['tracks']} tracks over "
                     f"{truth_side['objects']} objects")

@@ -572,7 +572,8 @@ class Handler:
         from . import cli, fit, objects, overlay, temporal, video_in
         args = self.args
         track_iou = getattr(args, "overlay_tracks", None)
-        stream = objects.TrackStream(track_iou, max_objects=overlay.MAX_TRACK_OBJECTS) if track_iou is not None else None
+        track_gap = int(getattr(args, "overlay_gap", 0) or 0)                 # --overlay-gap: objects.TrackStream's max_gap
+        stream = objects.TrackStream(track_iou, max_objects=overlay.MAX_TRACK_OBJECTS, max_gap=track_gap) if track_iou is not None else None
         ffmpeg, ffprobe = video_in.find_ffmpeg(), video_in.find_ffprobe()
         W, H, rate = video_in.probe(path, ffprobe)
         k = args.overlay_panels
@@ -688,7 +689,7 @@ class Handler:
                       f"{stem}-objects.json and {stem}-tracks.json are not written")
             tracks = {"tracks": {"iou": track_iou, "min_area": args.overlay_min_area, "boxes": args.overlay_boxes,
                                  "scale": overlay.scale(H, W), "max_objects": overlay.MAX_TRACK_OBJECTS, "n_tracks": int(stream.n_tracks),
-                                 "reports": reports}}
+                                 **({"gap": track_gap} if track_gap else {}), "reports": reports}}
         write_json(f"{out_dir}/{stem}.json", {
             "frame_size": [H, W], "frames": len(M), "rate": rate, "layout": args.overlay_layout, "color": list(args.overlay_color),
             "alpha256": args.overlay_alpha256, "outline": args.overlay_outline, "threshold": thr,

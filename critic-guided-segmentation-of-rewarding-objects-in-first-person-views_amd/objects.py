@@ -11,7 +11,9 @@ up the matched pairs' IoU on the device, and ``parse_match_iou`` / ``match_repor
 threshold, chains resolved on the device), ``switches`` counts identity switches of a prediction's tracks against the truth's, and
 ``parse_track_iou`` / ``natural_order`` / ``track_report`` / ``track_rows`` are the pure host helpers of ``-objects --track-iou``
 (eval_tracks.json, tracks.json).  ``TrackStream`` gives ``track``'s numbers to a label stack that arrives in chunks
-(``-process --source-video --overlay-tracks``); ``stream_remap`` is its arithmetic."""
+(``-process --source-video --overlay-tracks``); ``stream_remap`` is its arithmetic.  With ``max_gap`` G > 0 (``--track-gap``,
+``--overlay-gap``) both bridge gaps of up to G missing frames (cgs_objects_track_gap), and ``fragments`` counts how often a truth
+track is split over several predicted tracks."""
 import re
 from collections import namedtuple
 
@@ -29,7 +31,9 @@ Matches = namedtuple("Matches", ["pred_max", "truth_max", "matched_pred", "match
 TRACK_FIELDS = ("first_frame", "first_label", "length", "area_sum", "area_min", "area_max", "inter_sum", "union_sum")
 TRACK_MAX_FRAMES = _lib.OBJ_TRACK_MAX_FRAMES
 LENGTH_BINS = ("1", "2", "3-4", "5-8", "9-16", "17-32", "33+")             # upper ends 1, 2, 4, 8, 16, 32, then the rest
-Tracks = namedtuple("Tracks", ["prev", "track", "n_tracks", "n_links", "n_objects", "longest", "table", "track_labels", "rgb"])
+TRACK_MAX_GAP = _lib.OBJ_TRACK_MAX_GAP
+Tracks = namedtuple("Tracks", ["prev", "track", "n_tracks", "n_links", "n_objects", "longest", "table", "track_labels", "rgb",
+                               "gap", "gap_links", "extra"], defaults=(None, None, None))
 
 
 def label(src, thresh=None, inclusive=False, connectivity=8, min_area=1, max_objects=64, want_labels=True, want_mask=False):
@@ -187,7 +191,14 @@ def _track_milli(iou):
     return m
 
 
-def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, want_rgb=False):
+def _max_gap(max_gap):
+    max_gap = _as_int(max_gap, "max_gap")
+    if not 0 <= max_gap <= TRACK_MAX_GAP:
+        raise ValueError(f"max_gap must be 0..{TRACK_MAX_GAP}, got {max_gap}")
+    return max_gap
+
+
+def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, want_rgb=False, max_gap=0):
     """labels: int32 device tensor [n,h,w] or [h,w] (then n = 1), 1 <= h, w <= 64, n <= 2^17, a label stack as ``label`` gives it
     (hand-made maps allowed; views are made contiguous).  An object of frame f is a label in 1..max_objects (at most 64) with a pixel
     in f.  Objects p of f and q of f + 1 are linked when each is the other's best partner (``match``'s `best`: largest IoU, ties to the
@@ -198,13 +209,18 @@ def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, w
     [max_tracks,8]: first_frame, first_label, length, area_sum, area_min, area_max, inter_sum, union_sum per track (the last two over
     its links), zero rows from min(n_tracks, max_tracks) on; max_tracks defaults to n * max_objects, which holds every track;
     track_labels int32 [n,h,w] or None: per pixel its object's track, rgb uint8 [n,h,w,3] or None: a colour per track, black where
-    there is none).  No CPU path: raises CgsError without a GPU."""
+    there is none).  No CPU path: raises CgsError without a GPU.
+    max_gap G in 0..8: 0 is the above (cgs_objects_track).  G > 0 bridges up to G missing frames (cgs_objects_track_gap, whose header
+    comment defines the level order): prev then names the label in frame f - gap, longest is the longest span in frames, and the tuple
+    also holds gap int32 [n,K] (0 no link, 1 adjacent, g bridged over g - 1 frames), gap_links int32 [G + 1] (links of gap g at g - 1)
+    and extra int32 [max_tracks,2] (bridges, missed per track; span = length + missed); the three are None at G = 0."""
     if not isinstance(labels, torch.Tensor):
         raise ValueError(f"labels must be a torch tensor, got {type(labels).__name__}")
     if labels.dtype != torch.int32:
         raise ValueError(f"labels must be torch.int32, got {labels.dtype}")
     if labels.dim() not in (2, 3):
         raise ValueError(f"labels must be [n,h,w] or [h,w], got {tuple(labels.shape)}")
+    max_gap = _max_gap(max_gap)
     if labels.dim() == 2:
         labels = labels[None]
     n, h, w = (int(s) for s in labels.shape)
@@ -223,7 +239,8 @@ def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, w
     labels = labels.contiguous()
     dev, K = labels.device, max_objects
     with torch.cuda.device(dev):
-        need = int(_lib.load().cgs_objects_track_scratch_bytes(n, K))
+        need = int(_lib.load().cgs_objects_track_gap_scratch_bytes(n, K, max_gap) if max_gap else
+                   _lib.load().cgs_objects_track_scratch_bytes(n, K))
         scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
         prev = torch.empty((n, K), dtype=torch.int32, device=dev)
         trk = torch.empty((n, K), dtype=torch.int32, device=dev)
@@ -231,6 +248,15 @@ def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, w
         table = torch.empty((max_tracks, len(TRACK_FIELDS)), dtype=torch.int32, device=dev)
         painted = torch.empty((n, h, w), dtype=torch.int32, device=dev) if want_labels else None
         rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev) if want_rgb else None
+        if max_gap:
+            gap = torch.empty((n, K), dtype=torch.int32, device=dev)
+            gap_links = torch.empty(max_gap + 1, dtype=torch.int32, device=dev)
+            extra = torch.empty((max_tracks, 2), dtype=torch.int32, device=dev)
+            _lib.call("cgs_objects_track_gap", labels.data_ptr(), n, h, w, K, milli, max_gap, max_tracks, prev.data_ptr(), gap.data_ptr(),
+                      trk.data_ptr(), totals.data_ptr(), gap_links.data_ptr(), table.data_ptr(), extra.data_ptr(),
+                      painted.data_ptr() if want_labels else None, rgb.data_ptr() if want_rgb else None, scratch.data_ptr(),
+                      scratch.numel() * 8, torch.cuda.current_stream().cuda_stream)
+            return Tracks(prev, trk, totals[0], totals[1], totals[2], totals[3], table, painted, rgb, gap, gap_links, extra)
         _lib.call("cgs_objects_track", labels.data_ptr(), n, h, w, K, milli, max_tracks, prev.data_ptr(), trk.data_ptr(),
                   totals.data_ptr(), table.data_ptr(), painted.data_ptr() if want_labels else None, rgb.data_ptr() if want_rgb else None,
                   scratch.data_ptr(), scratch.numel() * 8, torch.cuda.current_stream().cuda_stream)
@@ -243,11 +269,14 @@ def stream_remap(local, carried_local, carried_global, c0, n_tracks):
     these are 1..c0 in label order); carried_global: int [K], the carried frame's numbers in the stream; c0: the carried frame's object
     count; n_tracks: the stream's tracks before this chunk (both scalars, tensors or ints).  A local number t of a carried object maps
     to that object's number, every other t to n_tracks + (t - c0) -- heads are numbered by frame, then label, in both -- and 0 to 0.
-    Returns int64 [m,K].  torch gather / scatter on the tensors' device, no synchronisation."""
-    local, carried_local = local.to(torch.int64), carried_local.to(torch.int64)
+    Returns int64 [m,K].  torch gather / scatter on the tensors' device, no synchronisation.
+    Behind c carried frames (``TrackStream`` with max_gap = c - 1): carried_local and carried_global are [c,K], rows c.. are local and
+    c0 is the number of local tracks whose first frame is carried (they are 1..c0, and each holds a carried object).  Links inside
+    the carried frames are the stream's own, so carried objects that share a local number share their stream number."""
+    local, carried_local = local.to(torch.int64), carried_local.to(torch.int64).reshape(-1)
     size = local.shape[0] * local.shape[1] + carried_local.shape[0] + 1           # more than the largest local number
     lut = torch.arange(size, dtype=torch.int64, device=local.device) - c0 + n_tracks
-    lut.scatter_(0, carried_local, carried_global.to(torch.int64))                # (an absent object writes 0 at 0)
+    lut.scatter_(0, carried_local, carried_global.to(torch.int64).reshape(-1))    # (an absent object writes 0 at 0)
     lut[0] = 0
     return lut[local]
 
@@ -256,16 +285,19 @@ class TrackStream:
     """``track`` for a label stack that comes in chunks: for every split of a stack, the concatenated results of ``push`` are
     ``track(stack, iou, max_objects).track`` bit for bit.  A link depends on its two frames only and tracks are numbered by their first
     frame, then label, so the last frame of a chunk (its labels and its numbers) is all that the next chunk needs.  ``n_tracks`` is the
-    number of tracks so far, an int32 scalar on the device (0 before the first push); nothing here synchronises with the host."""
+    number of tracks so far, an int32 scalar on the device (0 before the first push); nothing here synchronises with the host.
+    With max_gap = G > 0 a link (f - g -> f), g <= G + 1, depends on the frames f - g .. f only, so the last G + 1 frames pushed are
+    carried (fewer while the stream is shorter than that): G frames are not enough, a chunk's first frame may reach G + 1 back."""
 
-    def __init__(self, iou, max_objects=64):
+    def __init__(self, iou, max_objects=64, max_gap=0):
         self.milli = _track_milli(iou)
         self.iou = self.milli / 1000
         self.max_objects = _as_int(max_objects, "max_objects")
         if not 1 <= self.max_objects <= MATCH_MAX_OBJECTS:
             raise ValueError(f"max_objects must be 1..{MATCH_MAX_OBJECTS}, got {max_objects}")
+        self.max_gap = _max_gap(max_gap)
         self.n_tracks = 0
-        self._carry = None                     # (labels [1,h,w], numbers int32 [K], object count) of the last frame pushed
+        self._carry = None                     # (labels [c,h,w], numbers int32 [c,K]) of the last c <= max_gap + 1 frames pushed
 
     def push(self, labels):
         """labels: int32 device tensor [m,h,w], m >= 1, of the shape and on the device of the first push, m + 1 <= 2^17.  Returns int32
@@ -274,20 +306,25 @@ class TrackStream:
             raise ValueError("labels must be an int32 tensor [m,h,w] with at least one frame, got "
                              + (f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, torch.Tensor) else type(labels).__name__))
         m = int(labels.shape[0])
-        if m + 1 > TRACK_MAX_FRAMES:
-            raise ValueError(f"a chunk of {m} frames: with the carried frame at most {TRACK_MAX_FRAMES} are tracked at once")
+        keep = self.max_gap + 1
+        if m + keep > TRACK_MAX_FRAMES:
+            raise ValueError(f"a chunk of {m} frames: with the carried frame{'s' if keep > 1 else ''} at most {TRACK_MAX_FRAMES} are "
+                             "tracked at once")
         if self._carry is None:
-            tr = track(labels, iou=self.iou, max_objects=self.max_objects, max_tracks=1)
+            tr = track(labels, iou=self.iou, max_objects=self.max_objects, max_tracks=1, max_gap=self.max_gap)
             ids, self.n_tracks = tr.track, tr.n_tracks
+            self._carry = (labels[-keep:].contiguous().clone(), ids[-keep:].clone())
         else:
-            last, last_ids, c0 = self._carry
+            last, last_ids = self._carry
             if labels.shape[1:] != last.shape[1:] or labels.device != last.device:
                 raise ValueError(f"labels {tuple(labels.shape)} on {labels.device}: the stream holds frames of {tuple(last.shape[1:])} on "
                                  f"{last.device}")
-            tr = track(torch.cat((last, labels)), iou=self.iou, max_objects=self.max_objects, max_tracks=1)
-            ids = stream_remap(tr.track[1:], tr.track[0], last_ids, c0, self.n_tracks).to(torch.int32)
+            c = int(last.shape[0])
+            tr = track(torch.cat((last, labels)), iou=self.iou, max_objects=self.max_objects, max_tracks=1, max_gap=self.max_gap)
+            c0 = tr.track[:c].max()            # tracks are numbered by first frame: those headed in the carry are 1..c0
+            ids = stream_remap(tr.track[c:], tr.track[:c], last_ids, c0, self.n_tracks).to(torch.int32)
             self.n_tracks = (self.n_tracks + tr.n_tracks - c0).to(torch.int32)
-        self._carry = (labels[-1:].contiguous().clone(), ids[-1].clone(), (ids[-1] > 0).sum())
+            self._carry = (torch.cat((last, labels))[-keep:].contiguous().clone(), torch.cat((last_ids, ids))[-keep:].clone())
         return ids
 
 
@@ -295,7 +332,9 @@ def switches(truth_prev, pred_track, best, iou):
     """truth_prev: ``track(truth).prev``, pred_track: ``track(pred).track``, both int32 [n,K]; best: ``match(pred, truth).best`` int32
     [n,2,K,4], all on one device; iou as ``match`` takes it.  int32 [T,3] on the device, per threshold (covered: truth objects whose best
     predicted partner reaches it, continued: truth links with both ends covered, switches: continued links whose two predicted partners
-    lie in different predicted tracks).  Gaps are not bridged: an uncovered frame ends the comparison there."""
+    lie in different predicted tracks).  Gaps are not bridged: an uncovered frame ends the comparison there.  The kernel reads
+    truth_prev as "the label in frame f - 1", so with tracks of ``max_gap`` > 0 pass ``torch.where(tr.gap == 1, tr.prev, 0)``; what
+    bridging buys shows in ``fragments``."""
     for name, t in (("truth_prev", truth_prev), ("pred_track", pred_track), ("best", best)):
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
@@ -322,7 +361,49 @@ def switches(truth_prev, pred_track, best, iou):
     return counts
 
 
+def fragments(truth_track, pred_track, best, iou):
+    """truth_track: ``track(truth).track``, pred_track: ``track(pred).track``, int32 [n,K]; best: ``match(pred, truth).best`` int32
+    [n,2,K,4], all on one device; iou as ``match`` takes it.  int64 [T] on that device: per matching threshold, over the covered truth
+    objects (those whose best predicted partner reaches it), the number of distinct (truth track, predicted track) pairs less the
+    number of distinct truth tracks -- 0 when every truth track is followed by one predicted track.  torch.unique on the device."""
+    for name, t in (("truth_track", truth_track), ("pred_track", pred_track), ("best", best)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != torch.int32:
+            raise ValueError(f"{name} must be torch.int32, got {t.dtype}")
+    if truth_track.dim() != 2 or truth_track.shape != pred_track.shape:
+        raise ValueError(f"truth_track and pred_track must be [n,K] of one shape, got {tuple(truth_track.shape)} and "
+                         f"{tuple(pred_track.shape)}")
+    n, K = (int(s) for s in truth_track.shape)
+    if n < 1 or K < 1 or tuple(best.shape) != (n, 2, K, 4):
+        raise ValueError(f"[n,K] = [{n},{K}] needs best [{n},2,{K},4], got {tuple(best.shape)}")
+    if not truth_track.device == pred_track.device == best.device:
+        raise ValueError("truth_track, pred_track and best are on different devices")
+    milli = iou_milli(iou)
+    row = best[:, 1].to(torch.int64)                                              # (pred partner, inter, area_t, area_p) per truth object
+    partner, inter, union = row[..., 0], row[..., 1], row[..., 2] + row[..., 3] - row[..., 1]
+    tt = truth_track.to(torch.int64)
+    pt = torch.gather(pred_track.to(torch.int64), 1, (partner - 1).clamp(0, K - 1))
+    base = int(n) * K + 1                                                         # more than any track number
+    out = []
+    for m in milli:
+        cov = (partner >= 1) & (partner <= K) & (tt > 0) & (inter > 0) & (1000 * inter >= m * union)
+        out.append(torch.unique(tt[cov] * base + pt[cov]).numel() - torch.unique(tt[cov]).numel())
+    return torch.tensor(out, dtype=torch.int64, device=best.device)
+
+
 # ---------------------------------------------------------------------------------------------------------------- host helpers
+def parse_track_gap(s, flag="--track-gap"):
+    """``--track-gap`` / ``--overlay-gap``: a whole number 0..8 (objects.TRACK_MAX_GAP).  Returns the int; ValueError otherwise."""
+    try:
+        g = int(str(s).strip())
+    except ValueError:
+        raise ValueError(f"{flag} {s!r}: expected a whole number 0..{TRACK_MAX_GAP}") from None
+    if not 0 <= g <= TRACK_MAX_GAP:
+        raise ValueError(f"{flag} {g}: expected a whole number 0..{TRACK_MAX_GAP}")
+    return g
+
+
 def parse_track_iou(s):
     """``--track-iou``: one number in (0, 1], a whole number of thousandths.  Returns it as a float; ValueError otherwise."""
     s = str(s).strip()
@@ -361,12 +442,14 @@ def length_hist(lengths):
     return np.bincount(np.searchsorted(np.array([1, 2, 4, 8, 16, 32]), v, side="left"), minlength=len(LENGTH_BINS))
 
 
-def track_report(totals, lengths, inter_sum=0, union_sum=0, untracked=0):
+def track_report(totals, lengths, inter_sum=0, union_sum=0, untracked=0, max_gap=0, gap_links=None, missed=0):
     """One side of eval_tracks.json / tracks.json.  totals: (tracks, links, objects, longest) of ``track``; lengths: the table's length
     column (a tensor is binned where it is and only the 7 counts come to the host); inter_sum, union_sum: the sums of those columns;
     untracked: objects numbered above max_objects.  {"objects", "untracked_objects", "tracks", "links", "singletons", "mean_length":
     objects / tracks, "max_length", "length_hist": {"1", "2", "3-4", "5-8", "9-16", "17-32", "33+"}, "link_iou": inter_sum / union_sum};
-    a ratio with a zero denominator is None."""
+    a ratio with a zero denominator is None.  With max_gap G > 0 (gap_links: ``track``'s, missed: the sum of its extra's second
+    column) the fourth total is the longest span: "max_length" is then the largest length, and the dict gains "track_gap": G,
+    "bridged_links", "missed_frames", "links_by_gap": {"1", ..., "G+1"} and "max_span"."""
     n_tracks, n_links, n_objects, longest = (int(v) for v in _host(totals).reshape(-1))
     hist = [int(v) for v in _host(length_hist(lengths))]
     inter_sum, union_sum, untracked = int(inter_sum), int(union_sum), int(untracked)
@@ -375,15 +458,30 @@ def track_report(totals, lengths, inter_sum=0, union_sum=0, untracked=0):
     if sum(hist) != n_tracks:
         raise ValueError(f"the length column holds {sum(hist)} tracks, the totals say {n_tracks}")
     ratio = lambda a, b: a / b if b else None
-    return {"objects": n_objects, "untracked_objects": untracked, "tracks": n_tracks, "links": n_links, "singletons": hist[0],
+    side = {"objects": n_objects, "untracked_objects": untracked, "tracks": n_tracks, "links": n_links, "singletons": hist[0],
             "mean_length": ratio(n_objects, n_tracks), "max_length": longest, "length_hist": dict(zip(LENGTH_BINS, hist)),
             "link_iou": ratio(inter_sum, union_sum)}
+    max_gap = _max_gap(max_gap)
+    if max_gap:
+        by_gap = [int(v) for v in _host(gap_links).reshape(-1)]
+        if len(by_gap) != max_gap + 1 or min(by_gap) < 0 or sum(by_gap) != n_links or int(missed) < 0:
+            raise ValueError(f"gap_links {by_gap} must be {max_gap + 1} counts that add up to the {n_links} links")
+        lengths = _host(lengths).reshape(-1)
+        side.update({"max_length": int(lengths.max()) if lengths.size else 0, "track_gap": max_gap, "bridged_links": sum(by_gap[1:]),
+                     "missed_frames": int(missed), "links_by_gap": {str(g + 1): v for g, v in enumerate(by_gap)}, "max_span": longest})
+    return side
 
 
-def track_rows(table, n_tracks):
+def track_rows(table, n_tracks, extra=None):
     """table [max_tracks,8] (tensor or array) -> the first min(n_tracks, max_tracks) tracks as {"track", "first_frame", "first_label",
-    "length", "area_sum", "area_min", "area_max", "inter_sum", "union_sum", "link_iou": inter_sum / union_sum (None for a singleton)}."""
+    "length", "area_sum", "area_min", "area_max", "inter_sum", "union_sum", "link_iou": inter_sum / union_sum (None for a singleton)}.
+    extra [max_tracks,2] (``track``'s with max_gap > 0): the rows gain "bridges", "missed" and "last_frame" = first_frame + length +
+    missed - 1."""
     table = _host(table)
+    if extra is not None:
+        extra = _host(extra)
+        if extra.shape != (table.shape[0], 2):
+            raise ValueError(f"extra {extra.shape} must be [{table.shape[0]}, 2]")
     if table.ndim != 2 or table.shape[1] != len(TRACK_FIELDS):
         raise ValueError(f"table {table.shape} must be [max_tracks, {len(TRACK_FIELDS)}]")
     n_tracks = int(n_tracks)
@@ -393,6 +491,8 @@ def track_rows(table, n_tracks):
     for t in range(min(n_tracks, table.shape[0])):
         row = {"track": t + 1, **{k: int(v) for k, v in zip(TRACK_FIELDS, table[t])}}
         row["link_iou"] = row["inter_sum"] / row["union_sum"] if row["union_sum"] else None
+        if extra is not None:
+            row.update(bridges=int(extra[t, 0]), missed=int(extra[t, 1]), last_frame=row["first_frame"] + row["length"] + int(extra[t, 1]) - 1)
         rows.append(row)
     return rows
 

@@ -90,7 +90,7 @@ def video_reports(args, M, stem, device, rank):
     stems = [f"{i:06d}" for i in range(len(M))]
     names = (f"{stem}-objects.json", f"{stem}-tracks.json")
     _objects(args, res, head, stems, M.shape[-1], rank, png=False, name=names[0])
-    _tracks(args, res, head, stems, rank, png=False, name=names[1], iou=args.overlay_tracks)
+    _tracks(args, res, head, stems, rank, png=False, name=names[1], iou=args.overlay_tracks, gap=int(getattr(args, "overlay_gap", 0) or 0))
     return list(names)
 
 
@@ -112,29 +112,36 @@ def _objects(args, res, head, stems, width, rank, png=True, name="objects.json")
         Image.fromarray(np.repeat((mask[i] * np.uint8(255))[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-objects-mask.png")
 
 
-def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None):
+def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None, gap=None):
     """The objects objects.json describes followed through the frames in natural order of their names on the GPU (objects.track);
     labels above 64 are untracked.  Rank 0 writes {R}/tracks.json and per frame {R}/{stem}-tracks-mask.png, a colour per track
-    (png=False: the report alone, as {R}/{name}; iou: the link threshold when it is not --track-iou's)."""
+    (png=False: the report alone, as {R}/{name}; iou, gap: the link threshold and the gap when they are not --track-iou's and
+    --track-gap's).  With a gap G > 0 (objects.track's max_gap) the report also holds "track_gap", the summary's and the tracks' gap
+    keys and per object its "gap"; "last" is then the track's last frame, missed frames counted."""
     from PIL import Image
     K, iou = MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou) if iou is None else iou
+    gap = int(getattr(args, "track_gap", 0) or 0) if gap is None else gap
     order = objects.natural_order(stems)                             # os.listdir's order is arbitrary; only the label stack is reordered
     pick = torch.tensor(order, dtype=torch.int64, device=res.labels.device)
-    tr = objects.track(res.labels[pick], iou=iou, max_objects=K, want_rgb=png)
+    tr = objects.track(res.labels[pick], iou=iou, max_objects=K, want_rgb=png, max_gap=gap)
     if rank != 0:
         return
     totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
+    more = {"max_gap": gap, "gap_links": tr.gap_links, "missed": tr.extra[:, 1].sum(dtype=torch.int64)} if gap else {}
     side = objects.track_report(totals, tr.table[:, 2], tr.table[:, 6].sum(dtype=torch.int64), tr.table[:, 7].sum(dtype=torch.int64),
-                                (res.kept[pick] - K).clamp(min=0).sum())
-    rows = objects.track_rows(tr.table, side["tracks"])
+                                (res.kept[pick] - K).clamp(min=0).sum(), **more)
+    rows = objects.track_rows(tr.table, side["tracks"], tr.extra)
     names = [stems[i] for i in order]
     prev, trk = tr.prev.cpu().numpy(), tr.track.cpu().numpy()
-    report = {**head, "max_objects": K, "track_iou": iou, "summary": side, "order": names,
-              "frames": {stem: [{"label": int(l) + 1, "track": int(trk[j, l]), "prev": int(prev[j, l])} for l in np.flatnonzero(trk[j])]
+    gaps = tr.gap.cpu().numpy() if gap else None
+    last = (lambda r: r["last_frame"]) if gap else (lambda r: r["first_frame"] + r["length"] - 1)
+    report = {**head, "max_objects": K, "track_iou": iou, **({"track_gap": gap} if gap else {}), "summary": side, "order": names,
+              "frames": {stem: [{"label": int(l) + 1, "track": int(trk[j, l]), "prev": int(prev[j, l]),
+                                 **({"gap": int(gaps[j, l])} if gap else {})} for l in np.flatnonzero(trk[j])]
                          for j, stem in enumerate(names)},
-              "tracks": [{"track": r["track"], "first": names[r["first_frame"]], "last": names[r["first_frame"] + r["length"] - 1],
+              "tracks": [{"track": r["track"], "first": names[r["first_frame"]], "last": names[last(r)],
                           "length": r["length"], "area_sum": r["area_sum"], "area_min": r["area_min"], "area_max": r["area_max"],
-                          "link_iou": r["link_iou"]} for r in rows]}
+                          "link_iou": r["link_iou"], **({"bridges": r["bridges"], "missed": r["missed"]} if gap else {})} for r in rows]}
     out_dir = args.mask_output_imgs
     write_json(f"{out_dir}/{name}", report)
     if not png:

@@ -911,6 +911,38 @@ int cgs_objects_track_switches(const int32_t* truth_prev, const int32_t* pred_tr
                                const int32_t* iou_milli, int32_t T, int32_t n, int32_t max_objects, int32_t* counts,
                                cgs_stream_t stream);
 
+/* cgs_objects_track_gap: cgs_objects_track that bridges gaps of up to max_gap = G missing frames (0..CGS_OBJ_TRACK_MAX_GAP; 8 is a
+ * judgement -- long enough for a hand swinging across an object, short enough that one threshold still means "the same thing" -- not
+ * a measured value).  Linking runs in levels g = 1 .. G + 1, all links of a level before any of the next:
+ *   level 1     cgs_objects_track's rule and path, unchanged.
+ *   level g>=2  for every frame f >= g on its own: the open tails of f - g (objects without a successor from a level < g) against the
+ *               open heads of f (objects without a predecessor from a level < g), every other label read as background in both frames;
+ *               then the same rule on the two masked frames: best partners among the open objects only, mutual best, inter > 0 &&
+ *               1000 inter >= iou_milli union with the inter and union of the two masks g frames apart.  A link closes both ends.
+ * So a shorter gap always beats a longer one, and an object that is already taken does not block a bridge (masking comes before the
+ * best-partner search).  Within a level frame f touches only the heads of f and the tails of f - g: one launch per level, one
+ * workgroup per frame pair, no label stack copied.  A track is a maximal chain of links of any gap, numbered as in cgs_objects_track.
+ *   prev       int32 [n][K]: the label in frame f - gap that the object continues, 0 for a head
+ *   gap        int32 [n][K]: 0 no link, 1 adjacent, g bridged over g - 1 missing frames
+ *   totals     int32 [4]: tracks, links of any gap, objects, the longest span in frames, max(f - first_frame + 1) (without gaps: the
+ *              longest length)
+ *   gap_links  int32 [max_gap + 1]: the number of links of gap g at index g - 1
+ *   tracks     as cgs_objects_track: length counts objects, inter_sum and union_sum run over all links, bridged ones included
+ *   tracks_extra  int32 [max_tracks][2] or NULL: bridges (links of gap > 1) and missed (sum of gap - 1); span = length + missed
+ *   track, track_labels, rgb  as cgs_objects_track
+ *   scratch    8-byte aligned, at least cgs_objects_track_gap_scratch_bytes(n, max_objects, max_gap) bytes (0 for a bad argument)
+ * With max_gap = 0 every output shared with cgs_objects_track is bit-identical to it.  8 + R + (n > 1) + min(G, n - 1) launches (a level
+ * with no frame pair launches nothing), a function of n and G alone; no synchronisation, nothing allocated, all integer, global atomics
+ * add / min / max only.  gap and gap_links not NULL and 4-byte aligned, max_gap in 0..8, else CGS_ERR_BADARG; every other limit and
+ * return code is cgs_objects_track's.  For cgs_objects_track_switches pass the truth's prev with the entries of gap != 1 set to 0: it
+ * reads prev as "in frame f - 1".                                                                                                      */
+enum { CGS_OBJ_TRACK_MAX_GAP = 8 };
+int64_t cgs_objects_track_gap_scratch_bytes(int32_t n, int32_t max_objects, int32_t max_gap);
+int cgs_objects_track_gap(const int32_t* labels, int32_t n, int32_t h, int32_t w, int32_t max_objects, int32_t iou_milli,
+                          int32_t max_gap, int32_t max_tracks, int32_t* prev, int32_t* gap, int32_t* track, int32_t* totals,
+                          int32_t* gap_links, int32_t* tracks, int32_t* tracks_extra, int32_t* track_labels, uint8_t* rgb,
+                          void* scratch, int64_t scratch_bytes, cgs_stream_t stream);
+
 /* ---- the saliency baseline over a threshold grid (csrc/saliency.hip; Handler._saliency_post, main.py:976-1003; this build's own
  * -eval -salience --salience-grid) -----------------------------------------------------------------------------------------------------
  * The baseline's whole post-processing for T thresholds at once, each threshold with its own normaliser as the host form has it.  A
