@@ -46,6 +46,9 @@ def build_parser():
     # (this build's own flag) --track-iou T --track-gap G: an object may be missing for up to G frames (0..8, default 0) and keeps its
     # track (objects.track's max_gap); check_objects_flags turns it into an int
     p.add_argument("--track-gap", type=str, default=None)
+    # (this build's own flag) --track-iou T --track-motion S: the earlier frame's labels are carried along block vectors of the 64 x 64
+    # frames, up to S cells a frame (0..4, default 0 = off), before they are compared (objects.track's motion); an int after the check
+    p.add_argument("--track-motion", type=str, default=None)
     # (this build's own flag) -eval --boundary-tol "0-1-2-3" or "lo:hi:n": every evaluated stack's outline against the truth's outline at
     # these tolerances in pixels -- boundary F, boundary IoU and the Hausdorff distance -- on the GPU (boundary.score); leaves
     # {model}/eval_boundary.json
@@ -65,7 +68,8 @@ def build_parser():
     # objects through the stream at link IoU T (objects.TrackStream) and draws every object in its track's colour with its bounding box,
     # --overlay-boxes B pixels thick (0: none), and its track number (overlay.compose_tracks); leaves {R}/{stem}-objects.json and
     # {R}/{stem}-tracks.json.  A and B default to 1.  --overlay-gap G (0..8, default 0) is --track-gap for this stream: an object that
-    # has no mask for up to G frames comes back under its number and colour
+    # has no mask for up to G frames comes back under its number and colour.  --overlay-motion S (0..4, default 0) is --track-motion for
+    # this stream: the labels are carried along block vectors of the shrunk frames before they are compared
     p.add_argument("--source-video", type=str, default="")
     p.add_argument("--overlay-video", type=str, default="")
     p.add_argument("--smooth", type=int, default=None)
@@ -79,6 +83,7 @@ def build_parser():
     p.add_argument("--overlay-min-area", type=int, default=None)
     p.add_argument("--overlay-boxes", type=int, default=None)
     p.add_argument("--overlay-gap", type=str, default=None)
+    p.add_argument("--overlay-motion", type=str, default=None)
     for flag in ("-masker", "-critic", "-cload", "-mload", "-staticnorm", "-visbesteval", "-salglobal"):
         p.add_argument(flag, type=bool, default=True)
     p.add_argument("--salience-thresh", type=float, default="1.5")
@@ -166,9 +171,10 @@ def check_sweep_flags(args):
 
 
 def check_objects_flags(args):
-    """-objects / --min-area / --connectivity / --match-iou / --track-iou / --track-gap / --boundary-tol: combinations that could not
-    run and a malformed --match-iou, --track-iou, --track-gap or --boundary-tol are refused here, before any GPU work; the defaults
-    (--min-area 1, --connectivity 8, --track-gap 0 as an int) are filled in.  --boundary-tol needs -eval, not -objects."""
+    """-objects / --min-area / --connectivity / --match-iou / --track-iou / --track-gap / --track-motion / --boundary-tol: combinations
+    that could not run and a malformed --match-iou, --track-iou, --track-gap, --track-motion or --boundary-tol are refused here, before
+    any GPU work; the defaults (--min-area 1, --connectivity 8, --track-gap 0 and --track-motion 0 as ints) are filled in.
+    --boundary-tol needs -eval, not -objects."""
     given = [f for f, v in (("--min-area", args.min_area), ("--connectivity", args.connectivity)) if v is not None]
     if args.match_iou:
         from .objects import parse_match_iou
@@ -194,6 +200,13 @@ def check_objects_flags(args):
         args.track_gap = parse_track_gap(args.track_gap)
     else:
         args.track_gap = 0
+    if args.track_motion is not None:
+        from .objects import parse_track_motion
+        if not args.track_iou:
+            raise ValueError("--track-motion belongs to --track-iou: give --track-iou T")
+        args.track_motion = parse_track_motion(args.track_motion)
+    else:
+        args.track_motion = 0
     if not args.objects:
         if given:
             raise ValueError(f"{' / '.join(given)} belong to -objects: give -objects")
@@ -233,7 +246,7 @@ def check_fit_flags(args):
 def check_video_flags(args):
     """--source-video / --overlay-video and the --smooth* / --overlay-* options: combinations that could not run and values out of range
     are refused here, before any GPU work; the defaults (--smooth 0, --smooth-range 16, --smooth-motion 0, --overlay-layout overlay,
-    --overlay-color 0,255,0, --overlay-alpha 0.5, --overlay-outline 1; with --overlay-tracks T also --overlay-min-area 1, --overlay-boxes 1, --overlay-gap 0) are filled
+    --overlay-color 0,255,0, --overlay-alpha 0.5, --overlay-outline 1; with --overlay-tracks T also --overlay-min-area 1, --overlay-boxes 1, --overlay-gap 0, --overlay-motion 0) are filled
     in, --overlay-color becomes (r, g, b), args.overlay_alpha256 is round(256 alpha), --overlay-tracks becomes a float (None without the
     flag), and -fit is switched on: a video goes through the -fit machinery.  The frame size is checked after the probe
     (check_video_size)."""
@@ -242,7 +255,8 @@ def check_video_flags(args):
                             ("--overlay-layout", args.overlay_layout), ("--overlay-color", args.overlay_color),
                             ("--overlay-alpha", args.overlay_alpha), ("--overlay-outline", args.overlay_outline),
                             ("--overlay-tracks", args.overlay_tracks), ("--overlay-min-area", args.overlay_min_area),
-                            ("--overlay-boxes", args.overlay_boxes), ("--overlay-gap", args.overlay_gap)) if v is not None]
+                            ("--overlay-boxes", args.overlay_boxes), ("--overlay-gap", args.overlay_gap),
+                            ("--overlay-motion", args.overlay_motion)) if v is not None]
     if not args.source_video:
         if given:
             raise ValueError(f"{' / '.join(given)} belong to --source-video: give --source-video")
@@ -279,7 +293,7 @@ def check_video_flags(args):
                                  overlay.OUTLINE if args.overlay_outline is None else args.overlay_outline)
     if args.overlay_tracks is None:
         extra = [f for f, v in (("--overlay-min-area", args.overlay_min_area), ("--overlay-boxes", args.overlay_boxes),
-                                ("--overlay-gap", args.overlay_gap)) if v is not None]
+                                ("--overlay-gap", args.overlay_gap), ("--overlay-motion", args.overlay_motion)) if v is not None]
         if extra:
             raise ValueError(f"{' / '.join(extra)} belong to --overlay-tracks: give --overlay-tracks T")
     else:
@@ -296,6 +310,8 @@ def check_video_flags(args):
         args.overlay_boxes = named("--overlay-boxes", overlay.check_boxes, overlay.BOXES if args.overlay_boxes is None else args.overlay_boxes)
         from .objects import parse_track_gap
         args.overlay_gap = 0 if args.overlay_gap is None else parse_track_gap(args.overlay_gap, "--overlay-gap")
+        from .objects import parse_track_motion
+        args.overlay_motion = 0 if args.overlay_motion is None else parse_track_motion(args.overlay_motion, "--overlay-motion")
     args.fit = True
 
 

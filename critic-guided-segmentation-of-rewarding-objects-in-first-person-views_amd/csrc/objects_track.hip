@@ -21,6 +21,10 @@
 //
 // cgs_objects_track_gap bridges gaps of up to G missing frames: the path above as level 1, then per level g = 2 .. G + 1 one launch of
 // track_level_kernel over the frame pairs (f - g, f); see "bridged gaps" below and DESIGN.md.
+//
+// cgs_objects_track_mc is the same path with the earlier frame's labels carried along a block motion field before they are counted:
+// track_level_kernel<true> gathers them in LDS, at level 1 too (there it writes `best` in objects_match_kernel's layout); see "carried
+// labels" below.  Everything after the counting is the kernels above and below, called as they are.
 #include "pixel_common.h"
 
 namespace {
@@ -287,15 +291,41 @@ track_gap_prepare_kernel(const int32_t* __restrict__ best, const int32_t* __rest
 // One workgroup, one frame pair (a, a + g): objects_match_kernel's count and its two scans over the open tails of a and the open heads
 // of a + g, every other label read as 0.  The words of frame a + g's heads and frame a's tails belong to this workgroup alone within
 // the launch.  A pair with no open tail or no open head has nothing to link and reads no pixel.
+//
+// carried labels (MC, cgs_objects_track_mc).  The workgroup first stages frame a's labels in LDS, a byte per cell, already clamped and
+// masked, and the g tables bwd[f - 1] .. bwd[a] (2 bytes a block).  A lane then walks its 16 cells q = (y, x) of frame f back along
+// them (cgs_temporal_smooth_mc's path for k < 0: each step reads the table at the clamped cell; the 16 walks run side by side, so a
+// step's LDS latency is paid once, not 16 times) and takes the staged label at q + m_g, 0 outside the grid, into a second plane W: a
+// gather, so the count below is unchanged -- its "area of a" is now the number of cells that hold the carried label.
+// The vector is constant over a block's 8 cells, so a carried run is not cut where the source run was whole.  Every read is bounded for
+// any int8 field: the table index comes from a clamped cell, the label index is checked, |m| <= 9 * 128.
+// At g = 1 with MC the pair is counted over every object of both frames (no words of open ends exist yet) and, instead of linking, the
+// workgroup writes slot a of `best` as objects_match_kernel would: side 0 (partner, inter, TRUE own area, partner's area), side 1
+// (partner, inter, own area, CARRIED area of the partner), so that the link kernel's row[2] + row[3] - row[1] is the union compared
+// and every reader of best[f][0][l][2] still finds the object's area.  The true areas are counted while frame a is staged.
+constexpr int OT_SIDE = CGS_TEMPORAL_SIDE;
+constexpr int OT_BLOCKS = OT_SIDE / CGS_TEMPORAL_BLOCK;
+constexpr int OT_MAX_LEVELS = CGS_OBJ_TRACK_MAX_GAP + 1;
+constexpr int OT_ROWS = OT_SIDE / OT_WAVES;             // rows of a frame per lane
+static_assert(OT_SIDE == CGS_OBJ_MAX_SIDE && CGS_TEMPORAL_BLOCK == 8 && OT_MAX_K < 256, "a staged label is a byte, a block 8 cells");
+
+template <bool MC>
 __global__ void __launch_bounds__(OT_THREADS)
-track_level_kernel(const int32_t* __restrict__ labels, int h, int w, int K, int g, int iou, int32_t* __restrict__ prev,
-                   int32_t* __restrict__ gap, int32_t* __restrict__ root, int32_t* __restrict__ link, unsigned long long* __restrict__ heads,
-                   unsigned long long* __restrict__ tails, int32_t* __restrict__ totals) {
+track_level_kernel(const int32_t* __restrict__ labels, const int8_t* __restrict__ bwd, int h, int w, int K, int g, int iou,
+                   int32_t* __restrict__ prev, int32_t* __restrict__ gap, int32_t* __restrict__ root, int32_t* __restrict__ link,
+                   unsigned long long* __restrict__ heads, unsigned long long* __restrict__ tails, int32_t* __restrict__ totals,
+                   int32_t* __restrict__ best) {
     __shared__ __attribute__((aligned(16))) int s_I[OT_CELLS];           // [tail - 1][head - 1], row stride 65
     __shared__ int s_A[2][OT_MAX_K];                                     // area of the tails, of the heads
     __shared__ int s_best[2][OT_MAX_K];
+    __shared__ int s_true[MC ? OT_MAX_K : 1];                            // MC, g = 1: the areas of frame a's objects where they are
+    __shared__ uint8_t s_L[MC ? OT_SIDE * OT_SIDE : 1];                  // MC: frame a's labels, clamped and masked
+    __shared__ uint16_t s_m[MC ? OT_MAX_LEVELS : 1][OT_BLOCKS * OT_BLOCKS];      // MC: [j] = bwd[f - j - 1], dy | dx << 8
+    __shared__ uint8_t s_W[MC ? OT_SIDE * OT_SIDE : 1];                  // MC: the carried labels, W of the header
     const int a = blockIdx.x, f = a + g;
-    const unsigned long long tmask = tails[a], hmask = heads[f];
+    const bool pairs = MC && g == 1;                                     // level 1 of the motion path: all objects, rows of `best`
+    const unsigned long long all = K >= 64 ? ~0ull : (1ull << K) - 1ull;
+    const unsigned long long tmask = pairs ? all : tails[a], hmask = pairs ? all : heads[f];
     if (!tmask || !hmask) return;                                        // uniform over the workgroup
     const int x = threadIdx.x & (CGS_WAVE - 1), wave = threadIdx.x / CGS_WAVE;
     const bool live = x < w;
@@ -304,19 +334,67 @@ track_level_kernel(const int32_t* __restrict__ labels, int h, int w, int K, int 
 
     for (int j = threadIdx.x; j < OT_CELLS / 4; j += OT_THREADS) reinterpret_cast<int4*>(s_I)[j] = make_int4(0, 0, 0, 0);
     if (threadIdx.x < 2 * OT_MAX_K) (&s_A[0][0])[threadIdx.x] = 0;
+    if (MC && threadIdx.x < OT_MAX_K) s_true[threadIdx.x] = 0;
     __syncthreads();
+
+    if constexpr (MC) {                                                  // h = w = 64 here: every lane is live
+#pragma unroll
+        for (int k = 0; k < (OT_MAX_LEVELS * OT_BLOCKS * OT_BLOCKS + OT_THREADS - 1) / OT_THREADS; ++k) {
+            const int i = threadIdx.x + k * OT_THREADS;
+            if (i < g * OT_BLOCKS * OT_BLOCKS) {
+                const int8_t* m = bwd + ((int64_t)(f - 1 - (i >> 6)) * (OT_BLOCKS * OT_BLOCKS) + (i & 63)) * 2;
+                s_m[i >> 6][i & 63] = (uint16_t)((uint32_t)(uint8_t)m[0] | ((uint32_t)(uint8_t)m[1] << 8));
+            }
+        }
+        int pa[OT_ROWS];                                                 // all of a lane's loads in flight before the first is used
+#pragma unroll
+        for (int r = 0; r < OT_ROWS; ++r) pa[r] = labels[fa + (wave + OT_WAVES * r) * OT_SIDE + x];
+#pragma unroll
+        for (int r = 0; r < OT_ROWS; ++r) {
+            const int y = wave + OT_WAVES * r, p = pa[r];
+            const int pc = (p >= 1 && p <= K && ((tmask >> (p - 1)) & 1ull)) ? p : 0;
+            s_L[y * OT_SIDE + x] = (uint8_t)pc;
+            if (pairs) {                                                 // one add per run, as below
+                const int left = __shfl_up(pc, 1, CGS_WAVE);
+                const unsigned long long starts = __ballot(x == 0 || pc != left);
+                const bool last = x == CGS_WAVE - 1 || ((starts >> (x + 1)) & 1ull);
+                if (last && pc) atomicAdd(&s_true[pc - 1], x - (63 - __clzll((long long)(starts & upto))) + 1);
+            }
+        }
+        __syncthreads();
+        // the walk, all 16 rows of a lane side by side: a step is one dependent LDS read per row, and the rows do not wait for each other
+        int my[OT_ROWS], mx[OT_ROWS];
+#pragma unroll
+        for (int r = 0; r < OT_ROWS; ++r) my[r] = mx[r] = 0;
+        for (int j = 0; j < g; ++j) {
+#pragma unroll
+            for (int r = 0; r < OT_ROWS; ++r) {
+                const int qy = min(max(wave + OT_WAVES * r + my[r], 0), OT_SIDE - 1), qx = min(max(x + mx[r], 0), OT_SIDE - 1);
+                const uint32_t v = s_m[j][(qy >> 3) * OT_BLOCKS + (qx >> 3)];
+                my[r] += (int)(int8_t)(v & 255u);
+                mx[r] += (int)(int8_t)(v >> 8);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < OT_ROWS; ++r) {                              // W of cell (y, x): read back below by this same lane
+            const int y = wave + OT_WAVES * r, sy = y + my[r], sx = x + mx[r];
+            s_W[y * OT_SIDE + x] = (sy >= 0 && sy < OT_SIDE && sx >= 0 && sx < OT_SIDE) ? s_L[sy * OT_SIDE + sx] : (uint8_t)0;
+        }
+    }
 
     int pn = 0, tn = 0;
     if (live && wave < h) {
-        pn = labels[fa + wave * w + x];
+        if (!MC) pn = labels[fa + wave * w + x];
         tn = labels[ff + wave * w + x];
     }
     for (int y = wave; y < h; y += OT_WAVES) {
-        const int p = pn, t = tn;
+        int p = pn;
+        const int t = tn;
         if (live && y + OT_WAVES < h) {
-            pn = labels[fa + (y + OT_WAVES) * w + x];
+            if (!MC) pn = labels[fa + (y + OT_WAVES) * w + x];
             tn = labels[ff + (y + OT_WAVES) * w + x];
         }
+        if constexpr (MC) p = (int)s_W[y * OT_SIDE + x];                   // the carried label: clamped and masked when it was staged
         const int pc = (p >= 1 && p <= K && ((tmask >> (p - 1)) & 1ull)) ? p : 0;
         const int tc = (t >= 1 && t <= K && ((hmask >> (t - 1)) & 1ull)) ? t : 0;
         const int key = live ? ((pc << 8) | tc) : -1;
@@ -333,11 +411,15 @@ track_level_kernel(const int32_t* __restrict__ labels, int h, int w, int K, int 
     __syncthreads();
 
     const int side = wave & 1;                                           // waves 0 and 1 scan, 2 and 3 only keep the barriers
-    const int n_other = 64 - __clzll((long long)(side ? tmask : hmask));
+    int n_other = 64 - __clzll((long long)(side ? tmask : hmask));
+    if constexpr (MC) {                                                  // the largest number on the other side that holds a cell
+        const unsigned long long present = __ballot(s_A[side ^ 1][x] > 0);
+        n_other = present ? 64 - __clzll((long long)present) : 0;
+    }
     const int own_step = side ? 1 : OT_STRIDE, other_step = side ? OT_STRIDE : 1;
     const int own_area = s_A[side][x];
     const int* other_areas = s_A[side ^ 1];
-    int bi = 0, bu = 1, bj = 0;
+    int bi = 0, bu = 1, bj = 0, ba = 0;
     if (wave < 2) {
         for (int j = 0; j < n_other; ++j) {
             const int inter = s_I[x * own_step + j * other_step], oa = other_areas[j];
@@ -346,9 +428,20 @@ track_level_kernel(const int32_t* __restrict__ labels, int h, int w, int K, int 
                 bi = inter;
                 bu = uni;
                 bj = j + 1;
+                ba = oa;
             }
         }
         s_best[side][x] = bj;
+    }
+    if (pairs) {                                                         // slot a of `best`; the link kernel decides
+        if (wave < 2 && x < K) {
+            int32_t* row = best + (((int64_t)a * 2 + side) * K + x) * 4;
+            row[0] = bj;
+            row[1] = bi;
+            row[2] = side ? own_area : s_true[x];
+            row[3] = ba;
+        }
+        return;
     }
     __syncthreads();
     if (wave >= 2) return;
@@ -518,20 +611,14 @@ extern "C" int64_t cgs_objects_track_gap_scratch_bytes(int32_t n, int32_t max_ob
     return words * 4u > (unsigned __int128)INT64_MAX ? INT64_MAX : (int64_t)(words * 4u);
 }
 
-// Launches: init, match (n > 1), self-match, link, prepare, min(G, n - 1) levels, R x resolve, number, heads, table, paint:
-// 8 + R + (n > 1) + min(G, n - 1), a function of n and G alone.
-extern "C" int cgs_objects_track_gap(const int32_t* labels, int32_t n, int32_t h, int32_t w, int32_t max_objects, int32_t iou_milli,
-                                     int32_t max_gap, int32_t max_tracks, int32_t* prev, int32_t* gap, int32_t* track, int32_t* totals,
-                                     int32_t* gap_links, int32_t* tracks, int32_t* tracks_extra, int32_t* track_labels, uint8_t* rgb,
-                                     void* scratch, int64_t scratch_bytes, cgs_stream_t stream_) {
-    if (!labels || !prev || !gap || !track || !totals || !gap_links || !scratch || n < 1 || h < 1 || w < 1 || max_objects < 1 ||
-        max_tracks < 1 || iou_milli < 1 || iou_milli > 1000 || max_gap < 0 || max_gap > CGS_OBJ_TRACK_MAX_GAP ||
-        ((uintptr_t)labels & 3u) || ((uintptr_t)prev & 3u) || ((uintptr_t)gap & 3u) || ((uintptr_t)track & 3u) ||
-        ((uintptr_t)totals & 3u) || ((uintptr_t)gap_links & 3u) || ((uintptr_t)tracks & 3u) || ((uintptr_t)tracks_extra & 3u) ||
-        ((uintptr_t)track_labels & 3u) || ((uintptr_t)scratch & 7u) ||
-        scratch_bytes < cgs_objects_track_gap_scratch_bytes(n, max_objects, max_gap))
-        return CGS_ERR_BADARG;
-    if (h > CGS_OBJ_MAX_SIDE || w > CGS_OBJ_MAX_SIDE || max_objects > OT_MAX_K || n > CGS_OBJ_TRACK_MAX_FRAMES) return CGS_ERR_UNSUPPORTED;
+namespace {
+
+// What cgs_objects_track_gap and cgs_objects_track_mc launch once their arguments are checked; bwd NULL: no motion.
+// Launches: init, match or the level-1 count (n > 1), self-match, link, prepare, min(G, n - 1) levels, R x resolve, number, heads,
+// table, paint: 8 + R + (n > 1) + min(G, n - 1), a function of n and G alone.
+int track_gap_run(const int32_t* labels, const int8_t* bwd, int32_t n, int32_t h, int32_t w, int32_t max_objects, int32_t iou_milli,
+                  int32_t max_gap, int32_t max_tracks, int32_t* prev, int32_t* gap, int32_t* track, int32_t* totals, int32_t* gap_links,
+                  int32_t* tracks, int32_t* tracks_extra, int32_t* track_labels, uint8_t* rgb, void* scratch, cgs_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const int K = max_objects, hw = h * w, levels = max_gap + 1;
     const Layout o = layout(n, K);
@@ -548,7 +635,11 @@ extern "C" int cgs_objects_track_gap(const int32_t* labels, int32_t n, int32_t h
     const unsigned init_blocks = (unsigned)(want_blocks < 1 ? 1 : want_blocks > 4096 ? 4096 : want_blocks);
     hipLaunchKernelGGL(track_init_kernel, dim3(init_blocks), dim3(OT_THREADS), 0, stream, tracks, words, totals, milli, (int)iou_milli);
     CGS_HIP_CHECK_LAUNCH();
-    if (n > 1) {
+    if (n > 1 && bwd) {                                                   // level 1 along the field: slots 0 .. n - 2 of `best`
+        hipLaunchKernelGGL(track_level_kernel<true>, dim3((unsigned)(n - 1)), dim3(OT_THREADS), 0, stream, labels, bwd, (int)h, (int)w, K, 1,
+                           (int)iou_milli, prev, gap, root_a, link, heads, tails, totals, best);
+        CGS_HIP_CHECK_LAUNCH();
+    } else if (n > 1) {
         const int rc = cgs_objects_match(labels, labels + hw, n - 1, h, w, K, milli, 1, counts, best, stream_);
         if (rc != CGS_OK) return rc;
     }
@@ -562,8 +653,12 @@ extern "C" int cgs_objects_track_gap(const int32_t* labels, int32_t n, int32_t h
                        gap_links, levels, tracks_extra, tracks_extra ? 2 * (int64_t)max_tracks : (int64_t)0);
     CGS_HIP_CHECK_LAUNCH();
     for (int g = 2; g <= levels && g <= n - 1; ++g) {                     // a level with no frame pair launches nothing
-        hipLaunchKernelGGL(track_level_kernel, dim3((unsigned)(n - g)), dim3(OT_THREADS), 0, stream, labels, (int)h, (int)w, K, g,
-                           (int)iou_milli, prev, gap, root_a, link, heads, tails, totals);
+        if (bwd)
+            hipLaunchKernelGGL(track_level_kernel<true>, dim3((unsigned)(n - g)), dim3(OT_THREADS), 0, stream, labels, bwd, (int)h, (int)w, K,
+                               g, (int)iou_milli, prev, gap, root_a, link, heads, tails, totals, best);
+        else
+            hipLaunchKernelGGL(track_level_kernel<false>, dim3((unsigned)(n - g)), dim3(OT_THREADS), 0, stream, labels, bwd, (int)h, (int)w, K,
+                               g, (int)iou_milli, prev, gap, root_a, link, heads, tails, totals, best);
         CGS_HIP_CHECK_LAUNCH();
     }
     const int total = n * K;
@@ -587,4 +682,43 @@ extern "C" int cgs_objects_track_gap(const int32_t* labels, int32_t n, int32_t h
                        track_labels, rgb);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
+}
+
+}  // namespace
+
+extern "C" int cgs_objects_track_gap(const int32_t* labels, int32_t n, int32_t h, int32_t w, int32_t max_objects, int32_t iou_milli,
+                                     int32_t max_gap, int32_t max_tracks, int32_t* prev, int32_t* gap, int32_t* track, int32_t* totals,
+                                     int32_t* gap_links, int32_t* tracks, int32_t* tracks_extra, int32_t* track_labels, uint8_t* rgb,
+                                     void* scratch, int64_t scratch_bytes, cgs_stream_t stream_) {
+    if (!labels || !prev || !gap || !track || !totals || !gap_links || !scratch || n < 1 || h < 1 || w < 1 || max_objects < 1 ||
+        max_tracks < 1 || iou_milli < 1 || iou_milli > 1000 || max_gap < 0 || max_gap > CGS_OBJ_TRACK_MAX_GAP ||
+        ((uintptr_t)labels & 3u) || ((uintptr_t)prev & 3u) || ((uintptr_t)gap & 3u) || ((uintptr_t)track & 3u) ||
+        ((uintptr_t)totals & 3u) || ((uintptr_t)gap_links & 3u) || ((uintptr_t)tracks & 3u) || ((uintptr_t)tracks_extra & 3u) ||
+        ((uintptr_t)track_labels & 3u) || ((uintptr_t)scratch & 7u) ||
+        scratch_bytes < cgs_objects_track_gap_scratch_bytes(n, max_objects, max_gap))
+        return CGS_ERR_BADARG;
+    if (h > CGS_OBJ_MAX_SIDE || w > CGS_OBJ_MAX_SIDE || max_objects > OT_MAX_K || n > CGS_OBJ_TRACK_MAX_FRAMES) return CGS_ERR_UNSUPPORTED;
+    return track_gap_run(labels, nullptr, n, h, w, max_objects, iou_milli, max_gap, max_tracks, prev, gap, track, totals, gap_links, tracks,
+                         tracks_extra, track_labels, rgb, scratch, stream_);
+}
+
+// The scratch is cgs_objects_track_gap's: the carried labels live in LDS.
+extern "C" int64_t cgs_objects_track_mc_scratch_bytes(int32_t n, int32_t max_objects, int32_t max_gap) {
+    return cgs_objects_track_gap_scratch_bytes(n, max_objects, max_gap);
+}
+
+extern "C" int cgs_objects_track_mc(const int32_t* labels, const int8_t* bwd, int32_t n, int32_t h, int32_t w, int32_t max_objects,
+                                    int32_t iou_milli, int32_t max_gap, int32_t max_tracks, int32_t* prev, int32_t* gap, int32_t* track,
+                                    int32_t* totals, int32_t* gap_links, int32_t* tracks, int32_t* tracks_extra, int32_t* track_labels,
+                                    uint8_t* rgb, void* scratch, int64_t scratch_bytes, cgs_stream_t stream_) {
+    if (!labels || (!bwd && n != 1) || !prev || !gap || !track || !totals || !gap_links || !scratch || n < 1 || h < 1 || w < 1 ||
+        max_objects < 1 || max_tracks < 1 || iou_milli < 1 || iou_milli > 1000 || max_gap < 0 || max_gap > CGS_OBJ_TRACK_MAX_GAP ||
+        ((uintptr_t)labels & 3u) || ((uintptr_t)prev & 3u) || ((uintptr_t)gap & 3u) || ((uintptr_t)track & 3u) ||
+        ((uintptr_t)totals & 3u) || ((uintptr_t)gap_links & 3u) || ((uintptr_t)tracks & 3u) || ((uintptr_t)tracks_extra & 3u) ||
+        ((uintptr_t)track_labels & 3u) || ((uintptr_t)scratch & 7u) ||
+        scratch_bytes < cgs_objects_track_mc_scratch_bytes(n, max_objects, max_gap))
+        return CGS_ERR_BADARG;
+    if (h != OT_SIDE || w != OT_SIDE || max_objects > OT_MAX_K || n > CGS_OBJ_TRACK_MAX_FRAMES) return CGS_ERR_UNSUPPORTED;
+    return track_gap_run(labels, bwd, n, h, w, max_objects, iou_milli, max_gap, max_tracks, prev, gap, track, totals, gap_links, tracks,
+                         tracks_extra, track_labels, rgb, scratch, stream_);
 }

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from . import boundary, metrics, objects, saliency
+from . import boundary, metrics, objects, saliency, temporal
 
 MATCH_MAX_OBJECTS = 64          # objects per frame and side that --match-iou matches and --track-iou follows
 
@@ -39,7 +39,7 @@ def fmt(v):
 class Stacks:
     """The stacks of one -eval run by name, host arrays in `host`: "truth" (bool), "mask" (the probabilities, float32, read with the
     strict compare of --eval-thresh, main.py:964), the hard stacks "crf", "saliency", "saliency_crf" where the run has them, and the
-    saliency sweep's inputs "sal" and "preds" (float32).  dev uploads a stack when it is first read; labelled and matched likewise."""
+    saliency sweep's inputs "sal" and "preds" (float32), and with --track-motion "frames" (uint8 [n,64,64,3]).  dev uploads a stack when it is first read; labelled and matched likewise."""
 
     def __init__(self, args, device, **host):
         self.args, self.device, self.host, self._made = args, device, host, {}
@@ -159,29 +159,36 @@ def match_report(args, st):
         f"{b['truth_objects']} truth objects, f1 {fmt(first(b)['f1'])}, pq {fmt(first(b)['pq'])}" for pre, b in _blocks(st, report))
 
 
-def _tracked(labelled, iou, gap=0):
+def _tracked(labelled, iou, gap=0, motion=None):
     """(Tracks, one side of eval_tracks.json) of a labelled stack: tracked on the GPU, the length histogram and the link sums formed
-    there; only the totals, 7 counts and 3 sums come back (with --track-gap also the links by gap and the missed frames)."""
+    there; only the totals, 7 counts and 3 sums come back (with --track-gap also the links by gap and the missed frames).  motion:
+    (bwd, search) of --track-motion; the side then gains "track_motion"."""
     K = MATCH_MAX_OBJECTS
-    tr = objects.track(labelled.labels, iou=iou, max_objects=K, max_gap=gap)
+    tr = objects.track(labelled.labels, iou=iou, max_objects=K, max_gap=gap, motion=motion[0] if motion else None)
     totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
     more = {"max_gap": gap, "gap_links": tr.gap_links, "missed": tr.extra[:, 1].sum(dtype=torch.int64)} if gap else {}
-    return tr, objects.track_report(totals, tr.table[:, 2], tr.table[:, 6].sum(dtype=torch.int64), tr.table[:, 7].sum(dtype=torch.int64),
-                                    (labelled.kept - K).clamp(min=0).sum(), **more)
+    side = objects.track_report(totals, tr.table[:, 2], tr.table[:, 6].sum(dtype=torch.int64), tr.table[:, 7].sum(dtype=torch.int64),
+                                (labelled.kept - K).clamp(min=0).sum(), **more)
+    if motion:
+        side["track_motion"] = objects.motion_report(*motion)
+    return tr, side
 
 
 def tracks_report(args, st):
     """--track-iou: the same objects followed from frame to frame on the GPU; with --match-iou the identity switches at its thresholds,
     from the matches eval_match.json reports.  --track-gap G tracks truth and predictions with the same G (objects.track's max_gap);
-    the switches then follow the truth's adjacent links only, and every threshold's entry gains "fragments" (objects.fragments)."""
+    the switches then follow the truth's adjacent links only, and every threshold's entry gains "fragments" (objects.fragments).
+    --track-motion S tracks both along one field, temporal.flow of the evaluation frames as bytes (the stack "frames")."""
     t_iou = objects.parse_track_iou(args.track_iou)
     gap = int(getattr(args, "track_gap", 0) or 0)
+    search = int(getattr(args, "track_motion", 0) or 0)
+    motion = (temporal.flow(st.dev("frames"), search)[1], search) if search else None
     m_iou = objects.parse_match_iou(args.match_iou) if getattr(args, "match_iou", "") else None
-    truth_tr, truth_side = _tracked(st.labelled("truth"), t_iou, gap)
+    truth_tr, truth_side = _tracked(st.labelled("truth"), t_iou, gap, motion)
     report = _head(args, max_objects=MATCH_MAX_OBJECTS, track_iou=t_iou, truth=truth_side)
-    truth_prev = torch.where(truth_tr.gap == 1, truth_tr.prev, 0) if gap else truth_tr.prev
+    truth_prev = torch.where(truth_tr.gap == 1, truth_tr.prev, 0) if gap else truth_tr.prev     # (without gaps every link has gap 1)
     for name in st.names(("mask", "crf")):
-        pred_tr, side = _tracked(st.labelled(name), t_iou, gap)
+        pred_tr, side = _tracked(st.labelled(name), t_iou, gap, motion)
         report[name] = {"pred": side}
         if m_iou is not None:
             best = st.matched(name, m_iou).best
@@ -193,11 +200,12 @@ def tracks_report(args, st):
                     entry["fragments"] = int(v)
     report = _json_safe(report)
     p = report["mask"]["pred"]
+    moved = f" motion<={search}" if search else ""
     if gap:
-        return report, (f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g} gap<={gap}: {p['tracks']} tracks over "
+        return report, (f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g} gap<={gap}{moved}: {p['tracks']} tracks over "
                         f"{p['objects']} objects ({p['bridged_links']} of {p['links']} links bridged), mean length {fmt(p['mean_length'])}, "
                         f"longest {p['max_length']}; truth {truth_side['tracks']} tracks over {truth_side['objects']} objects")
-    return report, (f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g}: {p['tracks']} tracks over {p['objects']} "
+    return report, (f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g}{moved}: {p['tracks']} tracks over {p['objects']} "
                     f"objects, mean length {fmt(p['mean_length'])}, longest {p['max_length']}; truth {truth_side['tracks']} tracks over "
                     f"{truth_side['objects']} objects")
 

@@ -456,7 +456,8 @@ class Handler:
         if getattr(args, "fit", False):                 # (this build's flag) frames of any one size; everything below stays as it is
             return self._segment_fit(folder)
         files, stems = process.list_folder(folder)
-        frames = np.stack([np.array(Image.open(os.path.join(folder, f)))[..., :3] for f in files]) / 255.0     # NHWC float64 in [0,1]
+        file_bytes = np.stack([np.array(Image.open(os.path.join(folder, f)))[..., :3] for f in files])        # NHWC, as the files hold them
+        frames = file_bytes / 255.0                                                                              # NHWC float64 in [0,1]
         fp16 = bool(getattr(args, "fp16", False))      # (this build's switch) BASELINE config 4: fp16 layers on the uint8 frames
 
         def to_device(chunk):
@@ -472,7 +473,8 @@ class Handler:
         if args.crf:                    # main.py:1169-1172 (with --binarymaskthreshold 0 this column lands in position 2)
             cols.append(self.crf(frames, M, None))
         if getattr(args, "objects", False):     # (this build's flag) not a column: the by-position naming and the strip stay as they are
-            process.objects_and_tracks(args, M, cols[-1] if args.crf else None, stems[:len(frames)], self.device, self.rank)
+            process.objects_and_tracks(args, M, cols[-1] if args.crf else None, stems[:len(frames)], self.device, self.rank,
+                                       low=np.ascontiguousarray(file_bytes, dtype=np.uint8) if getattr(args, "track_motion", 0) else None)
         if args.process_salience:       # main.py:1176-1197
             sal_maps, sal_hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
             cols += [sal_maps, sal_hard]
@@ -522,12 +524,15 @@ class Handler:
         sig = dict(sigma_s=args.fit_spatial, sigma_r=args.fit_range)
         step = process.chunk_frames(self.FIT_CHUNK_FRAMES, self.FIT_CHUNK_BYTES, H, W)
         masks, crf_masks = [], []
+        lows = [] if getattr(args, "objects", False) and getattr(args, "track_motion", 0) else None     # --track-motion: the shrunk frames
         unit = process.unit_table(self.device)
         for lo in range(0, len(files), step):
             print("segmentation in progress", round(lo / len(files), 2), end="%\r")
             host = np.stack([np.array(Image.open(os.path.join(folder, f)))[..., :3] for f in files[lo:lo + step]])    # NHWC uint8
             guide = torch.from_numpy(np.ascontiguousarray(host, dtype=np.uint8)).to(self.device)
             low = fit.down(guide)
+            if lows is not None:
+                lows.append(low)
             Z = process.fit_infer(eng, low, unit, fp16, bool(args.noevalmode))
             M = Z.cpu().numpy()[:, None]
             masks.append(M)
@@ -545,7 +550,8 @@ class Handler:
         M = np.concatenate(masks, axis=0)
         crf_mask = np.concatenate(crf_masks, axis=0) if args.crf else None
         if getattr(args, "objects", False):
-            process.objects_and_tracks(args, M, crf_mask, stems[:len(files)], self.device, self.rank)
+            process.objects_and_tracks(args, M, crf_mask, stems[:len(files)], self.device, self.rank,
+                                       low=torch.cat(lows) if lows is not None else None)
         write_json(f"{out_dir}/fit.json", {"frame_size": [H, W], "net_size": [fit.SIDE, fit.SIDE], "sigma_spatial": args.fit_spatial,
                                            "sigma_range": args.fit_range, "radius": fit.RADIUS, "frames": len(files)}, self.rank)
         return M
@@ -563,6 +569,8 @@ class Handler:
              With --overlay-tracks T the smoothed masks are labelled (objects.label at the threshold, 8-connected, --overlay-min-area),
              objects.TrackStream numbers the objects through the chunks as objects.track numbers the whole stack, and
              overlay.compose_tracks draws each in its track's colour with its box and number in place of overlay.compose.
+             With --overlay-motion S the stream tracks along temporal.flow's backward vectors of the chunk's shrunk frames and the one
+             before them (kept across the chunk boundary); the vectors stay on the device, 128 bytes a frame pair, for the reports.
         Stage A of chunk c + 1 runs before stage B of chunk c (a chunk waits until R frames after it are there, or the stream has ended).
         No PNG is written.  Rank 0 leaves {R}/{stem of OUT}.json, with --overlay-tracks also {R}/{stem}-objects.json and
         {R}/{stem}-tracks.json (process.video_reports; skipped beyond objects.TRACK_MAX_FRAMES frames, the video is complete all the
@@ -573,7 +581,10 @@ class Handler:
         args = self.args
         track_iou = getattr(args, "overlay_tracks", None)
         track_gap = int(getattr(args, "overlay_gap", 0) or 0)                 # --overlay-gap: objects.TrackStream's max_gap
-        stream = objects.TrackStream(track_iou, max_objects=overlay.MAX_TRACK_OBJECTS, max_gap=track_gap) if track_iou is not None else None
+        track_motion = int(getattr(args, "overlay_motion", 0) or 0)           # --overlay-motion: the search range of its block vectors
+        stream = objects.TrackStream(track_iou, max_objects=overlay.MAX_TRACK_OBJECTS, max_gap=track_gap,
+                                     motion=bool(track_motion)) if track_iou is not None else None
+        before_low, fields = None, []                  # --overlay-motion: the shrunk frame before the chunk; every chunk's vectors
         ffmpeg, ffprobe = video_in.find_ffmpeg(), video_in.find_ffprobe()
         W, H, rate = video_in.probe(path, ffprobe)
         k = args.overlay_panels
@@ -604,7 +615,7 @@ class Handler:
             return guide, low, process.fit_infer(eng, low, unit, fp16, bool(args.noevalmode)).contiguous().clone()
 
         def stage_b():
-            nonlocal tail, moved, vectors
+            nonlocal tail, moved, vectors, before_low
             guide, low, Z = pending.popleft()
             if R:
                 zs, ls = [Z], [low]
@@ -636,7 +647,17 @@ class Handler:
             if stream is not None:
                 res = objects.label(Zs, thresh=thr, inclusive=True, connectivity=8, min_area=args.overlay_min_area,
                                     max_objects=overlay.MAX_TRACK_OBJECTS)
-                frames = overlay.compose_tracks(guide, up.grey, up.hard, res.labels, stream.push(res.labels), res.table,
+                if track_motion:                       # row i: from frame i of the chunk to the frame before it in the stream
+                    first = before_low is None
+                    bwd = temporal.flow(low if first else torch.cat((before_low, low)), track_motion)[1]
+                    if first:                          # no frame before the stream's first: a row the stream ignores
+                        bwd = torch.cat((bwd.new_zeros((1,) + tuple(bwd.shape[1:])), bwd))
+                    before_low = low[-1:].clone()
+                    fields.append(bwd)
+                    ids = stream.push(res.labels, bwd)
+                else:
+                    ids = stream.push(res.labels)
+                frames = overlay.compose_tracks(guide, up.grey, up.hard, res.labels, ids, res.table,
                                                 color=args.overlay_color, alpha256=args.overlay_alpha256, outline=args.overlay_outline,
                                                 boxes=args.overlay_boxes, layout=args.overlay_layout)
             else:
@@ -683,13 +704,15 @@ class Handler:
         if stream is not None:
             reports = None
             if len(M) <= objects.TRACK_MAX_FRAMES:
-                reports = process.video_reports(args, M, stem, self.device, self.rank)
+                reports = process.video_reports(args, M, stem, self.device, self.rank,
+                                                bwd=torch.cat(fields)[1:] if track_motion else None)
             else:
                 print(f"--overlay-tracks: {len(M)} frames are more than the {objects.TRACK_MAX_FRAMES} one report holds: the video is complete, "
                       f"{stem}-objects.json and {stem}-tracks.json are not written")
             tracks = {"tracks": {"iou": track_iou, "min_area": args.overlay_min_area, "boxes": args.overlay_boxes,
                                  "scale": overlay.scale(H, W), "max_objects": overlay.MAX_TRACK_OBJECTS, "n_tracks": int(stream.n_tracks),
-                                 **({"gap": track_gap} if track_gap else {}), "reports": reports}}
+                                 **({"gap": track_gap} if track_gap else {}), **({"motion": track_motion} if track_motion else {}),
+                                 "reports": reports}}
         write_json(f"{out_dir}/{stem}.json", {
             "frame_size": [H, W], "frames": len(M), "rate": rate, "layout": args.overlay_layout, "color": list(args.overlay_color),
             "alpha256": args.overlay_alpha256, "outline": args.overlay_outline, "threshold": thr,
@@ -854,6 +877,8 @@ class Handler:
             if getattr(args, "match_iou", ""):
                 self.matches = report(evaluate.match_report, "eval_match.json")
             if getattr(args, "track_iou", ""):
+                if getattr(args, "track_motion", 0):   # the frames as bytes, the conversion of Handler.crf
+                    st.host["frames"] = frames if frames.dtype == np.uint8 else (255 * frames).astype(np.uint8)
                 self.tracks = report(evaluate.tracks_report, "eval_tracks.json")
         if getattr(args, "boundary_tol", ""):   # (this build's flag) the outlines against the truth's outline
             self.boundary = report(evaluate.boundary_report, "eval_boundary.json")

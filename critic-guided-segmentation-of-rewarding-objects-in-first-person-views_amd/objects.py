@@ -13,7 +13,9 @@ threshold, chains resolved on the device), ``switches`` counts identity switches
 (eval_tracks.json, tracks.json).  ``TrackStream`` gives ``track``'s numbers to a label stack that arrives in chunks
 (``-process --source-video --overlay-tracks``); ``stream_remap`` is its arithmetic.  With ``max_gap`` G > 0 (``--track-gap``,
 ``--overlay-gap``) both bridge gaps of up to G missing frames (cgs_objects_track_gap), and ``fragments`` counts how often a truth
-track is split over several predicted tracks."""
+track is split over several predicted tracks.  With ``motion`` (``--track-motion``, ``--overlay-motion``) the earlier frame's labels
+are carried along ``temporal.flow``'s backward block vectors before they are intersected (cgs_objects_track_mc); ``motion_report``
+is the block the reports gain."""
 import re
 from collections import namedtuple
 
@@ -32,6 +34,7 @@ TRACK_FIELDS = ("first_frame", "first_label", "length", "area_sum", "area_min", 
 TRACK_MAX_FRAMES = _lib.OBJ_TRACK_MAX_FRAMES
 LENGTH_BINS = ("1", "2", "3-4", "5-8", "9-16", "17-32", "33+")             # upper ends 1, 2, 4, 8, 16, 32, then the rest
 TRACK_MAX_GAP = _lib.OBJ_TRACK_MAX_GAP
+MOTION_SIDE, MOTION_BLOCKS, MOTION_MAX_SEARCH = 64, 64 // _lib.TEMPORAL_BLOCK, _lib.TEMPORAL_MAX_SEARCH      # cgs_objects_track_mc
 Tracks = namedtuple("Tracks", ["prev", "track", "n_tracks", "n_links", "n_objects", "longest", "table", "track_labels", "rgb",
                                "gap", "gap_links", "extra"], defaults=(None, None, None))
 
@@ -198,7 +201,23 @@ def _max_gap(max_gap):
     return max_gap
 
 
-def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, want_rgb=False, max_gap=0):
+def _motion_field(motion, n, device):
+    """``track``'s motion argument as the int8 [n - 1,8,8,2] backward field on the labels' device; ValueError otherwise."""
+    if isinstance(motion, (tuple, list)):
+        if len(motion) != 2:
+            raise ValueError(f"motion must be the bwd tensor or the (fwd, bwd) pair of temporal.flow, got {len(motion)} items")
+        motion = motion[1]
+    if not isinstance(motion, torch.Tensor) or motion.dtype != torch.int8:
+        raise ValueError("motion must be an int8 tensor [n - 1,8,8,2] (temporal.flow's bwd), got "
+                         + (f"{motion.dtype}" if isinstance(motion, torch.Tensor) else type(motion).__name__))
+    if tuple(motion.shape) != (n - 1, MOTION_BLOCKS, MOTION_BLOCKS, 2):
+        raise ValueError(f"motion {tuple(motion.shape)}: {n} frames need [{n - 1},{MOTION_BLOCKS},{MOTION_BLOCKS},2]")
+    if motion.device != device:
+        raise ValueError(f"motion is on {motion.device}, the labels on {device}")
+    return motion.contiguous()
+
+
+def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, want_rgb=False, max_gap=0, motion=None):
     """labels: int32 device tensor [n,h,w] or [h,w] (then n = 1), 1 <= h, w <= 64, n <= 2^17, a label stack as ``label`` gives it
     (hand-made maps allowed; views are made contiguous).  An object of frame f is a label in 1..max_objects (at most 64) with a pixel
     in f.  Objects p of f and q of f + 1 are linked when each is the other's best partner (``match``'s `best`: largest IoU, ties to the
@@ -213,7 +232,11 @@ def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, w
     max_gap G in 0..8: 0 is the above (cgs_objects_track).  G > 0 bridges up to G missing frames (cgs_objects_track_gap, whose header
     comment defines the level order): prev then names the label in frame f - gap, longest is the longest span in frames, and the tuple
     also holds gap int32 [n,K] (0 no link, 1 adjacent, g bridged over g - 1 frames), gap_links int32 [G + 1] (links of gap g at g - 1)
-    and extra int32 [max_tracks,2] (bridges, missed per track; span = length + missed); the three are None at G = 0."""
+    and extra int32 [max_tracks,2] (bridges, missed per track; span = length + missed); the three are None at G = 0.
+    motion: ``temporal.flow``'s bwd (int8 [n - 1,8,8,2] on the labels' device) or its (fwd, bwd) pair; the stack must be 64 x 64.  Frame
+    a's labels are then gathered along the chain of block vectors from f back to a before they are intersected with frame f's, at
+    every level, and the union counts the carried area (cgs_objects_track_mc, whose header comment in include/cgs_hip.h is the rule).
+    The result always carries gap, gap_links and extra; an all-zero field gives the result without motion bit for bit."""
     if not isinstance(labels, torch.Tensor):
         raise ValueError(f"labels must be a torch tensor, got {type(labels).__name__}")
     if labels.dtype != torch.int32:
@@ -227,6 +250,10 @@ def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, w
     if not 1 <= n <= TRACK_MAX_FRAMES or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
         raise ValueError(f"labels {tuple(labels.shape)}: 1..{TRACK_MAX_FRAMES} frames of 1..{MAX_SIDE} x 1..{MAX_SIDE} pixels")
     milli = _track_milli(iou)
+    if motion is not None:
+        if (h, w) != (MOTION_SIDE, MOTION_SIDE):
+            raise ValueError(f"labels {tuple(labels.shape)}: motion needs frames of {MOTION_SIDE} x {MOTION_SIDE} (8 x 8 blocks of 8 cells)")
+        motion = _motion_field(motion, n, labels.device)
     max_objects = _as_int(max_objects, "max_objects")
     if not 1 <= max_objects <= MATCH_MAX_OBJECTS:
         raise ValueError(f"max_objects must be 1..{MATCH_MAX_OBJECTS}, got {max_objects}")
@@ -239,8 +266,8 @@ def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, w
     labels = labels.contiguous()
     dev, K = labels.device, max_objects
     with torch.cuda.device(dev):
-        need = int(_lib.load().cgs_objects_track_gap_scratch_bytes(n, K, max_gap) if max_gap else
-                   _lib.load().cgs_objects_track_scratch_bytes(n, K))
+        need = int(_lib.load().cgs_objects_track_gap_scratch_bytes(n, K, max_gap) if max_gap or motion is not None else
+                   _lib.load().cgs_objects_track_scratch_bytes(n, K))       # (the motion entry's scratch is the gap entry's)
         scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
         prev = torch.empty((n, K), dtype=torch.int32, device=dev)
         trk = torch.empty((n, K), dtype=torch.int32, device=dev)
@@ -248,14 +275,17 @@ def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, w
         table = torch.empty((max_tracks, len(TRACK_FIELDS)), dtype=torch.int32, device=dev)
         painted = torch.empty((n, h, w), dtype=torch.int32, device=dev) if want_labels else None
         rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev) if want_rgb else None
-        if max_gap:
+        if max_gap or motion is not None:
             gap = torch.empty((n, K), dtype=torch.int32, device=dev)
             gap_links = torch.empty(max_gap + 1, dtype=torch.int32, device=dev)
             extra = torch.empty((max_tracks, 2), dtype=torch.int32, device=dev)
-            _lib.call("cgs_objects_track_gap", labels.data_ptr(), n, h, w, K, milli, max_gap, max_tracks, prev.data_ptr(), gap.data_ptr(),
-                      trk.data_ptr(), totals.data_ptr(), gap_links.data_ptr(), table.data_ptr(), extra.data_ptr(),
-                      painted.data_ptr() if want_labels else None, rgb.data_ptr() if want_rgb else None, scratch.data_ptr(),
-                      scratch.numel() * 8, torch.cuda.current_stream().cuda_stream)
+            outs = (max_tracks, prev.data_ptr(), gap.data_ptr(), trk.data_ptr(), totals.data_ptr(), gap_links.data_ptr(), table.data_ptr(),
+                    extra.data_ptr(), painted.data_ptr() if want_labels else None, rgb.data_ptr() if want_rgb else None, scratch.data_ptr(),
+                    scratch.numel() * 8, torch.cuda.current_stream().cuda_stream)
+            if motion is not None:
+                _lib.call("cgs_objects_track_mc", labels.data_ptr(), motion.data_ptr() if n > 1 else None, n, h, w, K, milli, max_gap, *outs)
+            else:
+                _lib.call("cgs_objects_track_gap", labels.data_ptr(), n, h, w, K, milli, max_gap, *outs)
             return Tracks(prev, trk, totals[0], totals[1], totals[2], totals[3], table, painted, rgb, gap, gap_links, extra)
         _lib.call("cgs_objects_track", labels.data_ptr(), n, h, w, K, milli, max_tracks, prev.data_ptr(), trk.data_ptr(),
                   totals.data_ptr(), table.data_ptr(), painted.data_ptr() if want_labels else None, rgb.data_ptr() if want_rgb else None,
@@ -287,44 +317,63 @@ class TrackStream:
     frame, then label, so the last frame of a chunk (its labels and its numbers) is all that the next chunk needs.  ``n_tracks`` is the
     number of tracks so far, an int32 scalar on the device (0 before the first push); nothing here synchronises with the host.
     With max_gap = G > 0 a link (f - g -> f), g <= G + 1, depends on the frames f - g .. f only, so the last G + 1 frames pushed are
-    carried (fewer while the stream is shorter than that): G frames are not enough, a chunk's first frame may reach G + 1 back."""
+    carried (fewer while the stream is shorter than that): G frames are not enough, a chunk's first frame may reach G + 1 back.
+    With motion=True every push also takes the frames' backward block vectors and the results are those of ``track(stack,
+    motion=bwd)``: a link (a -> f) depends on the frames a and f and the vectors bwd[a .. f - 1] only, so the stream carries each
+    carried frame's vector (the one to the frame before it) beside its labels."""
 
-    def __init__(self, iou, max_objects=64, max_gap=0):
+    def __init__(self, iou, max_objects=64, max_gap=0, motion=False):
         self.milli = _track_milli(iou)
         self.iou = self.milli / 1000
         self.max_objects = _as_int(max_objects, "max_objects")
         if not 1 <= self.max_objects <= MATCH_MAX_OBJECTS:
             raise ValueError(f"max_objects must be 1..{MATCH_MAX_OBJECTS}, got {max_objects}")
         self.max_gap = _max_gap(max_gap)
+        self.motion = bool(motion)
         self.n_tracks = 0
         self._carry = None                     # (labels [c,h,w], numbers int32 [c,K]) of the last c <= max_gap + 1 frames pushed
+        self._vectors = None                   # motion: int8 [c,8,8,2], row j from carried frame j to the frame before it
 
-    def push(self, labels):
+    def push(self, labels, bwd=None):
         """labels: int32 device tensor [m,h,w], m >= 1, of the shape and on the device of the first push, m + 1 <= 2^17.  Returns int32
-        [m,K]: the track number in the whole stream of every object, 0 where there is none."""
+        [m,K]: the track number in the whole stream of every object, 0 where there is none.
+        bwd (with motion=True, and only then): int8 [m,8,8,2] on the labels' device, row i the vectors from pushed frame i to the
+        frame before it in the stream (``temporal.flow``'s bwd of the stream, one row late); row 0 of the first push is ignored."""
         if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.dim() != 3 or labels.shape[0] < 1:
             raise ValueError("labels must be an int32 tensor [m,h,w] with at least one frame, got "
                              + (f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, torch.Tensor) else type(labels).__name__))
         m = int(labels.shape[0])
         keep = self.max_gap + 1
+        if (bwd is not None) != self.motion:
+            raise ValueError("bwd goes with TrackStream(motion=True), and every push of such a stream needs it")
+        if self.motion:
+            if not isinstance(bwd, torch.Tensor) or bwd.dtype != torch.int8 or tuple(bwd.shape) != (m, MOTION_BLOCKS, MOTION_BLOCKS, 2) \
+                    or bwd.device != labels.device:
+                raise ValueError(f"bwd must be an int8 tensor [{m},{MOTION_BLOCKS},{MOTION_BLOCKS},2] on {labels.device}, got "
+                                 + (f"{bwd.dtype} {tuple(bwd.shape)} on {bwd.device}" if isinstance(bwd, torch.Tensor) else type(bwd).__name__))
         if m + keep > TRACK_MAX_FRAMES:
             raise ValueError(f"a chunk of {m} frames: with the carried frame{'s' if keep > 1 else ''} at most {TRACK_MAX_FRAMES} are "
                              "tracked at once")
         if self._carry is None:
-            tr = track(labels, iou=self.iou, max_objects=self.max_objects, max_tracks=1, max_gap=self.max_gap)
+            tr = track(labels, iou=self.iou, max_objects=self.max_objects, max_tracks=1, max_gap=self.max_gap,
+                       motion=bwd[1:] if self.motion else None)
             ids, self.n_tracks = tr.track, tr.n_tracks
             self._carry = (labels[-keep:].contiguous().clone(), ids[-keep:].clone())
+            self._vectors = bwd[-keep:].clone() if self.motion else None
         else:
             last, last_ids = self._carry
             if labels.shape[1:] != last.shape[1:] or labels.device != last.device:
                 raise ValueError(f"labels {tuple(labels.shape)} on {labels.device}: the stream holds frames of {tuple(last.shape[1:])} on "
                                  f"{last.device}")
             c = int(last.shape[0])
-            tr = track(torch.cat((last, labels)), iou=self.iou, max_objects=self.max_objects, max_tracks=1, max_gap=self.max_gap)
+            field = torch.cat((self._vectors[1:], bwd)) if self.motion else None      # row i: frames i + 1 -> i of cat(last, labels)
+            tr = track(torch.cat((last, labels)), iou=self.iou, max_objects=self.max_objects, max_tracks=1, max_gap=self.max_gap,
+                       motion=field)
             c0 = tr.track[:c].max()            # tracks are numbered by first frame: those headed in the carry are 1..c0
             ids = stream_remap(tr.track[c:], tr.track[:c], last_ids, c0, self.n_tracks).to(torch.int32)
             self.n_tracks = (self.n_tracks + tr.n_tracks - c0).to(torch.int32)
             self._carry = (torch.cat((last, labels))[-keep:].contiguous().clone(), torch.cat((last_ids, ids))[-keep:].clone())
+            self._vectors = torch.cat((self._vectors, bwd))[-keep:].clone() if self.motion else None
         return ids
 
 
@@ -402,6 +451,30 @@ def parse_track_gap(s, flag="--track-gap"):
     if not 0 <= g <= TRACK_MAX_GAP:
         raise ValueError(f"{flag} {g}: expected a whole number 0..{TRACK_MAX_GAP}")
     return g
+
+
+def parse_track_motion(s, flag="--track-motion"):
+    """``--track-motion`` / ``--overlay-motion``: a whole number 0..4 (the search range of temporal.flow in cells a frame; 0: off).
+    Returns the int; ValueError otherwise."""
+    try:
+        v = int(str(s).strip())
+    except ValueError:
+        raise ValueError(f"{flag} {s!r}: expected a whole number 0..{MOTION_MAX_SEARCH}") from None
+    if not 0 <= v <= MOTION_MAX_SEARCH:
+        raise ValueError(f"{flag} {v}: expected a whole number 0..{MOTION_MAX_SEARCH}")
+    return v
+
+
+def motion_report(bwd, search):
+    """The "track_motion" block of tracks.json / eval_tracks.json / {stem}-tracks.json from the backward field the tracker used (int8
+    [n - 1,8,8,2], tensor or array; may be empty): {"search", "block": 8, "mean_cells_per_frame": the mean Euclidean length of the
+    vectors, "saturated": the share of vectors with a component at +-search} -- the figures the video report gives for
+    --smooth-motion.  Both are None for an empty field."""
+    v = _host(bwd).reshape(-1, 2).astype(np.float64)
+    search = int(search)
+    return {"search": search, "block": _lib.TEMPORAL_BLOCK,
+            "mean_cells_per_frame": float(np.sqrt((v ** 2).sum(axis=1)).mean()) if len(v) else None,
+            "saturated": float((np.abs(v).max(axis=1) >= search).mean()) if len(v) else None}
 
 
 def parse_track_iou(s):

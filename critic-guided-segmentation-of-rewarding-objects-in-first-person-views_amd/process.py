@@ -65,23 +65,28 @@ def binary_source(args, M, crf_mask, device):
             dict(kw, thresh=thresh, inclusive=True))
 
 
-def objects_and_tracks(args, M, crf_mask, stems, device, rank):
+def objects_and_tracks(args, M, crf_mask, stems, device, rank, low=None):
     """-process -objects [--track-iou]: the stack of binary_source labelled on the GPU once (objects.py; labels, mask and counts do not
-    depend on the table's rows), then reported as objects and, if asked for, as tracks."""
+    depend on the table's rows), then reported as objects and, if asked for, as tracks.  low: with --track-motion the uint8 frames
+    [n,64,64,3] the masks were made from (tensor or array, in the order of stems)."""
     want_tracks = bool(getattr(args, "track_iou", ""))
     source, thresh, stack, kw = binary_source(args, M, crf_mask, device)
     res = objects.label(stack, max_objects=PROCESS_MAX_OBJECTS, want_labels=want_tracks, want_mask=True, **kw)
     head = {"source": source, "threshold": thresh, "connectivity": args.connectivity, "min_area": args.min_area}
     _objects(args, res, head, stems, M.shape[-1], rank)
     if want_tracks:
-        _tracks(args, res, head, stems, rank)
+        search = int(getattr(args, "track_motion", 0) or 0)
+        if search and low is None:
+            raise ValueError("--track-motion needs the 64 x 64 frames of the masks")
+        _tracks(args, res, head, stems, rank, low=torch.as_tensor(low).to(device) if search else None, search=search)
 
 
-def video_reports(args, M, stem, device, rank):
+def video_reports(args, M, stem, device, rank, bwd=None):
     """--source-video --overlay-tracks: the whole-stack reports of the masks M [n,1,64,64] that the stream returned, labelled as the
     stream labelled them (threshold inclusive, 8-connected, --overlay-min-area), as {R}/{stem}-objects.json and {R}/{stem}-tracks.json
     with the frames keyed "000000", "000001", ... in stream order and no PNG.  objects.TrackStream gives objects.track's numbers, so
-    the numbers of tracks.json are the ones drawn on the video.  Returns the two file names."""
+    the numbers of tracks.json are the ones drawn on the video.  bwd: with --overlay-motion the backward field the stream tracked along,
+    int8 [n - 1,8,8,2] on the device.  Returns the two file names."""
     thresh = float(args.binarymaskthreshold)
     stack = torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(device)
     res = objects.label(stack, thresh=thresh, inclusive=True, connectivity=8, min_area=args.overlay_min_area,
@@ -90,7 +95,8 @@ def video_reports(args, M, stem, device, rank):
     stems = [f"{i:06d}" for i in range(len(M))]
     names = (f"{stem}-objects.json", f"{stem}-tracks.json")
     _objects(args, res, head, stems, M.shape[-1], rank, png=False, name=names[0])
-    _tracks(args, res, head, stems, rank, png=False, name=names[1], iou=args.overlay_tracks, gap=int(getattr(args, "overlay_gap", 0) or 0))
+    _tracks(args, res, head, stems, rank, png=False, name=names[1], iou=args.overlay_tracks, gap=int(getattr(args, "overlay_gap", 0) or 0),
+            bwd=bwd, search=int(getattr(args, "overlay_motion", 0) or 0) if bwd is not None else 0)
     return list(names)
 
 
@@ -112,18 +118,24 @@ def _objects(args, res, head, stems, width, rank, png=True, name="objects.json")
         Image.fromarray(np.repeat((mask[i] * np.uint8(255))[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-objects-mask.png")
 
 
-def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None, gap=None):
+def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None, gap=None, low=None, bwd=None, search=0):
     """The objects objects.json describes followed through the frames in natural order of their names on the GPU (objects.track);
     labels above 64 are untracked.  Rank 0 writes {R}/tracks.json and per frame {R}/{stem}-tracks-mask.png, a colour per track
     (png=False: the report alone, as {R}/{name}; iou, gap: the link threshold and the gap when they are not --track-iou's and
     --track-gap's).  With a gap G > 0 (objects.track's max_gap) the report also holds "track_gap", the summary's and the tracks' gap
-    keys and per object its "gap"; "last" is then the track's last frame, missed frames counted."""
+    keys and per object its "gap"; "last" is then the track's last frame, missed frames counted.  With search S > 0 (--track-motion,
+    --overlay-motion) the labels are carried along the backward block vectors (objects.track's motion): temporal.flow of low, uint8
+    [n,64,64,3] in the order of stems, taken in the tracked order, or bwd where the caller has the field; the report gains
+    "track_motion" (objects.motion_report)."""
     from PIL import Image
     K, iou = MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou) if iou is None else iou
     gap = int(getattr(args, "track_gap", 0) or 0) if gap is None else gap
     order = objects.natural_order(stems)                             # os.listdir's order is arbitrary; only the label stack is reordered
     pick = torch.tensor(order, dtype=torch.int64, device=res.labels.device)
-    tr = objects.track(res.labels[pick], iou=iou, max_objects=K, want_rgb=png, max_gap=gap)
+    if search and bwd is None:
+        from . import temporal
+        bwd = temporal.flow(low[pick], search)[1]
+    tr = objects.track(res.labels[pick], iou=iou, max_objects=K, want_rgb=png, max_gap=gap, motion=bwd if search else None)
     if rank != 0:
         return
     totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
@@ -135,7 +147,8 @@ def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None
     prev, trk = tr.prev.cpu().numpy(), tr.track.cpu().numpy()
     gaps = tr.gap.cpu().numpy() if gap else None
     last = (lambda r: r["last_frame"]) if gap else (lambda r: r["first_frame"] + r["length"] - 1)
-    report = {**head, "max_objects": K, "track_iou": iou, **({"track_gap": gap} if gap else {}), "summary": side, "order": names,
+    report = {**head, "max_objects": K, "track_iou": iou, **({"track_gap": gap} if gap else {}),
+              **({"track_motion": objects.motion_report(bwd, search)} if search else {}), "summary": side, "order": names,
               "frames": {stem: [{"label": int(l) + 1, "track": int(trk[j, l]), "prev": int(prev[j, l]),
                                  **({"gap": int(gaps[j, l])} if gap else {})} for l in np.flatnonzero(trk[j])]
                          for j, stem in enumerate(names)},

@@ -943,6 +943,38 @@ int cgs_objects_track_gap(const int32_t* labels, int32_t n, int32_t h, int32_t w
                           int32_t* gap_links, int32_t* tracks, int32_t* tracks_extra, int32_t* track_labels, uint8_t* rgb,
                           void* scratch, int64_t scratch_bytes, cgs_stream_t stream);
 
+/* cgs_objects_track_mc: cgs_objects_track_gap with the earlier frame's labels carried along a block motion field before they are
+ * intersected, at level 1 and at every gap level.  This comment is the specification.
+ *   bwd        int8 [n - 1][8][8][2], components (dy, dx), exactly as cgs_temporal_flow writes its backward field: bwd[g] belongs to
+ *              frames g + 1 -> g.  May be NULL only when n == 1 (it is not read then).
+ *   path       for a frame pair (a, f), g = f - a >= 1, and a cell q of frame f (cgs_temporal_smooth_mc's path for k < 0): m_0 = (0, 0);
+ *              for j = 0 .. g - 1: c = q + m_j with each coordinate clamped into 0..63, m_{j+1} = m_j + bwd[f - j - 1][c.y >> 3][c.x >> 3].
+ *   carried    W_{a->f}[q] = L_a[q + m_g] when that cell lies inside the grid, 0 otherwise (L_a: frame a's labels, those outside 1..K
+ *              read as 0).  A gather: no cell has two sources, none is undefined.
+ *   linking    cgs_objects_track_gap's rule with W_{a->f} where L_a stood.  Level 1: all objects of f - 1 and f, pairs counted over the
+ *              cells q as (W[q], L_f[q]), best partner from both sides (largest IoU, ties to the smallest number), mutual best and inter >
+ *              0 && 1000 inter >= iou_milli union.  union = carried area + area of the later object - inter, the carried area being the
+ *              number of cells of W that hold the label: an object half out of the frame after a pan is compared by the half that is
+ *              seen.  Levels g = 2 .. G + 1: the open tails of f - g (carried over g steps) against the open heads of f, every other
+ *              label read as 0, level by level.
+ *   outputs    prev, gap, track, totals, gap_links, tracks, tracks_extra, track_labels, rgb as cgs_objects_track_gap.  area_sum / area_min
+ *              / area_max stay the objects' true areas (counted where the object is); inter_sum / union_sum are those of the links as
+ *              decided (with the carried areas).
+ *   scratch    cgs_objects_track_mc_scratch_bytes(n, max_objects, max_gap) = cgs_objects_track_gap_scratch_bytes of the same arguments
+ * An all-zero field gives cgs_objects_track_gap's outputs bit for bit.  A link (a -> f) depends on the labels of frames a and f and on
+ * bwd[a .. f - 1] only.  No read is out of range for any int8 content of bwd or any int32 content of labels (|m| <= 9 * 128); vectors
+ * beyond the search range of the flow merely carry further.  Compensated: translation by whole cells, constant over a block of 8 x 8
+ * cells.  Not compensated: motion of a fraction of a cell, motion inside a block, occlusion; there is no forward / backward consistency
+ * check.  One workgroup per frame pair and level, frame a's labels staged in LDS (a byte per cell); the launches are
+ * cgs_objects_track_gap's in number, with the level-1 count in place of cgs_objects_match.  max_gap in 0..8, bwd NULL only when n == 1,
+ * and cgs_objects_track_gap's other checks, else CGS_ERR_BADARG; then h == w == 64 (the field is 8 x 8 blocks over 64 x 64 cells),
+ * max_objects <= 64, n <= CGS_OBJ_TRACK_MAX_FRAMES, else CGS_ERR_UNSUPPORTED.  A bad argument launches nothing.                        */
+int64_t cgs_objects_track_mc_scratch_bytes(int32_t n, int32_t max_objects, int32_t max_gap);
+int cgs_objects_track_mc(const int32_t* labels, const int8_t* bwd, int32_t n, int32_t h, int32_t w, int32_t max_objects,
+                         int32_t iou_milli, int32_t max_gap, int32_t max_tracks, int32_t* prev, int32_t* gap, int32_t* track,
+                         int32_t* totals, int32_t* gap_links, int32_t* tracks, int32_t* tracks_extra, int32_t* track_labels, uint8_t* rgb,
+                         void* scratch, int64_t scratch_bytes, cgs_stream_t stream);
+
 /* ---- the saliency baseline over a threshold grid (csrc/saliency.hip; Handler._saliency_post, main.py:976-1003; this build's own
  * -eval -salience --salience-grid) -----------------------------------------------------------------------------------------------------
  * The baseline's whole post-processing for T thresholds at once, each threshold with its own normaliser as the host form has it.  A
