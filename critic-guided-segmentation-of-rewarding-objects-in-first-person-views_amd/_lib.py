@@ -62,6 +62,7 @@ VIS_VALUES, VIS_CELL_W, VIS_CELL_H, VIS_NONTEMPORAL = 2, 64, 16, 1              
 VIS_INDEX_X, VIS_VALUE_X, VIS_VALUE_Y, VIS_VALUE_DY = 230, 1, 1, 15
 SHEET_ROWS, SHEET_MAX_N = 7, 1 << 20                                            # cgs_sheet_compose (include/cgs_hip.h)
 OBJ_U8, OBJ_F32_GT, OBJ_F32_GE, OBJ_FIELDS, OBJ_MAX_SIDE = 0, 1, 2, 8, 64       # cgs_objects_label (include/cgs_hip.h)
+CLEAN_FIELDS, CLEAN_MAX_RADIUS, CLEAN_SQUARE, CLEAN_CROSS, CLEAN_MAX_FILL = 8, 4, 0, 1, 4096      # cgs_mask_clean (include/cgs_hip.h)
 OBJ_MATCH_MAX_OBJECTS, OBJ_MATCH_MAX_IOU = 64, 16                               # cgs_objects_match (include/cgs_hip.h)
 OBJ_TRACK_FIELDS, OBJ_TRACK_MAX_FRAMES = 8, 1 << 17                             # cgs_objects_track (include/cgs_hip.h)
 OBJ_TRACK_MAX_GAP = 8                                                           # cgs_objects_track_gap: a judgement, not a measured value
@@ -216,6 +217,7 @@ SIGNATURES = {
     "cgs_iou_curve": (i32, [vp, vp, vp, i32, i32, i64, vp, vp]),
     "cgs_iou_counts": (i32, [vp, vp, i32, i64, vp, vp]),
     "cgs_objects_label": (i32, [vp, i32, f32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "cgs_mask_clean": (i32, [vp, i32, f32, i32, f32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "cgs_objects_match": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]),
     "cgs_objects_track_scratch_bytes": (i64, [i32, i32]),
     "cgs_objects_track": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp]),

@@ -84,6 +84,13 @@ def build_parser():
     p.add_argument("--overlay-boxes", type=int, default=None)
     p.add_argument("--overlay-gap", type=str, default=None)
     p.add_argument("--overlay-motion", type=str, default=None)
+    # (this build's own flags) --clean SPEC with -process or -eval, --overlay-clean SPEC with --source-video: the thresholded mask (with
+    # -crf the CRF mask) cleaned on the GPU before anything reads it (clean.py): "hyst=0.8;open=1;close=2;fill=16;shape=cross;conn=4" --
+    # hysteresis with the strong threshold, opening and closing radii 0..4, holes of up to so many pixels filled, square | cross, 4 | 8.
+    # -process leaves {stem}-clean-mask.png and clean.json, -eval eval_clean.json; -objects, --match-iou, --track-iou and
+    # --boundary-tol then describe the cleaned masks, and the overlay video draws them.  check_clean_flags parses both into dicts
+    p.add_argument("--clean", type=str, default=None)
+    p.add_argument("--overlay-clean", type=str, default=None)
     for flag in ("-masker", "-critic", "-cload", "-mload", "-staticnorm", "-visbesteval", "-salglobal"):
         p.add_argument(flag, type=bool, default=True)
     p.add_argument("--salience-thresh", type=float, default="1.5")
@@ -141,6 +148,7 @@ def parse_args(argv=None):
     check_objects_flags(args)
     check_video_flags(args)
     check_fit_flags(args)
+    check_clean_flags(args)
     return args
 
 
@@ -313,6 +321,40 @@ def check_video_flags(args):
         from .objects import parse_track_motion
         args.overlay_motion = 0 if args.overlay_motion is None else parse_track_motion(args.overlay_motion, "--overlay-motion")
     args.fit = True
+
+
+def check_clean_flags(args):
+    """--clean / --overlay-clean: a malformed spec and combinations that could not run are refused here, before any GPU work; both
+    become clean.parse_clean's dict (None without the flag).  `hyst` needs a soft source (no -crf) and must not lie below the
+    threshold the path compares with: --binarymaskthreshold for -process and --source-video, --eval-thresh for -eval."""
+    from .clean import parse_clean
+    if args.overlay_clean is not None:
+        if not args.source_video:
+            raise ValueError("--overlay-clean cleans the masks of --source-video: give --source-video (the flag of -process and -eval "
+                             "is --clean)")
+        args.overlay_clean = spec = parse_clean(args.overlay_clean, "--overlay-clean")
+        if not args.binarymaskthreshold:
+            raise ValueError("--overlay-clean cleans the thresholded mask: --binarymaskthreshold 0 leaves nothing to clean")
+        if spec["hyst"] is not None and spec["hyst"] < args.binarymaskthreshold:
+            raise ValueError(f"--overlay-clean hyst={spec['hyst']!r} lies below --binarymaskthreshold {args.binarymaskthreshold!r}: the "
+                             "strong threshold is the higher of the two")
+    if args.clean is None:
+        return
+    if args.source_video:
+        raise ValueError("--clean with --source-video: the flag there is --overlay-clean")
+    if not (args.process or args.eval):
+        raise ValueError("--clean cleans the masks of -process or -eval (or -test): give one of them")
+    args.clean = spec = parse_clean(args.clean, "--clean")
+    if args.process and not args.binarymaskthreshold and not args.crf:
+        raise ValueError("-process --clean cleans the thresholded mask (or with -crf the CRF mask): --binarymaskthreshold 0 without "
+                         "-crf leaves nothing to clean")
+    if spec["hyst"] is None:
+        return
+    if args.crf:
+        raise ValueError("--clean hyst=... with -crf: the CRF mask is hard, it has no strong pixels (hysteresis needs the soft mask)")
+    for on, flag, thr in ((args.process, "--binarymaskthreshold", args.binarymaskthreshold), (args.eval, "--eval-thresh", args.eval_thresh)):
+        if on and spec["hyst"] < thr:
+            raise ValueError(f"--clean hyst={spec['hyst']!r} lies below {flag} {thr!r}: the strong threshold is the higher of the two")
 
 
 def check_video_size(w, h, panels):

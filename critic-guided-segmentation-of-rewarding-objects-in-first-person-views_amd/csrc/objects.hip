@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "cgs_common.h"
+#include "unionfind_rows.h"
 
 namespace {
 
@@ -35,40 +36,6 @@ constexpr int OBJ_MAX_SIDE = 64;                      // a row is one wave-wide 
 constexpr int OBJ_MAX_PX = OBJ_MAX_SIDE * OBJ_MAX_SIDE;
 constexpr int OBJ_CHUNK = 256;                        // objects per pass of the table
 constexpr int OBJ_FIELDS = 8;                         // area, x0, y0, x1, y1, sum_x, sum_y, first
-
-__device__ __forceinline__ int lds_get(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void lds_put(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-__device__ __forceinline__ int find_root(int* L, int a) {
-    int p;
-    while ((p = lds_get(&L[a])) != a) a = p;
-    return a;
-}
-
-// the root of a; a itself is pointed at it on the way out (it is no root, so this cannot undo a union; parents only decrease)
-__device__ __forceinline__ int find_compress(int* L, int a) {
-    const int r = find_root(L, a);
-    if (r != a) atomicMin(&L[a], r);
-    return r;
-}
-
-__device__ __forceinline__ void unite(int* L, int a, int b) {
-    for (;;) {
-        const int ra = find_compress(L, a), rb = find_compress(L, b);
-        if (ra == rb) return;
-        const int hi = max(ra, rb), lo = min(ra, rb);
-        const int old = atomicMin(&L[hi], lo);
-        if (old == hi) return;                         // hi was still a root: it hangs below lo now
-        a = old;                                       // hi had got a parent meanwhile; hi points at min(old, lo), and what is left to
-        b = lo;                                        // join is the tree of that parent with lo's
-    }
-}
-
-// start column of the run of on-pixels that holds column `lane` of the row with on-mask m (lane is on); lt = bits below lane
-__device__ __forceinline__ int run_start(unsigned long long m, unsigned long long lt) {
-    const unsigned long long zeros = ~m & lt;
-    return zeros ? 64 - __clzll((long long)zeros) : 0;
-}
 
 __global__ void __launch_bounds__(OBJ_THREADS)
 objects_kernel(const void* __restrict__ src, int kind, float thresh, int h, int w, int conn8, int min_area, int max_objects,
@@ -109,18 +76,7 @@ objects_kernel(const void* __restrict__ src, int kind, float thresh, int h, int 
     for (int y = wave; y < h; y += OBJ_WAVES) {
         if (y == 0) continue;
         const unsigned long long cur = s_row[y], up = s_row[y - 1];
-        if ((cur >> x) & 1ull) {
-            const bool U = (up >> x) & 1ull;
-            const bool UL = x > 0 && ((up >> (x - 1)) & 1ull), UR = x < 63 && ((up >> (x + 1)) & 1ull);
-            const bool Lf = x > 0 && ((cur >> (x - 1)) & 1ull), Rt = x < 63 && ((cur >> (x + 1)) & 1ull);
-            const int p = y * w + x;
-            if (U) {
-                if (!(Lf && UL)) unite(s_L, p, p - w);                     // else the pixel to the left joined the same two runs
-            } else if (conn8) {
-                if (UL && !Lf) unite(s_L, p, p - w - 1);                   // Lf: the left pixel has this run straight above it
-                if (UR && !Rt) unite(s_L, p, p - w + 1);                   // Rt: so has the right pixel
-            }
-        }
+        if ((cur >> x) & 1ull) unite_with_row_above(s_L, cur, up, y, x, w, conn8 != 0);
     }
     __syncthreads();
 

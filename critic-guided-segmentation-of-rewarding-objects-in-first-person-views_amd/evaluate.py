@@ -1,5 +1,5 @@
 """The reports of ``-eval`` (handler.Handler.eval): the threshold, saliency and CRF-grid sweeps of eval_sweep.json, and
-eval_objects.json, eval_match.json, eval_tracks.json, eval_boundary.json.  ``Stacks`` holds the stacks of one run on the device: each
+eval_objects.json, eval_match.json, eval_tracks.json, eval_boundary.json, eval_clean.json.  ``Stacks`` holds the stacks of one run on the device: each
 is uploaded when a report first reads it, labelled (objects.label) once per source and matched (objects.match) once per source and
 threshold list.  A report function takes (args, stacks) and returns (the dict of its file, its summary line); everything is scored on
 the GPU and only counts come back.  ``write_json`` is the one writer of every report, here and in process.py."""
@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from . import boundary, metrics, objects, saliency, temporal
+from . import boundary, clean, metrics, objects, saliency, temporal
 
 MATCH_MAX_OBJECTS = 64          # objects per frame and side that --match-iou matches and --track-iou follows
 
@@ -60,13 +60,25 @@ class Stacks:
     def thresh(self, name):
         return float(self.args.eval_thresh) if name == "mask" else None
 
+    def cleaned(self, name):
+        """--clean: clean.clean's result for "mask" (read at --eval-thresh, strict) or "crf", made once; its mask is the derived hard
+        stack "mask_clean" / "crf_clean"."""
+        return self._once(("clean", name), lambda: clean.clean(self.dev(name), thresh=self.thresh(name), **clean.spec_kwargs(self.args.clean)))
+
+    def object_source(self, name):
+        """(stack, threshold) the object reports label for a source: with --clean the cleaned stack of a prediction (hard: None)."""
+        if getattr(self.args, "clean", None) and name in ("mask", "crf"):
+            return self.cleaned(name).mask, None
+        return self.dev(name), self.thresh(name)
+
     def labelled(self, name):
         """objects.label's result for a stack, labels and kept-pixel mask: a prediction with --connectivity and --min-area (the
         objects eval_objects.json counts), the truth unfiltered.  One call serves every report: labels, mask, found and kept do not
-        depend on max_objects, and no report reads the table."""
+        depend on max_objects, and no report reads the table.  With --clean a prediction is labelled after the clean-up."""
         a = self.args
+        src, thresh = self.object_source(name)
         return self._once(("label", name), lambda: objects.label(
-            self.dev(name), thresh=self.thresh(name), connectivity=a.connectivity, min_area=1 if name == "truth" else a.min_area,
+            src, thresh=thresh, connectivity=a.connectivity, min_area=1 if name == "truth" else a.min_area,
             max_objects=MATCH_MAX_OBJECTS, want_labels=True, want_mask=name != "truth"))
 
     def matched(self, name, iou):
@@ -76,7 +88,8 @@ class Stacks:
 
 
 def _head(args, **more):
-    return {"connectivity": args.connectivity, "min_area": args.min_area, "threshold": float(args.eval_thresh), **more}
+    cleaned = {"clean": dict(args.clean)} if getattr(args, "clean", None) else {}
+    return {"connectivity": args.connectivity, "min_area": args.min_area, "threshold": float(args.eval_thresh), **cleaned, **more}
 
 
 def _blocks(st, report):
@@ -119,8 +132,8 @@ def crf_grid(args, st, tables):
 # ---------------------------------------------------------------------------------------------------------------- the objects
 def _objects_block(st, name):
     """One block of eval_objects.json: the kept pixels of a labelled stack and the unfiltered stack scored against the truth with
-    metrics.iou_counts / iou_curve.  Only the counts come back."""
-    res, src, truth, thresh = st.labelled(name), st.dev(name), st.dev("truth"), st.thresh(name)
+    metrics.iou_counts / iou_curve (with --clean both are the cleaned stack's).  Only the counts come back."""
+    res, (src, thresh), truth = st.labelled(name), st.object_source(name), st.dev("truth")
     inter, union = metrics.iou_counts(res.mask, truth).tolist()
     if thresh is None:
         inter0, union0 = metrics.iou_counts(src, truth).tolist()
@@ -210,12 +223,44 @@ def tracks_report(args, st):
                     f"{truth_side['objects']} objects")
 
 
+# ---------------------------------------------------------------------------------------------------------------- the clean-up
+def _scores(inter, union, pred_on, truth_on):
+    return {"inter": inter, "union": union, "iou": metrics.ratio(inter, union), "precision": metrics.ratio(inter, pred_on),
+            "recall": metrics.ratio(inter, truth_on)}
+
+
+def clean_report(args, st):
+    """--clean: every prediction cleaned on the GPU (clean.clean) and scored against the truth with metrics.iou_counts, beside the
+    same figures of the uncleaned stack; the clean-up's own counts are summed.  Only counts come back."""
+    truth = st.dev("truth")
+    truth_on = int(np.count_nonzero(st.host["truth"]))
+    report = {"clean": dict(args.clean), "threshold": float(args.eval_thresh)}
+    for name in st.names(("mask", "crf")):
+        res, src, thresh = st.cleaned(name), st.dev(name), st.thresh(name)
+        sums = clean.clean_report(res.counts, args.clean)
+        inter, union = metrics.iou_counts(res.mask, truth).tolist()
+        if thresh is None:
+            inter0, union0 = metrics.iou_counts(src, truth).tolist()
+        else:
+            inter0, union0 = (int(c[0]) for c in metrics.iou_curve(src, truth, [thresh]))
+        report[name + "_clean"] = {**_scores(inter, union, sums["after_fill"], truth_on),
+                                   "uncleaned": _scores(inter0, union0, sums["on"], truth_on),
+                                   "counts": {k: sums[k] for k in clean.COUNTS}}
+    report = _json_safe(report)
+    return report, f"\nCLEAN {clean.spec_text(args.clean)}: " + "; ".join(
+        f"{pre}iou {fmt(b['iou'])} (uncleaned {fmt(b['uncleaned']['iou'])}), {b['counts']['holes_filled']} holes filled, "
+        f"{b['counts']['components_dropped']} components dropped"
+        for pre, b in (("" if name == "mask" else name + " ", report[name + "_clean"]) for name in st.names(("mask", "crf"))))
+
+
 # ---------------------------------------------------------------------------------------------------------------- the outlines
 def boundary_report(args, st):
     """--boundary-tol: the outline of every hard stack, and with -objects of the mask eval_objects.json scores (small objects removed),
     against the truth's outline on the GPU (boundary.score); only the per-frame counts come back."""
     tol = boundary.parse_boundary_tol(args.boundary_tol)
     stacks = [(name, st.dev(name), st.thresh(name)) for name in st.names()]
+    if getattr(args, "clean", None):
+        stacks += [(name + "_clean", st.cleaned(name).mask, None) for name in st.names(("mask", "crf"))]
     if getattr(args, "objects", False):
         stacks.append(("mask_objects", st.labelled("mask").mask, None))
     report = {"tol": tol, "tol2": boundary.tol_squared(tol), "threshold": float(args.eval_thresh)}

@@ -77,6 +77,7 @@ class Handler:
         self.matches = None         # -eval -objects --match-iou: the dict of eval_match.json
         self.tracks = None          # -eval -objects --track-iou: the dict of eval_tracks.json
         self.boundary = None        # -eval --boundary-tol: the dict of eval_boundary.json
+        self.clean = None           # -eval --clean: the dict of eval_clean.json
         self._trace = None          # tests set a dict of lists (Handler.start_trace): per-step indices / losses of the two training loops
 
     def start_trace(self):
@@ -472,9 +473,16 @@ class Handler:
             cols.append(M >= args.binarymaskthreshold)
         if args.crf:                    # main.py:1169-1172 (with --binarymaskthreshold 0 this column lands in position 2)
             cols.append(self.crf(frames, M, None))
+        cleaned = None
+        if getattr(args, "clean", None):        # (this build's flag) not a column either: {stem}-clean-mask.png and clean.json
+            os.makedirs(args.mask_output_imgs, exist_ok=True)
+            source, thresh, res = process.clean_source(args, M[:, 0], cols[-1][:, 0] if args.crf else None, self.device)
+            cleaned = res.mask
+            process.write_clean(args, source, thresh, res.counts, stems[:len(frames)], self.rank, pngs=cleaned.cpu().numpy())
         if getattr(args, "objects", False):     # (this build's flag) not a column: the by-position naming and the strip stay as they are
             process.objects_and_tracks(args, M, cols[-1] if args.crf else None, stems[:len(frames)], self.device, self.rank,
-                                       low=np.ascontiguousarray(file_bytes, dtype=np.uint8) if getattr(args, "track_motion", 0) else None)
+                                       low=np.ascontiguousarray(file_bytes, dtype=np.uint8) if getattr(args, "track_motion", 0) else None,
+                                       cleaned=cleaned)
         if args.process_salience:       # main.py:1176-1197
             sal_maps, sal_hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
             cols += [sal_maps, sal_hard]
@@ -524,6 +532,8 @@ class Handler:
         sig = dict(sigma_s=args.fit_spatial, sigma_r=args.fit_range)
         step = process.chunk_frames(self.FIT_CHUNK_FRAMES, self.FIT_CHUNK_BYTES, H, W)
         masks, crf_masks = [], []
+        spec = getattr(args, "clean", None)              # --clean: per chunk the cleaned 64 x 64 masks and their counts, on the device
+        cleaned, clean_counts, clean_head = [], [], None
         lows = [] if getattr(args, "objects", False) and getattr(args, "track_motion", 0) else None     # --track-motion: the shrunk frames
         unit = process.unit_table(self.device)
         for lo in range(0, len(files), step):
@@ -545,13 +555,23 @@ class Handler:
                 crf_masks.append(labels)
                 dev_labels = torch.from_numpy(np.ascontiguousarray(labels[:, 0]).view(np.uint8)).to(self.device)
                 cols.append(fit.up(dev_labels, guide, low, thresh=0.5, want=("hard",), **sig).hard.cpu().numpy() * np.uint8(255))
+            if spec:                                     # brought to H x W as the CRF labels are; not a column
+                source, thresh, res = process.clean_source(args, Z, labels[:, 0] if args.crf else None, self.device)
+                clean_head = (source, thresh)
+                cleaned.append(res.mask)
+                clean_counts.append(res.counts)
+                big = fit.up(res.mask.view(torch.uint8), guide, low, thresh=0.5, want=("hard",), **sig).hard
+                if self.rank == 0:
+                    process.write_clean_pngs(out_dir, stems[lo:lo + len(host)], big.cpu().numpy())
             process.write_columns(out_dir, stems[lo:lo + len(host)], host, cols, args.concatenated)
         print()
         M = np.concatenate(masks, axis=0)
         crf_mask = np.concatenate(crf_masks, axis=0) if args.crf else None
+        if spec:
+            process.write_clean(args, *clean_head, torch.cat(clean_counts), stems[:len(files)], self.rank)
         if getattr(args, "objects", False):
             process.objects_and_tracks(args, M, crf_mask, stems[:len(files)], self.device, self.rank,
-                                       low=torch.cat(lows) if lows is not None else None)
+                                       low=torch.cat(lows) if lows is not None else None, cleaned=torch.cat(cleaned) if spec else None)
         write_json(f"{out_dir}/fit.json", {"frame_size": [H, W], "net_size": [fit.SIDE, fit.SIDE], "sigma_spatial": args.fit_spatial,
                                            "sigma_range": args.fit_range, "radius": fit.RADIUS, "frames": len(files)}, self.rank)
         return M
@@ -574,11 +594,15 @@ class Handler:
         Stage A of chunk c + 1 runs before stage B of chunk c (a chunk waits until R frames after it are there, or the stream has ended).
         No PNG is written.  Rank 0 leaves {R}/{stem of OUT}.json, with --overlay-tracks also {R}/{stem}-objects.json and
         {R}/{stem}-tracks.json (process.video_reports; skipped beyond objects.TRACK_MAX_FRAMES frames, the video is complete all the
-        same).  Returns the 64 x 64 masks [n,1,64,64], the smoothed ones with --smooth."""
+        same).  With --overlay-clean SPEC the masks are replaced, after --smooth and before fit.up and the labelling, by clean.clean's
+        `gated` at --binarymaskthreshold: tint, outline, track labels and the reports follow the cleaned mask, and {stem}.json gains
+        "clean".  Returns the 64 x 64 masks [n,1,64,64], the smoothed ones with --smooth, the gated ones with --overlay-clean."""
         from collections import deque
         import subprocess
-        from . import cli, fit, objects, overlay, temporal, video_in
+        from . import clean, cli, fit, objects, overlay, temporal, video_in
         args = self.args
+        spec = getattr(args, "overlay_clean", None)                           # --overlay-clean: the parsed spec
+        clean_counts = torch.zeros(len(clean.COUNTS), dtype=torch.int64, device=self.device) if spec else None
         track_iou = getattr(args, "overlay_tracks", None)
         track_gap = int(getattr(args, "overlay_gap", 0) or 0)                 # --overlay-gap: objects.TrackStream's max_gap
         track_motion = int(getattr(args, "overlay_motion", 0) or 0)           # --overlay-motion: the search range of its block vectors
@@ -615,7 +639,7 @@ class Handler:
             return guide, low, process.fit_infer(eng, low, unit, fp16, bool(args.noevalmode)).contiguous().clone()
 
         def stage_b():
-            nonlocal tail, moved, vectors, before_low
+            nonlocal tail, moved, vectors, before_low, clean_counts
             guide, low, Z = pending.popleft()
             if R:
                 zs, ls = [Z], [low]
@@ -642,6 +666,9 @@ class Handler:
                 tail = (before[0][-R:], before[1][-R:])
             else:
                 Zs = Z
+            if spec:                                   # per frame, so the chunking does not show: gated >= thr is the cleaned mask
+                res = clean.clean(Zs, thresh=thr, inclusive=True, want_gated=True, **clean.spec_kwargs(spec))
+                Zs, clean_counts = res.gated, clean_counts + res.counts.sum(dim=0, dtype=torch.int64)
             masks.append(Zs.cpu().numpy()[:, None])
             up = fit.up(Zs, guide, low, thresh=thr if thr else None, want=("grey", "hard") if thr else ("grey",), **sig)
             if stream is not None:
@@ -717,7 +744,8 @@ class Handler:
             "frame_size": [H, W], "frames": len(M), "rate": rate, "layout": args.overlay_layout, "color": list(args.overlay_color),
             "alpha256": args.overlay_alpha256, "outline": args.overlay_outline, "threshold": thr,
             "smooth": smooth,
-            "sigma_spatial": args.fit_spatial, "sigma_range": args.fit_range, **tracks}, self.rank)
+            "sigma_spatial": args.fit_spatial, "sigma_range": args.fit_range, **tracks,
+            **({"clean": {**clean.clean_report(clean_counts, spec), "frames": len(M)}} if spec else {})}, self.rank)
         return M
 
     def _sweep_masks(self, X, to_device, progress, want_saliency=False, fp16=False, batchsize=128, train_mode=None):
@@ -872,6 +900,8 @@ class Handler:
         if sweep:
             self.sweep = sweep
             write_json(self.path + "eval_sweep.json", sweep, self.rank)
+        if getattr(args, "clean", None):        # (this build's flag) the masks cleaned on the GPU; the reports below then read those
+            self.clean = report(evaluate.clean_report, "eval_clean.json")
         if getattr(args, "objects", False):     # (this build's flags) the masks as objects, matched to the truth's, followed through the frames
             self.objects = report(evaluate.objects_report, "eval_objects.json")
             if getattr(args, "match_iou", ""):

@@ -1,14 +1,15 @@
 """What the three ``-process`` paths of handler.Handler share (segment, _segment_fit, _segment_video): the folder listing, the chunk
 size, how a shrunk uint8 frame is fed to the network, the PNG columns with their by-position names, and ``-objects`` /
 ``--track-iou`` on the 64 x 64 masks (objects.json, tracks.json and their PNGs; ``video_reports`` writes the two reports of
-``--source-video --overlay-tracks`` without PNGs).  Under data parallelism every rank makes the GPU
+``--source-video --overlay-tracks`` without PNGs), and ``--clean`` (``clean_source``, ``write_clean``: clean.json and the
+{stem}-clean-mask.png files).  Under data parallelism every rank makes the GPU
 calls and rank 0 writes."""
 import os
 
 import numpy as np
 import torch
 
-from . import objects
+from . import clean, objects
 from .evaluate import MATCH_MAX_OBJECTS, write_json
 
 PROCESS_MAX_OBJECTS = 256       # rows of the object table of -process -objects
@@ -54,10 +55,13 @@ def write_columns(out_dir, stems, frames, cols, concatenated):
                 Image.fromarray(rgb(c[i])).save(f"{out_dir}/{stem}-{kind}.png")
 
 
-def binary_source(args, M, crf_mask, device):
+def binary_source(args, M, crf_mask, device, cleaned=None):
     """The stack -objects and --track-iou describe: (source name, threshold, device stack, objects.label's keywords) -- with -crf the
-    CRF masks, else M >= --binarymaskthreshold (the comparison of the thresholded column)."""
+    CRF masks, else M >= --binarymaskthreshold (the comparison of the thresholded column).  cleaned: with --clean the bool stack
+    clean_source made of that one; it is handed on under the name "clean-mask" / "clean-crf-mask"."""
     kw = dict(connectivity=args.connectivity, min_area=args.min_area)
+    if cleaned is not None:
+        return ("clean-crf-mask", None, cleaned, kw) if crf_mask is not None else ("clean-mask", float(args.binarymaskthreshold), cleaned, kw)
     if crf_mask is not None:
         return "crf-mask", None, torch.from_numpy(np.ascontiguousarray(crf_mask[:, 0])).to(device), kw
     thresh = float(args.binarymaskthreshold)
@@ -65,14 +69,50 @@ def binary_source(args, M, crf_mask, device):
             dict(kw, thresh=thresh, inclusive=True))
 
 
-def objects_and_tracks(args, M, crf_mask, stems, device, rank, low=None):
+def clean_source(args, soft, hard, device):
+    """--clean: the stack binary_source names, cleaned on the GPU (clean.clean).  soft: the masks [n,64,64] float32 (array or tensor),
+    read as soft >= --binarymaskthreshold; hard: with -crf the CRF labels [n,64,64] bool, which then are the source.  Returns (source
+    name, threshold, clean.Cleaned on the device)."""
+    to_dev = lambda a, dtype: a.to(device) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(device)
+    kw = clean.spec_kwargs(args.clean)
+    if hard is not None:
+        return "crf-mask", None, clean.clean(to_dev(hard, bool), **kw)
+    thresh = float(args.binarymaskthreshold)
+    return "thresholded-mask", thresh, clean.clean(to_dev(soft, np.float32), thresh=thresh, inclusive=True, **kw)
+
+
+def write_clean(args, source, thresh, counts, stems, rank, pngs=None):
+    """Rank 0 writes {R}/clean.json -- the spec, the source and its threshold, the summed counts and the counts per stem -- and, when
+    pngs (uint8 [n,H,W], 0 / 1) is given, per frame {R}/{stem}-clean-mask.png as 0 / 255 grey RGB (not a column: the by-position naming
+    and the concatenated strip stay as they are).  counts: int32 [n,8] of clean.clean, tensor or array."""
+    if rank != 0:
+        return
+    out_dir = args.mask_output_imgs
+    c = counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    write_json(f"{out_dir}/clean.json", {"source": source, "threshold": thresh, **clean.clean_report(c, args.clean),
+                                         "per_frame": {stem: {k: int(v) for k, v in zip(clean.COUNTS, c[i])} for i, stem in enumerate(stems)}})
+    if pngs is not None:
+        write_clean_pngs(out_dir, stems, pngs)
+
+
+def write_clean_pngs(out_dir, stems, masks):
+    """{R}/{stem}-clean-mask.png of a run of frames: masks uint8 or bool [n,H,W], non-zero = on, written as 0 / 255 grey RGB."""
+    from PIL import Image
+    for i, stem in enumerate(stems):
+        grey = (np.asarray(masks[i]) != 0) * np.uint8(255)
+        Image.fromarray(np.repeat(grey[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-clean-mask.png")
+
+
+def objects_and_tracks(args, M, crf_mask, stems, device, rank, low=None, cleaned=None):
     """-process -objects [--track-iou]: the stack of binary_source labelled on the GPU once (objects.py; labels, mask and counts do not
     depend on the table's rows), then reported as objects and, if asked for, as tracks.  low: with --track-motion the uint8 frames
-    [n,64,64,3] the masks were made from (tensor or array, in the order of stems)."""
+    [n,64,64,3] the masks were made from (tensor or array, in the order of stems).  cleaned: with --clean the cleaned bool stack on the
+    device, which is then the one described; the reports' header gains "clean"."""
     want_tracks = bool(getattr(args, "track_iou", ""))
-    source, thresh, stack, kw = binary_source(args, M, crf_mask, device)
+    source, thresh, stack, kw = binary_source(args, M, crf_mask, device, cleaned)
     res = objects.label(stack, max_objects=PROCESS_MAX_OBJECTS, want_labels=want_tracks, want_mask=True, **kw)
-    head = {"source": source, "threshold": thresh, "connectivity": args.connectivity, "min_area": args.min_area}
+    head = {"source": source, "threshold": thresh, "connectivity": args.connectivity, "min_area": args.min_area,
+            **({"clean": dict(args.clean)} if cleaned is not None else {})}
     _objects(args, res, head, stems, M.shape[-1], rank)
     if want_tracks:
         search = int(getattr(args, "track_motion", 0) or 0)

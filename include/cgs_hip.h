@@ -841,6 +841,36 @@ int cgs_objects_label(const void* src, int32_t src_kind, float thresh, int32_t n
                       int32_t min_area, int32_t max_objects, int32_t* labels, uint8_t* kept_mask, int32_t* count, int32_t* table,
                       cgs_stream_t stream);
 
+/* ---- mask clean-up (csrc/clean.hip; this build's own --clean / --overlay-clean, no counterpart in the reference) -------------------------
+ * The standard steps between a soft mask and its objects, for n frames of h x w (contiguous), one workgroup per frame, the frame as 64
+ * bit rows in LDS.  Integer or pure selection throughout: deterministic, bit for bit.  The stages, in this fixed order:
+ *   on     src_kind, thresh and NaN exactly as in cgs_objects_label (CGS_OBJ_U8, CGS_OBJ_F32_GT, CGS_OBJ_F32_GE; a NaN is off)
+ *   hyst   (hyst != 0; fp32 sources only) a `connectivity`-connected (4 or 8) component of the on pixels is kept only when at least
+ *          one of its pixels is strong: v > strong for _GT, v >= strong for _GE, compared in fp32
+ *   open   by open_r, then close by close_r (each 0..CGS_CLEAN_MAX_RADIUS, 0: off).  Opening is erosion then dilation, closing dilation
+ *          then erosion; a step over radius r is r iterations of the 8-neighbour step for CGS_CLEAN_SQUARE (the (2r+1)^2 square) and
+ *          of the 4-neighbour step for CGS_CLEAN_CROSS (the diamond).  Dilation reads everything outside the frame as off, erosion
+ *          reads it as ON (scipy's binary_dilation(border_value=0), binary_erosion(border_value=1)): a mask cut by the frame's edge is
+ *          not eaten from the edge, opening stays anti-extensive and closing extensive, and both are idempotent
+ *   fill   (fill_area 1..4096; 0: off) a hole is a component of OFF pixels at the complementary connectivity (4 when connectivity is
+ *          8, 8 when it is 4) that has no pixel in the first or last row or column; a hole of at most fill_area pixels is turned on.
+ *          fill_area = 4096 is scipy.ndimage.binary_fill_holes with the complementary structure
+ *   out    uint8 [n][h][w], 0 / 1
+ *   gated  fp32 [n][h][w] or NULL (fp32 sources with thresh > 0 only): 0 where out is 0; where out is 1, v when v passes the threshold
+ *          compare and thresh otherwise (a filled or closed cell, a NaN).  No arithmetic: gated >= thresh reproduces out, and the
+ *          soft values of surviving cells keep their bits
+ *   counts int32 [n][CGS_CLEAN_FIELDS]: on pixels after the threshold, after hyst, after open, after close, after fill (a stage that
+ *          is off repeats the count before it), components dropped by hyst, holes found, holes filled (both 0 with fill off)
+ * Runs on `stream` without synchronising, allocates nothing, can be captured in a graph.  src, out, counts not NULL, n >= 1, a valid
+ * src_kind, connectivity and shape, radii in 0..4, fill_area in 0..4096, hyst only with an fp32 source, a finite strong and strong >=
+ * thresh, gated only with an fp32 source and thresh > 0, fp32 src / gated / counts 4-byte aligned, else CGS_ERR_BADARG; then 1 <= h, w
+ * <= 64, else CGS_ERR_UNSUPPORTED.  A refused call launches nothing.                                                                    */
+enum { CGS_CLEAN_FIELDS = 8, CGS_CLEAN_MAX_RADIUS = 4 };
+enum { CGS_CLEAN_SQUARE = 0, CGS_CLEAN_CROSS = 1 };
+int cgs_mask_clean(const void* src, int32_t src_kind, float thresh, int32_t hyst, float strong, int32_t n, int32_t h, int32_t w,
+                   int32_t connectivity, int32_t shape, int32_t open_r, int32_t close_r, int32_t fill_area, uint8_t* out, float* gated,
+                   int32_t* counts, cgs_stream_t stream);
+
 /* ---- from objects to matches (csrc/objects_match.hip; this build's own -eval -objects --match-iou, no counterpart in the reference) -------
  * Instance matching of two label maps per frame: every predicted object intersected with every truth object, one workgroup per frame,
  * the K x K intersection table and the areas in LDS (K = max_objects).  No floating point and only LDS integer atomics: deterministic,
