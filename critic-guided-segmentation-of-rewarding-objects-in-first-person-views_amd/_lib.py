@@ -226,6 +226,7 @@ SIGNATURES = {
     "cgs_objects_track_gap": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "cgs_objects_track_mc_scratch_bytes": (i64, [i32, i32, i32]),
     "cgs_objects_track_mc": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "cgs_objects_track_fill": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "cgs_saliency_sweep": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "cgs_boundary_score": (i32, [vp, i32, f32, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
     "cgs_fit_down_u8": (i32, [vp, i32, i32, i32, vp, vp]),

@@ -49,6 +49,10 @@ def build_parser():
     # (this build's own flag) --track-iou T --track-motion S: the earlier frame's labels are carried along block vectors of the 64 x 64
     # frames, up to S cells a frame (0..4, default 0 = off), before they are compared (objects.track's motion); an int after the check
     p.add_argument("--track-motion", type=str, default=None)
+    # (this build's own flag) --track-iou T --track-gap G --track-fill: the frames a bridged link jumps over get the mask of the link's
+    # tail object, carried there along the vectors of --track-motion (objects.fill); -process leaves {stem}-filled-mask.png and paints
+    # {stem}-tracks-mask.png from the filled labels, -eval adds "fill" to eval_tracks.json.  Not for --source-video
+    p.add_argument("--track-fill", action="store_true")
     # (this build's own flag) -eval --boundary-tol "0-1-2-3" or "lo:hi:n": every evaluated stack's outline against the truth's outline at
     # these tolerances in pixels -- boundary F, boundary IoU and the Hausdorff distance -- on the GPU (boundary.score); leaves
     # {model}/eval_boundary.json
@@ -179,10 +183,10 @@ def check_sweep_flags(args):
 
 
 def check_objects_flags(args):
-    """-objects / --min-area / --connectivity / --match-iou / --track-iou / --track-gap / --track-motion / --boundary-tol: combinations
-    that could not run and a malformed --match-iou, --track-iou, --track-gap, --track-motion or --boundary-tol are refused here, before
-    any GPU work; the defaults (--min-area 1, --connectivity 8, --track-gap 0 and --track-motion 0 as ints) are filled in.
-    --boundary-tol needs -eval, not -objects."""
+    """-objects / --min-area / --connectivity / --match-iou / --track-iou / --track-gap / --track-motion / --track-fill / --boundary-tol:
+    combinations that could not run and a malformed --match-iou, --track-iou, --track-gap, --track-motion or --boundary-tol are refused
+    here, before any GPU work; the defaults (--min-area 1, --connectivity 8, --track-gap 0 and --track-motion 0 as ints) are filled in.
+    --boundary-tol needs -eval, not -objects; --track-fill needs --track-iou and a --track-gap of at least 1, and no --source-video."""
     given = [f for f, v in (("--min-area", args.min_area), ("--connectivity", args.connectivity)) if v is not None]
     if args.match_iou:
         from .objects import parse_match_iou
@@ -215,6 +219,14 @@ def check_objects_flags(args):
         args.track_motion = parse_track_motion(args.track_motion)
     else:
         args.track_motion = 0
+    if args.track_fill:
+        if not args.track_iou:
+            raise ValueError("--track-fill belongs to --track-iou: give --track-iou T --track-gap G")
+        if not args.track_gap:
+            raise ValueError("--track-fill fills the frames that a bridged link jumps over: give --track-gap G with G in 1..8")
+        if args.source_video:
+            raise ValueError("--track-fill with --source-video: outside this build (the stream would have to look --overlay-gap frames "
+                             "ahead before it draws a frame)")
     if not args.objects:
         if given:
             raise ValueError(f"{' / '.join(given)} belong to -objects: give -objects")

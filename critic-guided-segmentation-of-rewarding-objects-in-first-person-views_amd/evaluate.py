@@ -187,15 +187,27 @@ def _tracked(labelled, iou, gap=0, motion=None):
     return tr, side
 
 
+def _fill_block(labels, tracks, motion, truth):
+    """--track-fill: one stack's "fill" of eval_tracks.json.  The frames its bridged links jump over are filled on the GPU (objects.fill)
+    and the labelled pixels before and after are scored against the truth in one metrics.iou_counts launch; the four counts of the fill
+    and the four of the score come back."""
+    fl = objects.fill(labels, tracks, motion=motion[0] if motion else None, max_objects=MATCH_MAX_OBJECTS, want_table=False)
+    (inter0, union0), (inter, union) = metrics.iou_counts(torch.stack([labels > 0, fl.labels > 0]), truth).tolist()
+    return {**objects.fill_report(fl), "inter": inter, "union": union, "iou": metrics.ratio(inter, union),
+            "inter_before": inter0, "union_before": union0, "iou_before": metrics.ratio(inter0, union0)}
+
+
 def tracks_report(args, st):
     """--track-iou: the same objects followed from frame to frame on the GPU; with --match-iou the identity switches at its thresholds,
     from the matches eval_match.json reports.  --track-gap G tracks truth and predictions with the same G (objects.track's max_gap);
     the switches then follow the truth's adjacent links only, and every threshold's entry gains "fragments" (objects.fragments).
-    --track-motion S tracks both along one field, temporal.flow of the evaluation frames as bytes (the stack "frames")."""
+    --track-motion S tracks both along one field, temporal.flow of the evaluation frames as bytes (the stack "frames").
+    --track-fill (with a gap) gives every predicted stack's side "fill" (_fill_block); the truth is tracked as ever and never filled."""
     t_iou = objects.parse_track_iou(args.track_iou)
     gap = int(getattr(args, "track_gap", 0) or 0)
     search = int(getattr(args, "track_motion", 0) or 0)
     motion = (temporal.flow(st.dev("frames"), search)[1], search) if search else None
+    fill = bool(getattr(args, "track_fill", False) and gap)
     m_iou = objects.parse_match_iou(args.match_iou) if getattr(args, "match_iou", "") else None
     truth_tr, truth_side = _tracked(st.labelled("truth"), t_iou, gap, motion)
     report = _head(args, max_objects=MATCH_MAX_OBJECTS, track_iou=t_iou, truth=truth_side)
@@ -203,6 +215,8 @@ def tracks_report(args, st):
     for name in st.names(("mask", "crf")):
         pred_tr, side = _tracked(st.labelled(name), t_iou, gap, motion)
         report[name] = {"pred": side}
+        if fill:
+            report[name]["fill"] = _fill_block(st.labelled(name).labels, pred_tr, motion, st.dev("truth"))
         if m_iou is not None:
             best = st.matched(name, m_iou).best
             counts = objects.switches(truth_prev, pred_tr.track, best, m_iou).cpu().numpy()
@@ -215,9 +229,11 @@ def tracks_report(args, st):
     p = report["mask"]["pred"]
     moved = f" motion<={search}" if search else ""
     if gap:
+        f = report["mask"].get("fill")
+        filled = f"; filled {f['objects']} objects, iou {fmt(f['iou_before'])} -> {fmt(f['iou'])}" if f else ""
         return report, (f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g} gap<={gap}{moved}: {p['tracks']} tracks over "
                         f"{p['objects']} objects ({p['bridged_links']} of {p['links']} links bridged), mean length {fmt(p['mean_length'])}, "
-                        f"longest {p['max_length']}; truth {truth_side['tracks']} tracks over {truth_side['objects']} objects")
+                        f"longest {p['max_length']}; truth {truth_side['tracks']} tracks over {truth_side['objects']} objects{filled}")
     return report, (f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g}{moved}: {p['tracks']} tracks over {p['objects']} "
                     f"objects, mean length {fmt(p['mean_length'])}, longest {p['max_length']}; truth {truth_side['tracks']} tracks over "
                     f"{truth_side['objects']} objects")

@@ -15,7 +15,8 @@ threshold, chains resolved on the device), ``switches`` counts identity switches
 ``--overlay-gap``) both bridge gaps of up to G missing frames (cgs_objects_track_gap), and ``fragments`` counts how often a truth
 track is split over several predicted tracks.  With ``motion`` (``--track-motion``, ``--overlay-motion``) the earlier frame's labels
 are carried along ``temporal.flow``'s backward block vectors before they are intersected (cgs_objects_track_mc); ``motion_report``
-is the block the reports gain."""
+is the block the reports gain.  ``fill`` (csrc/objects_fill.hip, ``--track-fill``) gives the frames that a bridged link jumps over
+the mask of the link's tail object, carried there along the same vectors; ``fill_report`` is the block the reports gain."""
 import re
 from collections import namedtuple
 
@@ -37,6 +38,7 @@ TRACK_MAX_GAP = _lib.OBJ_TRACK_MAX_GAP
 MOTION_SIDE, MOTION_BLOCKS, MOTION_MAX_SEARCH = 64, 64 // _lib.TEMPORAL_BLOCK, _lib.TEMPORAL_MAX_SEARCH      # cgs_objects_track_mc
 Tracks = namedtuple("Tracks", ["prev", "track", "n_tracks", "n_links", "n_objects", "longest", "table", "track_labels", "rgb",
                                "gap", "gap_links", "extra"], defaults=(None, None, None))
+Filled = namedtuple("Filled", ["labels", "track", "age", "table", "n_objects", "n_cells", "n_dropped", "n_vanished", "rgb"])
 
 
 def label(src, thresh=None, inclusive=False, connectivity=8, min_area=1, max_objects=64, want_labels=True, want_mask=False):
@@ -293,6 +295,82 @@ def track(labels, iou=0.5, max_objects=64, max_tracks=None, want_labels=False, w
     return Tracks(prev, trk, totals[0], totals[1], totals[2], totals[3], table, painted, rgb)
 
 
+def track_colours(track_numbers):
+    """``track``'s colour of every track number (any integer tensor): uint8 [..., 3], black for 0, else with hsh = (uint32) t *
+    2654435761 channel c is 64 + ((hsh >> 8 c) & 255) * 191 / 255 -- the formula of cgs_objects_track's rgb, in torch."""
+    t = track_numbers.to(torch.int64) & 0xFFFFFFFF
+    hsh = (t * 2654435761) & 0xFFFFFFFF
+    rgb = torch.stack([64 + ((hsh >> (8 * c)) & 255) * 191 // 255 for c in range(3)], dim=-1)
+    return torch.where((t != 0)[..., None], rgb, torch.zeros_like(rgb)).to(torch.uint8)
+
+
+def fill(labels, tracks, motion=None, max_objects=64, want_table=True, want_rgb=False):
+    """The masks that the bridged links of ``track`` jump over (cgs_objects_track_fill, whose header comment in include/cgs_hip.h is
+    the rule).  labels: the int32 device stack [n,h,w] that was tracked; tracks: ``track``'s result for it with max_gap G >= 1 and the
+    same max_objects (G is len(tracks.gap_links) - 1; a result without gap raises ValueError); motion: as in ``track``, and the field
+    the tracks were made with (None: none).  For every frame between the two ends of a link of gap >= 2 the link's tail object is
+    carried there along the backward vectors, and the cells it lands on that hold no object become a new object of that frame, numbered
+    behind the frame's largest label; a new object that would be numbered above max_objects is dropped.
+    Returns Filled(labels int32 [n,h,w]: the input where nothing was written, track int32 [n,K]: the track of every object, new ones
+    included, age int32 [n,K]: for a new object the number of frames its mask was carried over, else 0, table int32 [n,K,8] or None:
+    ``label``'s row of every new object, zero elsewhere, n_objects, n_cells, n_dropped, n_vanished: int32 scalars ON THE DEVICE (new
+    objects, their cells, candidates dropped for want of a label, candidates that reached no free cell), rgb uint8 [n,h,w,3] or None:
+    ``track``'s colour per track over the filled labels).  Nothing here synchronises.  No CPU path: raises CgsError without a GPU.
+    Limits: the mask comes from the tail alone, moved by whole cells, block by block; cells that hold an object are never written."""
+    if not isinstance(labels, torch.Tensor):
+        raise ValueError(f"labels must be a torch tensor, got {type(labels).__name__}")
+    if labels.dtype != torch.int32:
+        raise ValueError(f"labels must be torch.int32, got {labels.dtype}")
+    if labels.dim() not in (2, 3):
+        raise ValueError(f"labels must be [n,h,w] or [h,w], got {tuple(labels.shape)}")
+    if labels.dim() == 2:
+        labels = labels[None]
+    n, h, w = (int(s) for s in labels.shape)
+    if not 1 <= n <= TRACK_MAX_FRAMES or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError(f"labels {tuple(labels.shape)}: 1..{TRACK_MAX_FRAMES} frames of 1..{MAX_SIDE} x 1..{MAX_SIDE} pixels")
+    max_objects = _as_int(max_objects, "max_objects")
+    if not 1 <= max_objects <= MATCH_MAX_OBJECTS:
+        raise ValueError(f"max_objects must be 1..{MATCH_MAX_OBJECTS}, got {max_objects}")
+    if not isinstance(tracks, Tracks):
+        raise ValueError(f"tracks must be the result of objects.track, got {type(tracks).__name__}")
+    if tracks.gap is None or tracks.gap_links is None:
+        raise ValueError("tracks without gap: fill needs the result of objects.track with max_gap >= 1")
+    G = int(tracks.gap_links.shape[0]) - 1
+    if not 1 <= G <= TRACK_MAX_GAP:
+        raise ValueError(f"tracks made with max_gap {G}: fill needs 1..{TRACK_MAX_GAP} (without a bridged link there is nothing to fill)")
+    for name, t in (("prev", tracks.prev), ("gap", tracks.gap), ("track", tracks.track)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (n, max_objects):
+            raise ValueError(f"tracks.{name} must be int32 [{n},{max_objects}] (the labels' frames, max_objects), got "
+                             + (f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__))
+        if t.device != labels.device:
+            raise ValueError(f"tracks.{name} is on {t.device}, the labels on {labels.device}")
+    if motion is not None:
+        if (h, w) != (MOTION_SIDE, MOTION_SIDE):
+            raise ValueError(f"labels {tuple(labels.shape)}: motion needs frames of {MOTION_SIDE} x {MOTION_SIDE} (8 x 8 blocks of 8 cells)")
+        motion = _motion_field(motion, n, labels.device)
+    if not torch.cuda.is_available() or not labels.is_cuda:
+        raise _lib.CgsError("objects.fill runs on the GPU (cgs_objects_track_fill); " + ("no GPU is visible" if not torch.cuda.is_available()
+                            else f"the tensor is on {labels.device}") + " and there is no CPU fallback")
+    labels = labels.contiguous()
+    prev, gap, trk = tracks.prev.contiguous(), tracks.gap.contiguous(), tracks.track.contiguous()
+    dev, K = labels.device, max_objects
+    with torch.cuda.device(dev):
+        out = torch.empty((n, h, w), dtype=torch.int32, device=dev)
+        out_track = torch.empty((n, K), dtype=torch.int32, device=dev)
+        age = torch.empty((n, K), dtype=torch.int32, device=dev)
+        table = torch.empty((n, K, len(FIELDS)), dtype=torch.int32, device=dev) if want_table else None
+        totals = torch.empty(4, dtype=torch.int32, device=dev)
+        _lib.call("cgs_objects_track_fill", labels.data_ptr(), motion.data_ptr() if motion is not None and n > 1 else None, n, h, w, K, G,
+                  prev.data_ptr(), gap.data_ptr(), trk.data_ptr(), out.data_ptr(), out_track.data_ptr(), age.data_ptr(),
+                  table.data_ptr() if want_table else None, totals.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        rgb = None
+        if want_rgb:
+            inside = (out >= 1) & (out <= K)
+            number = torch.gather(out_track, 1, (out.reshape(n, -1).to(torch.int64) - 1).clamp(0, K - 1)).reshape(n, h, w)
+            rgb = track_colours(torch.where(inside, number, torch.zeros_like(number)))
+    return Filled(out, out_track, age, table, totals[0], totals[1], totals[2], totals[3], rgb)
+
+
 def stream_remap(local, carried_local, carried_global, c0, n_tracks):
     """The track numbers of a chunk tracked behind one carried frame, as numbers of the whole stream.  local: int [m,K], rows 1.. of
     ``track(cat(carry, chunk)).track``; carried_local: int [K], its row 0 (every object of the carried frame heads a track there, so
@@ -475,6 +553,13 @@ def motion_report(bwd, search):
     return {"search": search, "block": _lib.TEMPORAL_BLOCK,
             "mean_cells_per_frame": float(np.sqrt((v ** 2).sum(axis=1)).mean()) if len(v) else None,
             "saturated": float((np.abs(v).max(axis=1) >= search).mean()) if len(v) else None}
+
+
+def fill_report(filled):
+    """The "track_fill" block of tracks.json and the counts of eval_tracks.json's "fill" from ``fill``'s result: {"objects", "cells",
+    "dropped", "vanished"}.  One transfer of the four scalars."""
+    counts = torch.stack([filled.n_objects, filled.n_cells, filled.n_dropped, filled.n_vanished]).tolist()
+    return dict(zip(("objects", "cells", "dropped", "vanished"), (int(v) for v in counts)))
 
 
 def parse_track_iou(s):

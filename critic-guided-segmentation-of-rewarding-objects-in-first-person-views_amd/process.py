@@ -118,7 +118,8 @@ def objects_and_tracks(args, M, crf_mask, stems, device, rank, low=None, cleaned
         search = int(getattr(args, "track_motion", 0) or 0)
         if search and low is None:
             raise ValueError("--track-motion needs the 64 x 64 frames of the masks")
-        _tracks(args, res, head, stems, rank, low=torch.as_tensor(low).to(device) if search else None, search=search)
+        _tracks(args, res, head, stems, rank, low=torch.as_tensor(low).to(device) if search else None, search=search,
+                fill=bool(getattr(args, "track_fill", False)))
 
 
 def video_reports(args, M, stem, device, rank, bwd=None):
@@ -158,7 +159,7 @@ def _objects(args, res, head, stems, width, rank, png=True, name="objects.json")
         Image.fromarray(np.repeat((mask[i] * np.uint8(255))[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-objects-mask.png")
 
 
-def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None, gap=None, low=None, bwd=None, search=0):
+def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None, gap=None, low=None, bwd=None, search=0, fill=False):
     """The objects objects.json describes followed through the frames in natural order of their names on the GPU (objects.track);
     labels above 64 are untracked.  Rank 0 writes {R}/tracks.json and per frame {R}/{stem}-tracks-mask.png, a colour per track
     (png=False: the report alone, as {R}/{name}; iou, gap: the link threshold and the gap when they are not --track-iou's and
@@ -166,7 +167,11 @@ def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None
     keys and per object its "gap"; "last" is then the track's last frame, missed frames counted.  With search S > 0 (--track-motion,
     --overlay-motion) the labels are carried along the backward block vectors (objects.track's motion): temporal.flow of low, uint8
     [n,64,64,3] in the order of stems, taken in the tracked order, or bwd where the caller has the field; the report gains
-    "track_motion" (objects.motion_report)."""
+    "track_motion" (objects.motion_report).  fill (--track-fill, with a gap): the frames a bridged link jumps over get the tail
+    object's carried mask (objects.fill).  {stem}-tracks-mask.png is then painted from the filled labels, {stem}-filled-mask.png holds
+    the filled labels > 0 as 0 / 255 grey RGB, and the report gains "track_fill" (objects.fill_report), per frame an entry {"label",
+    "track", "filled": the frames the mask was carried over, "area"} for every new object, and per track "filled", the number of its
+    new objects, counted on the device."""
     from PIL import Image
     K, iou = MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou) if iou is None else iou
     gap = int(getattr(args, "track_gap", 0) or 0) if gap is None else gap
@@ -175,7 +180,13 @@ def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None
     if search and bwd is None:
         from . import temporal
         bwd = temporal.flow(low[pick], search)[1]
-    tr = objects.track(res.labels[pick], iou=iou, max_objects=K, want_rgb=png, max_gap=gap, motion=bwd if search else None)
+    fill = bool(fill and gap)
+    stack = res.labels[pick]
+    tr = objects.track(stack, iou=iou, max_objects=K, want_rgb=png and not fill, max_gap=gap, motion=bwd if search else None)
+    if fill:
+        fl = objects.fill(stack, tr, motion=bwd if search else None, max_objects=K, want_rgb=png)
+        new = fl.age > 0
+        per_track = torch.bincount(fl.track[new].to(torch.int64).clamp(min=0), minlength=stack.shape[0] * K + 1)
     if rank != 0:
         return
     totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
@@ -188,17 +199,29 @@ def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None
     gaps = tr.gap.cpu().numpy() if gap else None
     last = (lambda r: r["last_frame"]) if gap else (lambda r: r["first_frame"] + r["length"] - 1)
     report = {**head, "max_objects": K, "track_iou": iou, **({"track_gap": gap} if gap else {}),
-              **({"track_motion": objects.motion_report(bwd, search)} if search else {}), "summary": side, "order": names,
+              **({"track_motion": objects.motion_report(bwd, search)} if search else {}),
+              **({"track_fill": objects.fill_report(fl)} if fill else {}), "summary": side, "order": names,
               "frames": {stem: [{"label": int(l) + 1, "track": int(trk[j, l]), "prev": int(prev[j, l]),
                                  **({"gap": int(gaps[j, l])} if gap else {})} for l in np.flatnonzero(trk[j])]
                          for j, stem in enumerate(names)},
               "tracks": [{"track": r["track"], "first": names[r["first_frame"]], "last": names[last(r)],
                           "length": r["length"], "area_sum": r["area_sum"], "area_min": r["area_min"], "area_max": r["area_max"],
                           "link_iou": r["link_iou"], **({"bridges": r["bridges"], "missed": r["missed"]} if gap else {})} for r in rows]}
+    if fill:
+        age, ftrk, area, per_track = fl.age.cpu().numpy(), fl.track.cpu().numpy(), fl.table[:, :, 0].cpu().numpy(), per_track.cpu().numpy()
+        for j, stem in enumerate(names):
+            report["frames"][stem] += [{"label": int(l) + 1, "track": int(ftrk[j, l]), "filled": int(age[j, l]), "area": int(area[j, l])}
+                                       for l in np.flatnonzero(age[j])]
+        for row in report["tracks"]:
+            row["filled"] = int(per_track[row["track"]])
     out_dir = args.mask_output_imgs
     write_json(f"{out_dir}/{name}", report)
     if not png:
         return
-    rgb = tr.rgb.cpu().numpy()
+    rgb = (fl.rgb if fill else tr.rgb).cpu().numpy()
     for j, stem in enumerate(names):
         Image.fromarray(rgb[j]).save(f"{out_dir}/{stem}-tracks-mask.png")
+    if fill:
+        on = (fl.labels > 0).cpu().numpy()
+        for j, stem in enumerate(names):
+            Image.fromarray(np.repeat((on[j] * np.uint8(255))[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-filled-mask.png")

@@ -1005,6 +1005,42 @@ int cgs_objects_track_mc(const int32_t* labels, const int8_t* bwd, int32_t n, in
                          int32_t* totals, int32_t* gap_links, int32_t* tracks, int32_t* tracks_extra, int32_t* track_labels, uint8_t* rgb,
                          void* scratch, int64_t scratch_bytes, cgs_stream_t stream);
 
+/* cgs_objects_track_fill (csrc/objects_fill.hip): the masks that the bridged links of cgs_objects_track_gap / cgs_objects_track_mc jump
+ * over.  For every frame m between the two ends of a link of gap >= 2 the link's tail object is carried from its frame to m along the
+ * backward vectors the link was decided on, and where it lands on cells without an object it becomes a new object of frame m.  This
+ * comment is the specification.
+ *   labels     int32 [n][h][w], the stack that was tracked.  bwd int8 [n - 1][8][8][2], the field it was tracked along, or NULL: the
+ *              all-zero field (then h, w <= 64; with a field h == w == 64).  K = max_objects <= 64, G = max_gap in 1..8.
+ *   prev, gap, track  int32 [n][K] as cgs_objects_track_gap / _mc wrote them for these labels with the same K and a max_gap <= G.  Any
+ *              int32 content is allowed: an entry outside the ranges below names nothing.
+ *   rule, for frame m and j = 1 .. min(G, m), a = m - j:
+ *     spanning   S(m, j) = the labels p in 1..K for which some f in m + 1 .. min(n - 1, a + G + 1) and l in 1..K have
+ *                gap[f][l-1] == f - a and prev[f][l-1] == p: the tails in frame a of links that jump over m.
+ *     carried    W_{a->m} is cgs_objects_track_mc's carried map with (a, m) for (a, f): labels outside 1..K read as 0, 0 outside the
+ *                grid; with bwd NULL it is frame a's labels (those outside 1..K read as 0).  The walk for j + 1 extends the walk for j.
+ *     claim      a cell q with labels[m][q] <= 0 is claimed by the smallest j with W_{m-j->m}[q] in S(m, j), for the candidate (j, p), p
+ *                that label.  A cell with a positive label is never touched (labels above K block too).  Pure selection per cell.
+ *     numbering  base = the largest value of labels[m], at least 0.  The candidates that claimed a cell, ordered by (j, p) ascending,
+ *                get the labels base + 1, base + 2, ...; those above K are dropped and their cells stay as they were.
+ *   out_labels int32 [n][h][w]: the input value where nothing was written, else the new label.  Must not be `labels`.
+ *   out_track  int32 [n][K]: row l-1 is track[m][l-1] when l in 1..K holds a cell of labels[m], track[a][p-1] for a new object, else 0
+ *   age        int32 [n][K]: j for a new label, 0 everywhere else
+ *   table      int32 [n][K][CGS_OBJ_FIELDS] or NULL: cgs_objects_label's row (area, x0, y0, x1, y1, sum_x, sum_y, first) of every new
+ *              object; all other rows are zero
+ *   totals     int32 [4], zeroed by the entry on the stream: new objects, their cells, dropped candidates, vanished candidates (in some
+ *              S(m, j) but without a claimed cell: carried out of the grid or fully covered)
+ * One launch, one workgroup per frame; a frame that no link jumps over is copied.  The frames m - 1 .. m - G are staged as bytes in
+ * LDS; no scratch.  All integer; the only global atomics are the integer adds of totals: bit-reproducible.  The inputs are not written.
+ * No read or write is out of range for any int32 content of labels, prev, gap, track or any int8 content of bwd.  Runs on `stream`
+ * without synchronising, allocates nothing, can be captured in a graph.  Limits of the rule: the mask comes from the tail alone (the
+ * head's mask and the forward field are not used), motion is whole-cell block motion, real pixels always win, a frame has K labels.
+ * labels, prev, gap, track, out_labels, out_track, age, totals not NULL, n, h, w, max_objects >= 1, max_gap in 1..8, int32 pointers
+ * 4-byte aligned, out_labels != labels, else CGS_ERR_BADARG (nothing is launched); then the sizes above, max_objects <= 64 and n <=
+ * CGS_OBJ_TRACK_MAX_FRAMES, else CGS_ERR_UNSUPPORTED.                                                                                  */
+int cgs_objects_track_fill(const int32_t* labels, const int8_t* bwd, int32_t n, int32_t h, int32_t w, int32_t max_objects,
+                           int32_t max_gap, const int32_t* prev, const int32_t* gap, const int32_t* track, int32_t* out_labels,
+                           int32_t* out_track, int32_t* age, int32_t* table, int32_t* totals, cgs_stream_t stream);
+
 /* ---- the saliency baseline over a threshold grid (csrc/saliency.hip; Handler._saliency_post, main.py:976-1003; this build's own
  * -eval -salience --salience-grid) -----------------------------------------------------------------------------------------------------
  * The baseline's whole post-processing for T thresholds at once, each threshold with its own normaliser as the host form has it.  A
