@@ -227,6 +227,7 @@ SIGNATURES = {
     "cgs_objects_track_mc_scratch_bytes": (i64, [i32, i32, i32]),
     "cgs_objects_track_mc": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "cgs_objects_track_fill": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "cgs_objects_track_fill_window": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
     "cgs_saliency_sweep": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "cgs_boundary_score": (i32, [vp, i32, f32, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
     "cgs_fit_down_u8": (i32, [vp, i32, i32, i32, vp, vp]),
@@ -234,6 +235,7 @@ SIGNATURES = {
     "cgs_temporal_smooth": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp]),
     "cgs_overlay_compose": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "cgs_overlay_compose_tracks": (i32, [vp] * 7 + [i32] * 12 + [vp, vp]),
+    "cgs_overlay_compose_tracks_carried": (i32, [vp] * 8 + [i32] * 12 + [vp, vp]),
     "cgs_temporal_flow": (i32, [vp, i32, i32, vp, vp, vp]),
     "cgs_temporal_smooth_mc": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
     "cgs_build_arch": (C.c_char_p, []),

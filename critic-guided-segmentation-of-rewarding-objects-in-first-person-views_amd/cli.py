@@ -73,7 +73,9 @@ def build_parser():
     # --overlay-boxes B pixels thick (0: none), and its track number (overlay.compose_tracks); leaves {R}/{stem}-objects.json and
     # {R}/{stem}-tracks.json.  A and B default to 1.  --overlay-gap G (0..8, default 0) is --track-gap for this stream: an object that
     # has no mask for up to G frames comes back under its number and colour.  --overlay-motion S (0..4, default 0) is --track-motion for
-    # this stream: the labels are carried along block vectors of the shrunk frames before they are compared
+    # this stream: the labels are carried along block vectors of the shrunk frames before they are compared.  --overlay-fill (with
+    # --overlay-gap G >= 1) is --track-fill for this stream: the frames a bridged link jumps over get the tail's mask, drawn hatched
+    # (objects.FillStream, overlay.compose_tracks(age=)); the overlay then runs G frames behind the masks
     p.add_argument("--source-video", type=str, default="")
     p.add_argument("--overlay-video", type=str, default="")
     p.add_argument("--smooth", type=int, default=None)
@@ -88,6 +90,7 @@ def build_parser():
     p.add_argument("--overlay-boxes", type=int, default=None)
     p.add_argument("--overlay-gap", type=str, default=None)
     p.add_argument("--overlay-motion", type=str, default=None)
+    p.add_argument("--overlay-fill", action="store_true")
     # (this build's own flags) --clean SPEC with -process or -eval, --overlay-clean SPEC with --source-video: the thresholded mask (with
     # -crf the CRF mask) cleaned on the GPU before anything reads it (clean.py): "hyst=0.8;open=1;close=2;fill=16;shape=cross;conn=4" --
     # hysteresis with the strong threshold, opening and closing radii 0..4, holes of up to so many pixels filled, square | cross, 4 | 8.
@@ -226,7 +229,7 @@ def check_objects_flags(args):
             raise ValueError("--track-fill fills the frames that a bridged link jumps over: give --track-gap G with G in 1..8")
         if args.source_video:
             raise ValueError("--track-fill with --source-video: outside this build (the stream would have to look --overlay-gap frames "
-                             "ahead before it draws a frame)")
+                             "ahead before it draws a frame); the video path's own flag is --overlay-fill, which does")
     if not args.objects:
         if given:
             raise ValueError(f"{' / '.join(given)} belong to -objects: give -objects")
@@ -267,7 +270,7 @@ def check_video_flags(args):
     """--source-video / --overlay-video and the --smooth* / --overlay-* options: combinations that could not run and values out of range
     are refused here, before any GPU work; the defaults (--smooth 0, --smooth-range 16, --smooth-motion 0, --overlay-layout overlay,
     --overlay-color 0,255,0, --overlay-alpha 0.5, --overlay-outline 1; with --overlay-tracks T also --overlay-min-area 1, --overlay-boxes 1, --overlay-gap 0, --overlay-motion 0) are filled
-    in, --overlay-color becomes (r, g, b), args.overlay_alpha256 is round(256 alpha), --overlay-tracks becomes a float (None without the
+    in (--overlay-fill needs --source-video, --overlay-tracks and an --overlay-gap of at least 1), --overlay-color becomes (r, g, b), args.overlay_alpha256 is round(256 alpha), --overlay-tracks becomes a float (None without the
     flag), and -fit is switched on: a video goes through the -fit machinery.  The frame size is checked after the probe
     (check_video_size)."""
     given = [f for f, v in (("--overlay-video", args.overlay_video or None), ("--smooth", args.smooth), ("--smooth-range", args.smooth_range),
@@ -276,7 +279,8 @@ def check_video_flags(args):
                             ("--overlay-alpha", args.overlay_alpha), ("--overlay-outline", args.overlay_outline),
                             ("--overlay-tracks", args.overlay_tracks), ("--overlay-min-area", args.overlay_min_area),
                             ("--overlay-boxes", args.overlay_boxes), ("--overlay-gap", args.overlay_gap),
-                            ("--overlay-motion", args.overlay_motion)) if v is not None]
+                            ("--overlay-motion", args.overlay_motion),
+                            ("--overlay-fill", True if getattr(args, "overlay_fill", False) else None)) if v is not None]
     if not args.source_video:
         if given:
             raise ValueError(f"{' / '.join(given)} belong to --source-video: give --source-video")
@@ -313,7 +317,8 @@ def check_video_flags(args):
                                  overlay.OUTLINE if args.overlay_outline is None else args.overlay_outline)
     if args.overlay_tracks is None:
         extra = [f for f, v in (("--overlay-min-area", args.overlay_min_area), ("--overlay-boxes", args.overlay_boxes),
-                                ("--overlay-gap", args.overlay_gap), ("--overlay-motion", args.overlay_motion)) if v is not None]
+                                ("--overlay-gap", args.overlay_gap), ("--overlay-motion", args.overlay_motion),
+                                ("--overlay-fill", True if getattr(args, "overlay_fill", False) else None)) if v is not None]
         if extra:
             raise ValueError(f"{' / '.join(extra)} belong to --overlay-tracks: give --overlay-tracks T")
     else:
@@ -332,6 +337,8 @@ def check_video_flags(args):
         args.overlay_gap = 0 if args.overlay_gap is None else parse_track_gap(args.overlay_gap, "--overlay-gap")
         from .objects import parse_track_motion
         args.overlay_motion = 0 if args.overlay_motion is None else parse_track_motion(args.overlay_motion, "--overlay-motion")
+        if getattr(args, "overlay_fill", False) and not args.overlay_gap:
+            raise ValueError("--overlay-fill fills the frames that a bridged link jumps over: give --overlay-gap G with G in 1..8")
     args.fit = True
 
 

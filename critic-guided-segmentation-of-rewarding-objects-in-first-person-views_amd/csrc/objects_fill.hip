@@ -15,6 +15,8 @@
 //   rank    the candidates (j, p) that claimed a cell are a 512-bit map (one LDS OR per run of equal claims in a row); a candidate's
 //           rank in (j, p) order is a popcount below its bit, its label base + rank + 1, dropped above K.
 //   table   cgs_objects_label's row of every new object with LDS integer atomics, one set per run of a row.
+// cgs_objects_track_fill_window gives a workgroup to the frames f0 <= m < f1 only and writes their outputs at m - f0: what a stream
+// needs, whose window holds halo frames on both sides (objects.FillStream).  The reads are those of the whole stack's frame m.
 // Every read is bounded for any content of the inputs: an entry of gap / prev is used only inside its range, a staged label is a
 // byte in 0..K, the table index of a step comes from a clamped cell, the staged cell is checked, |m_j| <= 8 * 128.
 #include "pixel_common.h"
@@ -48,7 +50,7 @@ __global__ void __launch_bounds__(OF_THREADS)
 fill_kernel(const int32_t* __restrict__ labels, const int8_t* __restrict__ bwd, int n, int h, int w, int K, int G,
             const int32_t* __restrict__ prev, const int32_t* __restrict__ gap, const int32_t* __restrict__ track,
             int32_t* __restrict__ out_labels, int32_t* __restrict__ out_track, int32_t* __restrict__ age, int32_t* __restrict__ table,
-            int32_t* __restrict__ totals) {
+            int32_t* __restrict__ totals, int f0) {
     __shared__ unsigned long long s_S[OF_MAX_GAP];                       // [j - 1]: the tails in frame m - j of links that jump over m
     __shared__ unsigned long long s_C[OF_MAX_GAP];                       // [j - 1]: those of them that claimed a cell
     __shared__ unsigned long long s_pres[OF_WAVES];
@@ -56,9 +58,10 @@ fill_kernel(const int32_t* __restrict__ labels, const int8_t* __restrict__ bwd, 
     __shared__ int s_tab[OF_MAX_K * CGS_OBJ_FIELDS];
     __shared__ uint8_t s_L[MC ? OF_MAX_GAP : 1][OF_SIDE * OF_SIDE];      // MC: [j - 1] = frame m - j, masked by S(m, j)
     __shared__ uint16_t s_m[MC ? OF_MAX_GAP : 1][OF_BLOCKS * OF_BLOCKS];  // MC: [s] = bwd[m - s - 1], dy | dx << 8
-    const int m = blockIdx.x, tid = threadIdx.x, x = tid & (CGS_WAVE - 1), wave = tid / CGS_WAVE;
+    const int m = f0 + (int)blockIdx.x, tid = threadIdx.x, x = tid & (CGS_WAVE - 1), wave = tid / CGS_WAVE;
     const bool live = x < w;
     const int64_t hw = (int64_t)h * w, fm = (int64_t)m * hw, rowK = (int64_t)m * K;
+    const int64_t fo = (int64_t)blockIdx.x * hw, rowO = (int64_t)blockIdx.x * K;    // the outputs hold the frames f0 .. only
 
     if (tid < OF_MAX_GAP) s_S[tid] = s_C[tid] = 0ull;
     for (int i = tid; i < OF_MAX_K * CGS_OBJ_FIELDS; i += OF_THREADS) {
@@ -104,14 +107,14 @@ fill_kernel(const int32_t* __restrict__ labels, const int8_t* __restrict__ bwd, 
 #pragma unroll
         for (int r = 0; r < OF_ROWS; ++r) {
             const int y = wave + OF_WAVES * r;
-            if (live && y < h) out_labels[fm + (int64_t)y * w + x] = own[r];
+            if (live && y < h) out_labels[fo + (int64_t)y * w + x] = own[r];
         }
         if (tid < K) {
-            out_track[rowK + tid] = ((present >> tid) & 1ull) ? track[rowK + tid] : 0;
-            age[rowK + tid] = 0;
+            out_track[rowO + tid] = ((present >> tid) & 1ull) ? track[rowK + tid] : 0;
+            age[rowO + tid] = 0;
         }
         if (table)
-            for (int i = tid; i < K * CGS_OBJ_FIELDS; i += OF_THREADS) table[rowK * CGS_OBJ_FIELDS + i] = 0;
+            for (int i = tid; i < K * CGS_OBJ_FIELDS; i += OF_THREADS) table[rowO * CGS_OBJ_FIELDS + i] = 0;
         return;
     }
 
@@ -203,7 +206,7 @@ fill_kernel(const int32_t* __restrict__ labels, const int8_t* __restrict__ bwd, 
             rank += __popcll(s_C[j - 1] & ((1ull << (p - 1)) - 1ull));
             if (rank < room) nl = base + rank + 1;
         }
-        if (live && y < h) out_labels[fm + (int64_t)y * w + x] = nl ? nl : own[r];
+        if (live && y < h) out_labels[fo + (int64_t)y * w + x] = nl ? nl : own[r];
         const int left = __shfl_up(nl, 1, CGS_WAVE);
         const unsigned long long starts = __ballot(x == 0 || nl != left);
         const bool last = x == CGS_WAVE - 1 || ((starts >> (x + 1)) & 1ull);
@@ -223,10 +226,10 @@ fill_kernel(const int32_t* __restrict__ labels, const int8_t* __restrict__ bwd, 
     __syncthreads();
 
     if (table)
-        for (int i = tid; i < K * CGS_OBJ_FIELDS; i += OF_THREADS) table[rowK * CGS_OBJ_FIELDS + i] = s_tab[i & ~7] > 0 ? s_tab[i] : 0;
+        for (int i = tid; i < K * CGS_OBJ_FIELDS; i += OF_THREADS) table[rowO * CGS_OBJ_FIELDS + i] = s_tab[i & ~7] > 0 ? s_tab[i] : 0;
     if (tid < K && !(tid >= base && tid - base < made)) {                // label tid + 1 is not a new one
-        out_track[rowK + tid] = ((present >> tid) & 1ull) ? track[rowK + tid] : 0;
-        age[rowK + tid] = 0;
+        out_track[rowO + tid] = ((present >> tid) & 1ull) ? track[rowK + tid] : 0;
+        age[rowO + tid] = 0;
     }
     for (int i = tid; i < J * OF_MAX_K; i += OF_THREADS) {               // candidate (j, p) = (i / 64 + 1, i % 64 + 1)
         const int j = i >> 6, b = i & 63;
@@ -235,8 +238,8 @@ fill_kernel(const int32_t* __restrict__ labels, const int8_t* __restrict__ bwd, 
             int rank = __popcll(C & ((1ull << b) - 1ull));
             for (int k = 0; k < j; ++k) rank += __popcll(s_C[k]);
             if (rank < room) {
-                age[rowK + base + rank] = j + 1;
-                out_track[rowK + base + rank] = track[(int64_t)(m - j - 1) * K + b];
+                age[rowO + base + rank] = j + 1;
+                out_track[rowO + base + rank] = track[(int64_t)(m - j - 1) * K + b];
             }
         }
     }
@@ -255,28 +258,43 @@ fill_kernel(const int32_t* __restrict__ labels, const int8_t* __restrict__ bwd, 
     }
 }
 
-}  // namespace
-
-extern "C" int cgs_objects_track_fill(const int32_t* labels, const int8_t* bwd, int32_t n, int32_t h, int32_t w, int32_t max_objects,
-                                      int32_t max_gap, const int32_t* prev, const int32_t* gap, const int32_t* track,
-                                      int32_t* out_labels, int32_t* out_track, int32_t* age, int32_t* table, int32_t* totals,
-                                      cgs_stream_t stream_) {
+// Both entries: the frames f0 <= m < f1 of the window of n frames, one workgroup each; the outputs hold those frames only.
+int fill_launch(const int32_t* labels, const int8_t* bwd, int32_t n, int32_t h, int32_t w, int32_t max_objects, int32_t max_gap,
+                const int32_t* prev, const int32_t* gap, const int32_t* track, int32_t* out_labels, int32_t* out_track, int32_t* age,
+                int32_t* table, int32_t* totals, int32_t f0, int32_t f1, cgs_stream_t stream_) {
     if (!labels || !prev || !gap || !track || !out_labels || !out_track || !age || !totals || n < 1 || h < 1 || w < 1 || max_objects < 1 ||
         max_gap < 1 || max_gap > OF_MAX_GAP || ((uintptr_t)labels & 3u) || ((uintptr_t)prev & 3u) || ((uintptr_t)gap & 3u) ||
         ((uintptr_t)track & 3u) || ((uintptr_t)out_labels & 3u) || ((uintptr_t)out_track & 3u) || ((uintptr_t)age & 3u) ||
-        ((uintptr_t)table & 3u) || ((uintptr_t)totals & 3u) || out_labels == labels)
+        ((uintptr_t)table & 3u) || ((uintptr_t)totals & 3u) || out_labels == labels || f0 < 0 || f0 > f1 || f1 > n)
         return CGS_ERR_BADARG;
     if (bwd ? (h != OF_SIDE || w != OF_SIDE) : (h > OF_SIDE || w > OF_SIDE)) return CGS_ERR_UNSUPPORTED;
     if (max_objects > OF_MAX_K || n > CGS_OBJ_TRACK_MAX_FRAMES) return CGS_ERR_UNSUPPORTED;
     hipStream_t stream = (hipStream_t)stream_;
     const hipError_t e = hipMemsetAsync(totals, 0, 4 * sizeof(int32_t), stream);
     if (e != hipSuccess) return (int)e;
+    if (f0 == f1) return CGS_OK;
     if (bwd)
-        hipLaunchKernelGGL(fill_kernel<true>, dim3((unsigned)n), dim3(OF_THREADS), 0, stream, labels, bwd, (int)n, (int)h, (int)w,
-                           (int)max_objects, (int)max_gap, prev, gap, track, out_labels, out_track, age, table, totals);
+        hipLaunchKernelGGL(fill_kernel<true>, dim3((unsigned)(f1 - f0)), dim3(OF_THREADS), 0, stream, labels, bwd, (int)n, (int)h, (int)w,
+                           (int)max_objects, (int)max_gap, prev, gap, track, out_labels, out_track, age, table, totals, (int)f0);
     else
-        hipLaunchKernelGGL(fill_kernel<false>, dim3((unsigned)n), dim3(OF_THREADS), 0, stream, labels, bwd, (int)n, (int)h, (int)w,
-                           (int)max_objects, (int)max_gap, prev, gap, track, out_labels, out_track, age, table, totals);
+        hipLaunchKernelGGL(fill_kernel<false>, dim3((unsigned)(f1 - f0)), dim3(OF_THREADS), 0, stream, labels, bwd, (int)n, (int)h, (int)w,
+                           (int)max_objects, (int)max_gap, prev, gap, track, out_labels, out_track, age, table, totals, (int)f0);
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;
+}
+
+}  // namespace
+
+extern "C" int cgs_objects_track_fill(const int32_t* labels, const int8_t* bwd, int32_t n, int32_t h, int32_t w, int32_t max_objects,
+                                      int32_t max_gap, const int32_t* prev, const int32_t* gap, const int32_t* track,
+                                      int32_t* out_labels, int32_t* out_track, int32_t* age, int32_t* table, int32_t* totals,
+                                      cgs_stream_t stream_) {
+    return fill_launch(labels, bwd, n, h, w, max_objects, max_gap, prev, gap, track, out_labels, out_track, age, table, totals, 0, n, stream_);
+}
+
+extern "C" int cgs_objects_track_fill_window(const int32_t* labels, const int8_t* bwd, int32_t n, int32_t h, int32_t w, int32_t max_objects,
+                                             int32_t max_gap, const int32_t* prev, const int32_t* gap, const int32_t* track, int32_t f0,
+                                             int32_t f1, int32_t* out_labels, int32_t* out_track, int32_t* age, int32_t* table,
+                                             int32_t* totals, cgs_stream_t stream_) {
+    return fill_launch(labels, bwd, n, h, w, max_objects, max_gap, prev, gap, track, out_labels, out_track, age, table, totals, f0, f1, stream_);
 }

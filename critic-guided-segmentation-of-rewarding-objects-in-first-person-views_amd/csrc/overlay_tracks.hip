@@ -96,8 +96,16 @@ __device__ __forceinline__ uint32_t ot_search(const OtShared& sh, int y, int x, 
     return pick;
 }
 
+// cgs_overlay_compose_tracks_carried (CARRIED): an object with age > 0 has bit 24 (OT_CARRIED) set in its sh.colour and in its box's colour
+// -- above the three channels, so no byte that is written sees it.  Off the stripe ((x + y) / (2 s) odd) such an object's pixel takes no
+// tint and its box has no border; plate, digits and outline are as without the flag.  Everything the flag adds stands under
+// `if constexpr (CARRIED)`: the kernel of cgs_overlay_compose_tracks is the one it was.
+constexpr uint32_t OT_CARRIED = 1u << 24;
+
 // Plate and border of the boxes in `hits` at pixel (y, x): true and the colour when one of them covers the pixel.
-__device__ __forceinline__ bool ot_decorate(const OtShared& sh, unsigned long long hits, int y, int x, int s, int thick, uint32_t* colour) {
+template <bool CARRIED>
+__device__ __forceinline__ bool ot_decorate(const OtShared& sh, unsigned long long hits, int y, int x, int s, int thick, bool stripe,
+                                            uint32_t* colour) {
     unsigned long long m = hits;
 #pragma unroll 1
     while (m) {
@@ -121,6 +129,8 @@ __device__ __forceinline__ bool ot_decorate(const OtShared& sh, unsigned long lo
         const OtBox& b = sh.box[__builtin_ctzll(m)];
         m &= m - 1;
         if (x < b.x0 || x > b.x1 || y < b.y0 || y > b.y1) continue;
+        if constexpr (CARRIED)
+            if ((b.colour & OT_CARRIED) && !stripe) continue;             // a carried object's border is hatched
         if (x - b.x0 < thick || b.x1 - x < thick || y - b.y0 < thick || b.y1 - y < thick) {
             *colour = b.colour;
             return true;
@@ -129,12 +139,12 @@ __device__ __forceinline__ bool ot_decorate(const OtShared& sh, unsigned long lo
     return false;
 }
 
-template <int PX, bool NT>
+template <int PX, bool NT, bool CARRIED>
 __global__ void __launch_bounds__(OV_THREADS)
 overlay_tracks_kernel(const uint8_t* __restrict__ guide, const uint8_t* __restrict__ grey, const uint8_t* __restrict__ hard,
                       const int32_t* __restrict__ labels, const int32_t* __restrict__ ids, const int32_t* __restrict__ table,
                       const uint8_t* __restrict__ font, int H, int W, int K, uint32_t tint, uint32_t alpha256, int thick, int boxes,
-                      int panels, uint8_t* __restrict__ out) {
+                      int panels, uint8_t* __restrict__ out, const int32_t* __restrict__ age) {
     __shared__ OtShared sh;
     const int t = threadIdx.x, f = blockIdx.y, y0 = (int)blockIdx.x * OV_BAND;
     const int rows = min(OV_BAND, H - y0);
@@ -163,6 +173,8 @@ overlay_tracks_kernel(const uint8_t* __restrict__ guide, const uint8_t* __restri
             if (t >= 1 && t <= K) {
                 const int32_t id = ids[(int64_t)f * K + t - 1];
                 if (id > 0) c = ot_track_colour((uint32_t)id);
+                if constexpr (CARRIED)
+                    if (age[(int64_t)f * K + t - 1] > 0) c |= OT_CARRIED;
             }
             sh.colour[t] = c;
         }
@@ -192,6 +204,8 @@ overlay_tracks_kernel(const uint8_t* __restrict__ guide, const uint8_t* __restri
                     b.xe = (int16_t)max((int)b.x1, b.x0 + b.pw - 1);
                     b.ye = (int16_t)max((int)b.y1, b.y0 + 9 * s - 1);
                     b.colour = ot_track_colour((uint32_t)id);
+                    if constexpr (CARRIED)
+                        if (age[(int64_t)f * K + t] > 0) b.colour |= OT_CARRIED;
                     keep = b.ye >= y0 && b.y0 <= y0 + rows - 1;
                 }
             }
@@ -246,7 +260,9 @@ overlay_tracks_kernel(const uint8_t* __restrict__ guide, const uint8_t* __restri
         // the overlay colour of pixel x + i: frame (r, g, b), grey byte g, outline bit o
         auto pixel = [&](int i, uint32_t r, uint32_t gg, uint32_t b, uint32_t g, bool o) -> uint32_t {
             uint32_t c;
-            if (hits && ot_decorate(sh, hits, y, x + i, s, boxes, &c)) return c;
+            bool stripe = true;
+            if constexpr (CARRIED) stripe = (((uint32_t)(x + i + y) / (uint32_t)(2 * s)) & 1u) == 0u;
+            if (hits && ot_decorate<CARRIED>(sh, hits, y, x + i, s, boxes, stripe, &c)) return c;
             c = tint;
             if (g != 0u || o) {                                           // elsewhere the colour does not show
                 const int cx = ot_home(x + i, inv_w);
@@ -255,7 +271,11 @@ overlay_tracks_kernel(const uint8_t* __restrict__ guide, const uint8_t* __restri
                 if (l < OT_NEAR) c = sh.colour[l];
             }
             if (o) return c;
-            const uint32_t q = alpha256 * g;
+            uint32_t q = alpha256 * g;
+            if constexpr (CARRIED) {
+                if ((c & OT_CARRIED) && !stripe) q = 0u;                  // off the stripe the frame's pixel passes through
+                c &= ~OT_CARRIED;
+            }
             return ov_tint(r, c & 255u, q) | (ov_tint(gg, (c >> 8) & 255u, q) << 8) | (ov_tint(b, c >> 16, q) << 16);
         };
         if constexpr (PX == 1) {
@@ -324,9 +344,28 @@ extern "C" int cgs_overlay_compose_tracks(const uint8_t* guide, const uint8_t* g
     if (const int rc = ov_prepare(guide, grey, out, n, h, w, r, g, b, alpha256, thickness, layout, flags, bad, &l)) return rc;
     if (max_objects > OT_K) return CGS_ERR_UNSUPPORTED;
     ov_dispatch(guide, grey, out, w, flags, [&](auto px, auto nt) {
-        hipLaunchKernelGGL((overlay_tracks_kernel<decltype(px)::value, decltype(nt)::value>), l.grid, dim3(OV_THREADS), 0, (hipStream_t)stream_,
-                           guide, grey, hard, labels, ids, table, font, (int)h, (int)w, (int)max_objects, l.tint, (uint32_t)alpha256,
-                           (int)thickness, (int)boxes, (int)layout, out);
+        hipLaunchKernelGGL((overlay_tracks_kernel<decltype(px)::value, decltype(nt)::value, false>), l.grid, dim3(OV_THREADS), 0,
+                           (hipStream_t)stream_, guide, grey, hard, labels, ids, table, font, (int)h, (int)w, (int)max_objects, l.tint,
+                           (uint32_t)alpha256, (int)thickness, (int)boxes, (int)layout, out, (const int32_t*)nullptr);
+    });
+    CGS_HIP_CHECK_LAUNCH();
+    return CGS_OK;
+}
+
+extern "C" int cgs_overlay_compose_tracks_carried(const uint8_t* guide, const uint8_t* grey, const uint8_t* hard, const int32_t* labels,
+                                                  const int32_t* ids, const int32_t* table, const int32_t* age, const uint8_t* font,
+                                                  int32_t n, int32_t h, int32_t w, int32_t max_objects, int32_t r, int32_t g, int32_t b,
+                                                  int32_t alpha256, int32_t thickness, int32_t boxes, int32_t layout, int32_t flags,
+                                                  uint8_t* out, cgs_stream_t stream_) {
+    const bool bad = !labels || !ids || !table || !age || !font || max_objects < 1 || boxes < 0 || boxes > CGS_OVERLAY_MAX_BOXES ||
+                     (((uintptr_t)labels | (uintptr_t)ids | (uintptr_t)table | (uintptr_t)age) & 3u);
+    OvLaunch l;
+    if (const int rc = ov_prepare(guide, grey, out, n, h, w, r, g, b, alpha256, thickness, layout, flags, bad, &l)) return rc;
+    if (max_objects > OT_K) return CGS_ERR_UNSUPPORTED;
+    ov_dispatch(guide, grey, out, w, flags, [&](auto px, auto nt) {
+        hipLaunchKernelGGL((overlay_tracks_kernel<decltype(px)::value, decltype(nt)::value, true>), l.grid, dim3(OV_THREADS), 0,
+                           (hipStream_t)stream_, guide, grey, hard, labels, ids, table, font, (int)h, (int)w, (int)max_objects, l.tint,
+                           (uint32_t)alpha256, (int)thickness, (int)boxes, (int)layout, out, age);
     });
     CGS_HIP_CHECK_LAUNCH();
     return CGS_OK;

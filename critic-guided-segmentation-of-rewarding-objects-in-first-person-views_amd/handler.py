@@ -591,6 +591,13 @@ class Handler:
              overlay.compose_tracks draws each in its track's colour with its box and number in place of overlay.compose.
              With --overlay-motion S the stream tracks along temporal.flow's backward vectors of the chunk's shrunk frames and the one
              before them (kept across the chunk boundary); the vectors stay on the device, 128 bytes a frame pair, for the reports.
+             With --overlay-fill (and --overlay-gap G >= 1) stage B splits: B1 is the above up to the labelling and pushes into an
+             objects.FillStream, which returns the frames that became final -- all but the last G pushed -- with the masks that bridged
+             links jump over filled in (objects.fill's result for the whole stack); B2 takes as many frames from the queue `held`, sets
+             the smoothed mask to 1 on the cells whose filled label differs from the segmented one, adds the carried objects' table rows
+             to the labeller's (disjoint: new objects are numbered behind the frame's largest label), and runs fit.up and
+             overlay.compose_tracks(age=), which draws a carried object hatched.  flush() behind the last chunk draws the last G frames.
+             The encoder gets the same frames in the same order, G frames later; G more frames of guide stay on the device.
         Stage A of chunk c + 1 runs before stage B of chunk c (a chunk waits until R frames after it are there, or the stream has ended).
         No PNG is written.  Rank 0 leaves {R}/{stem of OUT}.json, with --overlay-tracks also {R}/{stem}-objects.json and
         {R}/{stem}-tracks.json (process.video_reports; skipped beyond objects.TRACK_MAX_FRAMES frames, the video is complete all the
@@ -606,8 +613,10 @@ class Handler:
         track_iou = getattr(args, "overlay_tracks", None)
         track_gap = int(getattr(args, "overlay_gap", 0) or 0)                 # --overlay-gap: objects.TrackStream's max_gap
         track_motion = int(getattr(args, "overlay_motion", 0) or 0)           # --overlay-motion: the search range of its block vectors
-        stream = objects.TrackStream(track_iou, max_objects=overlay.MAX_TRACK_OBJECTS, max_gap=track_gap,
-                                     motion=bool(track_motion)) if track_iou is not None else None
+        track_fill = bool(getattr(args, "overlay_fill", False)) and track_iou is not None and track_gap > 0      # --overlay-fill
+        stream = (objects.FillStream if track_fill else objects.TrackStream)(
+            track_iou, max_objects=overlay.MAX_TRACK_OBJECTS, max_gap=track_gap, motion=bool(track_motion)) if track_iou is not None else None
+        held = deque()                                 # --overlay-fill: chunks through B1 whose frames are not all drawn yet
         before_low, fields = None, []                  # --overlay-motion: the shrunk frame before the chunk; every chunk's vectors
         ffmpeg, ffprobe = video_in.find_ffmpeg(), video_in.find_ffprobe()
         W, H, rate = video_in.probe(path, ffprobe)
@@ -637,6 +646,25 @@ class Handler:
             guide = torch.from_numpy(host).to(self.device)        # (a blocking copy: the reader may refill the buffer afterwards)
             low = fit.down(guide)
             return guide, low, process.fit_infer(eng, low, unit, fp16, bool(args.noevalmode)).contiguous().clone()
+
+        def stage_b2(filled):
+            """Draws the frames of `filled` (objects.Filled, in stream order): the oldest held ones."""
+            at, n_final = 0, int(filled.labels.shape[0])
+            while at < n_final:
+                guide, low, Zs, seg, table, lo = held[0]
+                m = min(n_final - at, len(Zs) - lo)    # one chunk's frames at a time: at most `step`, what a submit takes
+                cut, new = slice(lo, lo + m), slice(at, at + m)
+                labels = filled.labels[new]
+                Zf = torch.where(labels != seg[cut], torch.ones_like(Zs[cut]), Zs[cut])
+                up = fit.up(Zf, guide[cut], low[cut], thresh=thr if thr else None, want=("grey", "hard") if thr else ("grey",), **sig)
+                writer.submit(overlay.compose_tracks(guide[cut], up.grey, up.hard, labels, filled.track[new], table[cut] + filled.table[new],
+                                                     color=args.overlay_color, alpha256=args.overlay_alpha256,
+                                                     outline=args.overlay_outline, boxes=args.overlay_boxes, layout=args.overlay_layout,
+                                                     age=filled.age[new]))
+                at += m
+                held[0][5] = lo + m
+                if held[0][5] == len(Zs):
+                    held.popleft()
 
         def stage_b():
             nonlocal tail, moved, vectors, before_low, clean_counts
@@ -670,7 +698,8 @@ class Handler:
                 res = clean.clean(Zs, thresh=thr, inclusive=True, want_gated=True, **clean.spec_kwargs(spec))
                 Zs, clean_counts = res.gated, clean_counts + res.counts.sum(dim=0, dtype=torch.int64)
             masks.append(Zs.cpu().numpy()[:, None])
-            up = fit.up(Zs, guide, low, thresh=thr if thr else None, want=("grey", "hard") if thr else ("grey",), **sig)
+            if not track_fill:                         # (--overlay-fill upsamples in B2, the filled mask)
+                up = fit.up(Zs, guide, low, thresh=thr if thr else None, want=("grey", "hard") if thr else ("grey",), **sig)
             if stream is not None:
                 res = objects.label(Zs, thresh=thr, inclusive=True, connectivity=8, min_area=args.overlay_min_area,
                                     max_objects=overlay.MAX_TRACK_OBJECTS)
@@ -684,6 +713,9 @@ class Handler:
                     ids = stream.push(res.labels, bwd)
                 else:
                     ids = stream.push(res.labels)
+                if track_fill:                         # B1 ends here: `ids` is the FillStream's Filled for the frames that became final
+                    held.append([guide, low, Zs, res.labels, res.table, 0])
+                    return stage_b2(ids)
                 frames = overlay.compose_tracks(guide, up.grey, up.hard, res.labels, ids, res.table,
                                                 color=args.overlay_color, alpha256=args.overlay_alpha256, outline=args.overlay_outline,
                                                 boxes=args.overlay_boxes, layout=args.overlay_layout)
@@ -702,6 +734,8 @@ class Handler:
                     stage_b()
             while pending:
                 stage_b()
+            if track_fill and done:
+                stage_b2(stream.flush())
             writer.close()
         except BrokenPipeError as e:
             failure = e
@@ -739,6 +773,8 @@ class Handler:
             tracks = {"tracks": {"iou": track_iou, "min_area": args.overlay_min_area, "boxes": args.overlay_boxes,
                                  "scale": overlay.scale(H, W), "max_objects": overlay.MAX_TRACK_OBJECTS, "n_tracks": int(stream.n_tracks),
                                  **({"gap": track_gap} if track_gap else {}), **({"motion": track_motion} if track_motion else {}),
+                                 **({"fill": dict(zip(("objects", "cells", "dropped", "vanished"), (int(v) for v in stream.totals.tolist())))}
+                                    if track_fill else {}),
                                  "reports": reports}}
         write_json(f"{out_dir}/{stem}.json", {
             "frame_size": [H, W], "frames": len(M), "rate": rate, "layout": args.overlay_layout, "color": list(args.overlay_color),

@@ -16,7 +16,9 @@ threshold, chains resolved on the device), ``switches`` counts identity switches
 track is split over several predicted tracks.  With ``motion`` (``--track-motion``, ``--overlay-motion``) the earlier frame's labels
 are carried along ``temporal.flow``'s backward block vectors before they are intersected (cgs_objects_track_mc); ``motion_report``
 is the block the reports gain.  ``fill`` (csrc/objects_fill.hip, ``--track-fill``) gives the frames that a bridged link jumps over
-the mask of the link's tail object, carried there along the same vectors; ``fill_report`` is the block the reports gain."""
+the mask of the link's tail object, carried there along the same vectors; ``fill_report`` is the block the reports gain.
+``FillStream`` gives ``fill``'s result to a label stack that arrives in chunks, G frames behind it (``--overlay-fill``), through
+``fill(frames=)``, the frame range of a window (cgs_objects_track_fill_window)."""
 import re
 from collections import namedtuple
 
@@ -304,7 +306,17 @@ def track_colours(track_numbers):
     return torch.where((t != 0)[..., None], rgb, torch.zeros_like(rgb)).to(torch.uint8)
 
 
-def fill(labels, tracks, motion=None, max_objects=64, want_table=True, want_rgb=False):
+def _frame_range(frames, n):
+    """``fill``'s frames argument as (f0, f1) with 0 <= f0 <= f1 <= n; ValueError otherwise."""
+    if not isinstance(frames, (tuple, list)) or len(frames) != 2:
+        raise ValueError(f"frames must be None or a pair (f0, f1), got {frames!r}")
+    f0, f1 = _as_int(frames[0], "frames[0]"), _as_int(frames[1], "frames[1]")
+    if not 0 <= f0 <= f1 <= n:
+        raise ValueError(f"frames ({f0}, {f1}): 0 <= f0 <= f1 <= {n} (the stack's frames)")
+    return f0, f1
+
+
+def fill(labels, tracks, motion=None, max_objects=64, want_table=True, want_rgb=False, frames=None):
     """The masks that the bridged links of ``track`` jump over (cgs_objects_track_fill, whose header comment in include/cgs_hip.h is
     the rule).  labels: the int32 device stack [n,h,w] that was tracked; tracks: ``track``'s result for it with max_gap G >= 1 and the
     same max_objects (G is len(tracks.gap_links) - 1; a result without gap raises ValueError); motion: as in ``track``, and the field
@@ -316,6 +328,9 @@ def fill(labels, tracks, motion=None, max_objects=64, want_table=True, want_rgb=
     ``label``'s row of every new object, zero elsewhere, n_objects, n_cells, n_dropped, n_vanished: int32 scalars ON THE DEVICE (new
     objects, their cells, candidates dropped for want of a label, candidates that reached no free cell), rgb uint8 [n,h,w,3] or None:
     ``track``'s colour per track over the filled labels).  Nothing here synchronises.  No CPU path: raises CgsError without a GPU.
+    frames: None, or (f0, f1) with 0 <= f0 <= f1 <= n: only the frames f0 <= m < f1 are filled (cgs_objects_track_fill_window) -- the
+    results then hold f1 - f0 frames, frame m at m - f0, and the four counts are sums over those frames; every frame still sees the whole
+    stack around it, so (0, n) is the result of None bit for bit.  ``FillStream`` calls it so.
     Limits: the mask comes from the tail alone, moved by whole cells, block by block; cells that hold an object are never written."""
     if not isinstance(labels, torch.Tensor):
         raise ValueError(f"labels must be a torch tensor, got {type(labels).__name__}")
@@ -348,6 +363,8 @@ def fill(labels, tracks, motion=None, max_objects=64, want_table=True, want_rgb=
         if (h, w) != (MOTION_SIDE, MOTION_SIDE):
             raise ValueError(f"labels {tuple(labels.shape)}: motion needs frames of {MOTION_SIDE} x {MOTION_SIDE} (8 x 8 blocks of 8 cells)")
         motion = _motion_field(motion, n, labels.device)
+    if frames is not None:
+        f0, f1 = _frame_range(frames, n)
     if not torch.cuda.is_available() or not labels.is_cuda:
         raise _lib.CgsError("objects.fill runs on the GPU (cgs_objects_track_fill); " + ("no GPU is visible" if not torch.cuda.is_available()
                             else f"the tensor is on {labels.device}") + " and there is no CPU fallback")
@@ -355,14 +372,22 @@ def fill(labels, tracks, motion=None, max_objects=64, want_table=True, want_rgb=
     prev, gap, trk = tracks.prev.contiguous(), tracks.gap.contiguous(), tracks.track.contiguous()
     dev, K = labels.device, max_objects
     with torch.cuda.device(dev):
-        out = torch.empty((n, h, w), dtype=torch.int32, device=dev)
-        out_track = torch.empty((n, K), dtype=torch.int32, device=dev)
-        age = torch.empty((n, K), dtype=torch.int32, device=dev)
-        table = torch.empty((n, K, len(FIELDS)), dtype=torch.int32, device=dev) if want_table else None
+        m, rows = (n, n) if frames is None else (f1 - f0, max(f1 - f0, 1))       # (an empty range still hands the entry real buffers)
+        out = torch.empty((rows, h, w), dtype=torch.int32, device=dev)
+        out_track = torch.empty((rows, K), dtype=torch.int32, device=dev)
+        age = torch.empty((rows, K), dtype=torch.int32, device=dev)
+        table = torch.empty((rows, K, len(FIELDS)), dtype=torch.int32, device=dev) if want_table else None
         totals = torch.empty(4, dtype=torch.int32, device=dev)
-        _lib.call("cgs_objects_track_fill", labels.data_ptr(), motion.data_ptr() if motion is not None and n > 1 else None, n, h, w, K, G,
-                  prev.data_ptr(), gap.data_ptr(), trk.data_ptr(), out.data_ptr(), out_track.data_ptr(), age.data_ptr(),
-                  table.data_ptr() if want_table else None, totals.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        field = motion.data_ptr() if motion is not None and n > 1 else None
+        if frames is None:
+            _lib.call("cgs_objects_track_fill", labels.data_ptr(), field, n, h, w, K, G,
+                      prev.data_ptr(), gap.data_ptr(), trk.data_ptr(), out.data_ptr(), out_track.data_ptr(), age.data_ptr(),
+                      table.data_ptr() if want_table else None, totals.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        else:
+            _lib.call("cgs_objects_track_fill_window", labels.data_ptr(), field, n, h, w, K, G, prev.data_ptr(), gap.data_ptr(),
+                      trk.data_ptr(), f0, f1, out.data_ptr(), out_track.data_ptr(), age.data_ptr(),
+                      table.data_ptr() if want_table else None, totals.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            out, out_track, age, table, n = out[:m], out_track[:m], age[:m], table[:m] if want_table else None, m
         rgb = None
         if want_rgb:
             inside = (out >= 1) & (out <= K)
@@ -453,6 +478,88 @@ class TrackStream:
             self._carry = (torch.cat((last, labels))[-keep:].contiguous().clone(), torch.cat((last_ids, ids))[-keep:].clone())
             self._vectors = torch.cat((self._vectors, bwd))[-keep:].clone() if self.motion else None
         return ids
+
+
+class FillStream:
+    """``fill`` for a label stack that comes in chunks: for every split of a stack, the concatenation of what ``push`` and ``flush``
+    return (labels, track, age, table) is ``fill(stack, track(stack, iou, max_objects, max_gap=G, motion=...), motion=...)`` bit for bit,
+    and the four counts, summed over the calls, are the whole stack's (``totals`` holds the sums so far, int32 [4] on the device:
+    objects, cells, dropped, vanished).  The track numbers are the whole stream's, ``TrackStream``'s, for segmented and carried objects.
+    A frame m is spanned only by links (a -> f) with f in (m, m + G] and a >= m - G, and a link depends on the frames a .. f only
+    (``TrackStream``), so a frame is final once G frames behind it are pushed, and a window that starts G frames before the first frame
+    not yet returned holds every link that spans it: ``push`` returns all frames pushed so far except the last G, less those already
+    returned -- possibly none -- and ``flush`` the rest, behind which no frame exists.  The stream holds at most 2 G frames beside the
+    chunk.  Per push: ``TrackStream.push`` for the numbers, ``track`` over the window for prev / gap, and cgs_objects_track_fill_window
+    over the frames that became final.  ``n_tracks`` is ``TrackStream``'s; nothing here synchronises with the host."""
+
+    def __init__(self, iou, max_objects=64, max_gap=1, motion=False):
+        max_gap = _max_gap(max_gap)
+        if max_gap < 1:
+            raise ValueError(f"max_gap must be 1..{TRACK_MAX_GAP} for FillStream (without a bridged link there is nothing to fill), got 0")
+        self._stream = TrackStream(iou, max_objects=max_objects, max_gap=max_gap, motion=motion)
+        self.iou, self.max_objects, self.max_gap, self.motion = self._stream.iou, self._stream.max_objects, max_gap, self._stream.motion
+        self.totals = None                     # int32 [4] on the device after the first push
+        self._labels = self._ids = self._bwd = None      # the window: frames _start .. _pushed - 1 of the stream
+        self._start = self._done = self._pushed = 0      # _done: frames returned so far; _start = max(0, _done - max_gap)
+        self._flushed = False
+
+    @property
+    def n_tracks(self):
+        return self._stream.n_tracks
+
+    def _empty(self, like):
+        K, dev = self.max_objects, like.device
+        zero = torch.zeros(4, dtype=torch.int32, device=dev)
+        return Filled(like.new_empty((0,) + tuple(like.shape[1:])), torch.empty((0, K), dtype=torch.int32, device=dev),
+                      torch.empty((0, K), dtype=torch.int32, device=dev), torch.empty((0, K, len(FIELDS)), dtype=torch.int32, device=dev),
+                      zero[0], zero[1], zero[2], zero[3], None)
+
+    def _final(self, upto):
+        """The frames _done .. upto - 1 of the stream, filled; the window then starts max_gap frames before `upto`."""
+        if upto <= self._done:
+            return self._empty(self._labels)
+        G, lo = self.max_gap, self._start
+        field = self._bwd[1:] if self.motion else None                   # row i: frames i + 1 -> i of the window
+        tr = track(self._labels, iou=self.iou, max_objects=self.max_objects, max_tracks=1, max_gap=G, motion=field)
+        out = fill(self._labels, tr._replace(track=self._ids), motion=field, max_objects=self.max_objects,
+                   frames=(self._done - lo, upto - lo))
+        self.totals = self.totals + torch.stack((out.n_objects, out.n_cells, out.n_dropped, out.n_vanished))
+        self._done = upto
+        keep = max(lo, upto - G) - lo
+        self._labels, self._ids = self._labels[keep:].contiguous(), self._ids[keep:].contiguous()
+        if self.motion:
+            self._bwd = self._bwd[keep:].contiguous()
+        self._start = lo + keep
+        return out
+
+    def push(self, labels, bwd=None):
+        """labels (and bwd with motion=True) as ``TrackStream.push`` takes them.  Returns ``fill``'s Filled for the frames that became
+        final, in stream order: zero or more frames (rgb is None)."""
+        if self._flushed:
+            raise ValueError("the stream was flushed: a new stack needs a new FillStream")
+        if isinstance(labels, torch.Tensor) and labels.dim() == 3 and int(labels.shape[0]) + 2 * self.max_gap > TRACK_MAX_FRAMES:
+            raise ValueError(f"a chunk of {int(labels.shape[0])} frames: with the {2 * self.max_gap} frames of the window at most "
+                             f"{TRACK_MAX_FRAMES} are tracked at once")
+        ids = self._stream.push(labels, bwd)                             # (every check of the arguments is there)
+        labels = labels.contiguous()
+        if self._labels is None:
+            self._labels, self._ids, self._bwd = labels, ids, bwd
+            self.totals = torch.zeros(4, dtype=torch.int32, device=labels.device)
+        else:
+            self._labels, self._ids = torch.cat((self._labels, labels)), torch.cat((self._ids, ids))
+            if self.motion:
+                self._bwd = torch.cat((self._bwd, bwd))
+        self._pushed += int(labels.shape[0])
+        return self._final(self._pushed - self.max_gap)
+
+    def flush(self):
+        """The frames not yet returned, at most max_gap (none when everything was returned); the stream ends here."""
+        if self._labels is None:
+            raise ValueError("nothing was pushed")
+        if self._flushed:
+            raise ValueError("the stream was flushed already")
+        self._flushed = True
+        return self._final(self._pushed)
 
 
 def switches(truth_prev, pred_track, best, iou):

@@ -153,7 +153,7 @@ def _device_font(font, device):
 
 
 def compose_tracks(guide, grey, hard, labels, ids, table, font=FONT, color=COLOR, alpha256=128, outline=OUTLINE, boxes=BOXES, layout=LAYOUT,
-                   out=None, nontemporal=NONTEMPORAL):
+                   out=None, nontemporal=NONTEMPORAL, age=None):
     """``compose`` with the tracked objects drawn: guide, grey, hard, color, alpha256, outline, layout, out, nontemporal as there (hard may
     be None).  labels: int32 [n,64,64], ``objects.label``'s labels of the 64 x 64 masks; ids: int32 [n,K], K <= 64, the track number of
     every object (``objects.TrackStream.push``; 0: none); table: int32 [n,K,8], ``objects.label``'s table (area and bounding box are
@@ -163,11 +163,14 @@ def compose_tracks(guide, grey, hard, labels, ids, table, font=FONT, color=COLOR
     its object being the label of its home cell (fit.home_cells) or, when that is 0, of the nearest labelled cell of the 5 x 5 cells
     around it; `color` where there is none.  Every object with a track gets its box on the cells' pixel tiling and, at the box's top left
     corner, a plate with the track number in digits scale(H, W) font pixels big.  Plates lie over borders, borders over the outline.
+    age: None, or int32 [n,K], ``objects.fill``'s age: an object with age > 0 is a carried one and is drawn hatched
+    (cgs_overlay_compose_tracks_carried) -- on the stripes ((x + y) // (2 scale(H, W))) & 1 == 0 as above, between them without tint and
+    without its box's border; plate, digits and outline stay whole.  All ages <= 0 give the bytes of age=None.
     Integers throughout (include/cgs_hip.h has every formula).  No CPU path: raises CgsError without a GPU."""
     boxes = check_boxes(boxes)
 
     def tracked(n):
-        for name, t in (("labels", labels), ("ids", ids), ("table", table)):
+        for name, t in (("labels", labels), ("ids", ids), ("table", table)) + ((("age", age),) if age is not None else ()):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
                 raise ValueError(f"{name} must be an int32 tensor, got " + (str(t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
         side = _lib.FIT_SIDE
@@ -177,14 +180,23 @@ def compose_tracks(guide, grey, hard, labels, ids, table, font=FONT, color=COLOR
             raise ValueError(f"ids must be [{n},K] with K in 1..{MAX_TRACK_OBJECTS}, got {tuple(ids.shape)}")
         if tuple(table.shape) != (n, ids.shape[1], _lib.OBJ_FIELDS):
             raise ValueError(f"table must be [{n},{ids.shape[1]},{_lib.OBJ_FIELDS}] beside ids {tuple(ids.shape)}, got {tuple(table.shape)}")
-        return (labels, ids, table), ((font,) if isinstance(font, torch.Tensor) else ())
+        if age is not None and tuple(age.shape) != tuple(ids.shape):
+            raise ValueError(f"age must be [{n},{ids.shape[1]}] as ids, got {tuple(age.shape)}")
+        return (labels, ids, table) + ((age,) if age is not None else ()), ((font,) if isinstance(font, torch.Tensor) else ())
 
-    guide, grey, hard, out, (n, h, w), (r, g, b), outline, k = _prepare("overlay.compose_tracks (cgs_overlay_compose_tracks)", guide, grey,
+    entry = "cgs_overlay_compose_tracks" if age is None else "cgs_overlay_compose_tracks_carried"
+    guide, grey, hard, out, (n, h, w), (r, g, b), outline, k = _prepare(f"overlay.compose_tracks ({entry})", guide, grey,
                                                                         hard, color, alpha256, outline, layout, out, more=tracked)
     K = int(ids.shape[1])
     font = _device_font(font, guide.device)
     labels, ids, table = labels.contiguous(), ids.contiguous(), table.contiguous()
     with torch.cuda.device(guide.device):
+        if age is not None:
+            age = age.contiguous()
+            _lib.call(entry, guide.data_ptr(), grey.data_ptr(), hard.data_ptr() if hard is not None else None, labels.data_ptr(),
+                      ids.data_ptr(), table.data_ptr(), age.data_ptr(), font.data_ptr(), n, h, w, K, r, g, b, int(alpha256), outline, boxes, k,
+                      _lib.OVERLAY_NONTEMPORAL if nontemporal else 0, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            return out
         _lib.call("cgs_overlay_compose_tracks", guide.data_ptr(), grey.data_ptr(), hard.data_ptr() if hard is not None else None,
                   labels.data_ptr(), ids.data_ptr(), table.data_ptr(), font.data_ptr(), n, h, w, K, r, g, b, int(alpha256), outline, boxes, k,
                   _lib.OVERLAY_NONTEMPORAL if nontemporal else 0, out.data_ptr(), torch.cuda.current_stream().cuda_stream)

@@ -127,7 +127,8 @@ def video_reports(args, M, stem, device, rank, bwd=None):
     stream labelled them (threshold inclusive, 8-connected, --overlay-min-area), as {R}/{stem}-objects.json and {R}/{stem}-tracks.json
     with the frames keyed "000000", "000001", ... in stream order and no PNG.  objects.TrackStream gives objects.track's numbers, so
     the numbers of tracks.json are the ones drawn on the video.  bwd: with --overlay-motion the backward field the stream tracked along,
-    int8 [n - 1,8,8,2] on the device.  Returns the two file names."""
+    int8 [n - 1,8,8,2] on the device.  With --overlay-fill {stem}-tracks.json carries what --track-fill adds to tracks.json (the
+    whole stack filled by objects.fill: the stream's objects.FillStream gives the same).  Returns the two file names."""
     thresh = float(args.binarymaskthreshold)
     stack = torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(device)
     res = objects.label(stack, thresh=thresh, inclusive=True, connectivity=8, min_area=args.overlay_min_area,
@@ -137,7 +138,8 @@ def video_reports(args, M, stem, device, rank, bwd=None):
     names = (f"{stem}-objects.json", f"{stem}-tracks.json")
     _objects(args, res, head, stems, M.shape[-1], rank, png=False, name=names[0])
     _tracks(args, res, head, stems, rank, png=False, name=names[1], iou=args.overlay_tracks, gap=int(getattr(args, "overlay_gap", 0) or 0),
-            bwd=bwd, search=int(getattr(args, "overlay_motion", 0) or 0) if bwd is not None else 0)
+            bwd=bwd, search=int(getattr(args, "overlay_motion", 0) or 0) if bwd is not None else 0,
+            fill=bool(getattr(args, "overlay_fill", False)))
     return list(names)
 
 

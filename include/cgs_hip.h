@@ -1041,6 +1041,23 @@ int cgs_objects_track_fill(const int32_t* labels, const int8_t* bwd, int32_t n, 
                            int32_t max_gap, const int32_t* prev, const int32_t* gap, const int32_t* track, int32_t* out_labels,
                            int32_t* out_track, int32_t* age, int32_t* table, int32_t* totals, cgs_stream_t stream);
 
+/* cgs_objects_track_fill_window (csrc/objects_fill.hip): cgs_objects_track_fill for the frames f0 <= m < f1 of a window of n frames, what
+ * a stream needs whose window carries halo frames on both sides (cgs_temporal_smooth takes f0, f1 for the same reason).
+ *   labels, bwd, n, h, w, max_objects, max_gap, prev, gap, track   as cgs_objects_track_fill: the WHOLE window of n frames
+ *   f0, f1     0 <= f0 <= f1 <= n.  Only the frames f0 <= m < f1 get a workgroup.
+ *   out_labels int32 [f1 - f0][h][w], out_track, age int32 [f1 - f0][K], table int32 [f1 - f0][K][CGS_OBJ_FIELDS] or NULL: frame m's
+ *              outputs of cgs_objects_track_fill at index m - f0
+ *   totals     int32 [4], zeroed by the entry on the stream: the four sums over the frames f0 <= m < f1 only
+ * Frame m reads the labels of m - G .. m - 1 (and the vectors between them) and the prev / gap rows of m + 1 .. m + G, clipped to
+ * 0 .. n - 1, exactly as the whole-stack entry does: f0 = 0, f1 = n gives its outputs bit for bit.  f0 == f1 launches nothing and
+ * zeroes totals.  A stream needs the sub-range because dropped / vanished exist only in totals, and a window's totals would include
+ * halo frames whose contribution is not final.  The bounded-read guarantees, the argument checks and the limits are those of
+ * cgs_objects_track_fill; besides them 0 <= f0 <= f1 <= n, else CGS_ERR_BADARG (nothing is launched).                               */
+int cgs_objects_track_fill_window(const int32_t* labels, const int8_t* bwd, int32_t n, int32_t h, int32_t w, int32_t max_objects,
+                                  int32_t max_gap, const int32_t* prev, const int32_t* gap, const int32_t* track, int32_t f0, int32_t f1,
+                                  int32_t* out_labels, int32_t* out_track, int32_t* age, int32_t* table, int32_t* totals,
+                                  cgs_stream_t stream);
+
 /* ---- the saliency baseline over a threshold grid (csrc/saliency.hip; Handler._saliency_post, main.py:976-1003; this build's own
  * -eval -salience --salience-grid) -----------------------------------------------------------------------------------------------------
  * The baseline's whole post-processing for T thresholds at once, each threshold with its own normaliser as the host form has it.  A
@@ -1221,6 +1238,22 @@ int cgs_overlay_compose_tracks(const uint8_t* guide, const uint8_t* grey, const 
                                const int32_t* table, const uint8_t* font, int32_t n, int32_t h, int32_t w, int32_t max_objects, int32_t r,
                                int32_t g, int32_t b, int32_t alpha256, int32_t thickness, int32_t boxes, int32_t layout, int32_t flags,
                                uint8_t* out, cgs_stream_t stream);
+
+/* cgs_overlay_compose_tracks_carried (csrc/overlay_tracks.hip; -process --source-video --overlay-fill): cgs_overlay_compose_tracks with
+ * the objects that cgs_objects_track_fill carried into a frame drawn hatched, so that a carried mask shows as what it is.
+ *   age       int32 [n][K]: cgs_objects_track_fill's age.  Object l of frame f is a carried one when age[f][l - 1] > 0; any int32
+ *             content is read safely.  Every other argument is cgs_overlay_compose_tracks's.
+ * With s = max(1, min(h, w) / 256), the plate scale, pixel (y, x) of the overlay panel is on the stripe when ((x + y) / (2 s)) & 1 == 0.
+ *   tint      off the stripe a pixel whose object is a carried one gets no tint: q = 0, the frame's pixel passes through
+ *   border    off the stripe a border pixel of a carried object's box is not a border pixel of that object; the lower priorities
+ *             (the borders of the later labels, the outline, the tint) then apply
+ * Plate, digits, outline and every object with age <= 0 are as in cgs_overlay_compose_tracks, and so are the frame panel and the grey
+ * panel.  With every age <= 0 the output is cgs_overlay_compose_tracks's byte for byte, at every access width, layout and box
+ * thickness.  age not NULL and 4-byte aligned, else CGS_ERR_BADARG; the other checks are cgs_overlay_compose_tracks's.               */
+int cgs_overlay_compose_tracks_carried(const uint8_t* guide, const uint8_t* grey, const uint8_t* hard, const int32_t* labels,
+                                       const int32_t* ids, const int32_t* table, const int32_t* age, const uint8_t* font, int32_t n,
+                                       int32_t h, int32_t w, int32_t max_objects, int32_t r, int32_t g, int32_t b, int32_t alpha256,
+                                       int32_t thickness, int32_t boxes, int32_t layout, int32_t flags, uint8_t* out, cgs_stream_t stream);
 
 /* ---- block-matched motion for the temporal filter (csrc/temporal_motion.hip; -process --source-video --smooth R --smooth-motion S) -------
  * cgs_temporal_smooth looks, for a tap in frame f + k, at the 3 x 3 cells around the cell's own position whatever k is; under a camera pan
