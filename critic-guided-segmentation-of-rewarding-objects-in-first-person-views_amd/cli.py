@@ -53,6 +53,13 @@ def build_parser():
     # tail object, carried there along the vectors of --track-motion (objects.fill); -process leaves {stem}-filled-mask.png and paints
     # {stem}-tracks-mask.png from the filled labels, -eval adds "fill" to eval_tracks.json.  Not for --source-video
     p.add_argument("--track-fill", action="store_true")
+    # (this build's own flag) --track-iou T --track-reid S: tracks that do not overlap in time, lie at most --track-reid-window W frames
+    # apart (1..1024, default 64) and whose 64-bin colour histograms intersect to at least S (in (0, 1]) are chained into one identity
+    # on the GPU (objects.appearance, objects.reid); --track-reid-area A (default 64) is the pixels a track needs over its life.
+    # -process leaves {stem}-identities-mask.png and adds to tracks.json, -eval adds to eval_tracks.json.  Not for --source-video
+    p.add_argument("--track-reid", type=str, default=None)
+    p.add_argument("--track-reid-window", type=str, default=None)
+    p.add_argument("--track-reid-area", type=str, default=None)
     # (this build's own flag) -eval --boundary-tol "0-1-2-3" or "lo:hi:n": every evaluated stack's outline against the truth's outline at
     # these tolerances in pixels -- boundary F, boundary IoU and the Hausdorff distance -- on the GPU (boundary.score); leaves
     # {model}/eval_boundary.json
@@ -189,7 +196,9 @@ def check_objects_flags(args):
     """-objects / --min-area / --connectivity / --match-iou / --track-iou / --track-gap / --track-motion / --track-fill / --boundary-tol:
     combinations that could not run and a malformed --match-iou, --track-iou, --track-gap, --track-motion or --boundary-tol are refused
     here, before any GPU work; the defaults (--min-area 1, --connectivity 8, --track-gap 0 and --track-motion 0 as ints) are filled in.
-    --boundary-tol needs -eval, not -objects; --track-fill needs --track-iou and a --track-gap of at least 1, and no --source-video."""
+    --boundary-tol needs -eval, not -objects; --track-fill needs --track-iou and a --track-gap of at least 1, and no --source-video.
+    --track-reid S needs --track-iou and no --source-video; it becomes a float, and --track-reid-window / --track-reid-area (which need
+    it) become ints, 64 and 64 by default."""
     given = [f for f, v in (("--min-area", args.min_area), ("--connectivity", args.connectivity)) if v is not None]
     if args.match_iou:
         from .objects import parse_match_iou
@@ -230,6 +239,20 @@ def check_objects_flags(args):
         if args.source_video:
             raise ValueError("--track-fill with --source-video: outside this build (the stream would have to look --overlay-gap frames "
                              "ahead before it draws a frame); the video path's own flag is --overlay-fill, which does")
+    reid_more = [f for f, v in (("--track-reid-window", args.track_reid_window), ("--track-reid-area", args.track_reid_area)) if v is not None]
+    if args.track_reid is None:
+        if reid_more:
+            raise ValueError(f"{' / '.join(reid_more)} belong to --track-reid: give --track-reid S")
+    else:
+        from . import objects as _objects
+        if not args.track_iou:
+            raise ValueError("--track-reid belongs to --track-iou: give --track-iou T")
+        if args.source_video:
+            raise ValueError("--track-reid with --source-video: outside this build (the stream path has no identity layer)")
+        args.track_reid = _objects.parse_track_reid(args.track_reid)
+        args.track_reid_window = (_objects.REID_WINDOW if args.track_reid_window is None
+                                  else _objects.parse_track_reid_window(args.track_reid_window))
+        args.track_reid_area = _objects.REID_MIN_AREA if args.track_reid_area is None else _objects.parse_track_reid_area(args.track_reid_area)
     if not args.objects:
         if given:
             raise ValueError(f"{' / '.join(given)} belong to -objects: give -objects")

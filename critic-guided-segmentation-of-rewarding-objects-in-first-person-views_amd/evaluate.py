@@ -172,10 +172,12 @@ def match_report(args, st):
         f"{b['truth_objects']} truth objects, f1 {fmt(first(b)['f1'])}, pq {fmt(first(b)['pq'])}" for pre, b in _blocks(st, report))
 
 
-def _tracked(labelled, iou, gap=0, motion=None):
+def _tracked(labelled, iou, gap=0, motion=None, reid=None):
     """(Tracks, one side of eval_tracks.json) of a labelled stack: tracked on the GPU, the length histogram and the link sums formed
     there; only the totals, 7 counts and 3 sums come back (with --track-gap also the links by gap and the missed frames).  motion:
-    (bwd, search) of --track-motion; the side then gains "track_motion"."""
+    (bwd, search) of --track-motion; the side then gains "track_motion".  reid: (frames, similarity, window, area) of --track-reid;
+    the tracks are chained into identities on the GPU (objects.appearance, objects.reid), the side gains "reid" (four counts) and the
+    Reid comes back as the third item (None without it)."""
     K = MATCH_MAX_OBJECTS
     tr = objects.track(labelled.labels, iou=iou, max_objects=K, max_gap=gap, motion=motion[0] if motion else None)
     totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
@@ -184,7 +186,12 @@ def _tracked(labelled, iou, gap=0, motion=None):
                                 (labelled.kept - K).clamp(min=0).sum(), **more)
     if motion:
         side["track_motion"] = objects.motion_report(*motion)
-    return tr, side
+    rd = None
+    if reid:
+        rd = objects.reid(tr, objects.appearance(reid[0], labelled.labels, tr, max_objects=K), labelled.labels.shape[0], *reid[1:])
+        counts = torch.stack([rd.n_eligible, rd.n_links, rd.n_identities, rd.longest]).tolist()
+        side["reid"] = dict(zip(("eligible", "links", "identities", "longest"), (int(v) for v in counts)))
+    return tr, side, rd
 
 
 def _fill_block(labels, tracks, motion, truth):
@@ -202,18 +209,22 @@ def tracks_report(args, st):
     from the matches eval_match.json reports.  --track-gap G tracks truth and predictions with the same G (objects.track's max_gap);
     the switches then follow the truth's adjacent links only, and every threshold's entry gains "fragments" (objects.fragments).
     --track-motion S tracks both along one field, temporal.flow of the evaluation frames as bytes (the stack "frames").
-    --track-fill (with a gap) gives every predicted stack's side "fill" (_fill_block); the truth is tracked as ever and never filled."""
+    --track-fill (with a gap) gives every predicted stack's side "fill" (_fill_block); the truth is tracked as ever and never filled.
+    --track-reid S re-identifies truth and predictions with the same parameters on the stack "frames": every side gains "reid", and
+    with --match-iou every threshold's entry "fragments_identity", objects.fragments on the identities of both sides."""
     t_iou = objects.parse_track_iou(args.track_iou)
     gap = int(getattr(args, "track_gap", 0) or 0)
     search = int(getattr(args, "track_motion", 0) or 0)
     motion = (temporal.flow(st.dev("frames"), search)[1], search) if search else None
     fill = bool(getattr(args, "track_fill", False) and gap)
     m_iou = objects.parse_match_iou(args.match_iou) if getattr(args, "match_iou", "") else None
-    truth_tr, truth_side = _tracked(st.labelled("truth"), t_iou, gap, motion)
+    sim = getattr(args, "track_reid", None)
+    reid = (st.dev("frames").contiguous(), sim, args.track_reid_window, args.track_reid_area) if sim else None
+    truth_tr, truth_side, truth_rd = _tracked(st.labelled("truth"), t_iou, gap, motion, reid)
     report = _head(args, max_objects=MATCH_MAX_OBJECTS, track_iou=t_iou, truth=truth_side)
     truth_prev = torch.where(truth_tr.gap == 1, truth_tr.prev, 0) if gap else truth_tr.prev     # (without gaps every link has gap 1)
     for name in st.names(("mask", "crf")):
-        pred_tr, side = _tracked(st.labelled(name), t_iou, gap, motion)
+        pred_tr, side, pred_rd = _tracked(st.labelled(name), t_iou, gap, motion, reid)
         report[name] = {"pred": side}
         if fill:
             report[name]["fill"] = _fill_block(st.labelled(name).labels, pred_tr, motion, st.dev("truth"))
@@ -225,18 +236,24 @@ def tracks_report(args, st):
             if gap:
                 for entry, v in zip(report[name]["switches"], objects.fragments(truth_tr.track, pred_tr.track, best, m_iou).cpu().numpy()):
                     entry["fragments"] = int(v)
+            if reid:
+                frag = objects.fragments(objects.identities(truth_tr.track, truth_rd.identity),
+                                         objects.identities(pred_tr.track, pred_rd.identity), best, m_iou).cpu().numpy()
+                for entry, v in zip(report[name]["switches"], frag):
+                    entry["fragments_identity"] = int(v)
     report = _json_safe(report)
     p = report["mask"]["pred"]
     moved = f" motion<={search}" if search else ""
+    again = f"; reid {p['reid']['links']} links, {p['reid']['identities']} identities" if reid else ""
     if gap:
         f = report["mask"].get("fill")
         filled = f"; filled {f['objects']} objects, iou {fmt(f['iou_before'])} -> {fmt(f['iou'])}" if f else ""
         return report, (f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g} gap<={gap}{moved}: {p['tracks']} tracks over "
                         f"{p['objects']} objects ({p['bridged_links']} of {p['links']} links bridged), mean length {fmt(p['mean_length'])}, "
-                        f"longest {p['max_length']}; truth {truth_side['tracks']} tracks over {truth_side['objects']} objects{filled}")
+                        f"longest {p['max_length']}; truth {truth_side['tracks']} tracks over {truth_side['objects']} objects{filled}{again}")
     return report, (f"\nTRACKS conn={args.connectivity} min_area={args.min_area} iou>={t_iou:g}{moved}: {p['tracks']} tracks over {p['objects']} "
                     f"objects, mean length {fmt(p['mean_length'])}, longest {p['max_length']}; truth {truth_side['tracks']} tracks over "
-                    f"{truth_side['objects']} objects")
+                    f"{truth_side['objects']} objects{again}")
 
 
 # ---------------------------------------------------------------------------------------------------------------- the clean-up

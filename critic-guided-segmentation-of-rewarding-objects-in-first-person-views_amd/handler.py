@@ -481,7 +481,8 @@ class Handler:
             process.write_clean(args, source, thresh, res.counts, stems[:len(frames)], self.rank, pngs=cleaned.cpu().numpy())
         if getattr(args, "objects", False):     # (this build's flag) not a column: the by-position naming and the strip stay as they are
             process.objects_and_tracks(args, M, cols[-1] if args.crf else None, stems[:len(frames)], self.device, self.rank,
-                                       low=np.ascontiguousarray(file_bytes, dtype=np.uint8) if getattr(args, "track_motion", 0) else None,
+                                       low=np.ascontiguousarray(file_bytes, dtype=np.uint8)
+                                       if getattr(args, "track_motion", 0) or getattr(args, "track_reid", None) else None,
                                        cleaned=cleaned)
         if args.process_salience:       # main.py:1176-1197
             sal_maps, sal_hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
@@ -534,7 +535,7 @@ class Handler:
         masks, crf_masks = [], []
         spec = getattr(args, "clean", None)              # --clean: per chunk the cleaned 64 x 64 masks and their counts, on the device
         cleaned, clean_counts, clean_head = [], [], None
-        lows = [] if getattr(args, "objects", False) and getattr(args, "track_motion", 0) else None     # --track-motion: the shrunk frames
+        lows = [] if getattr(args, "objects", False) and (getattr(args, "track_motion", 0) or getattr(args, "track_reid", None)) else None     # --track-motion / --track-reid: the shrunk frames
         unit = process.unit_table(self.device)
         for lo in range(0, len(files), step):
             print("segmentation in progress", round(lo / len(files), 2), end="%\r")
@@ -943,7 +944,7 @@ class Handler:
             if getattr(args, "match_iou", ""):
                 self.matches = report(evaluate.match_report, "eval_match.json")
             if getattr(args, "track_iou", ""):
-                if getattr(args, "track_motion", 0):   # the frames as bytes, the conversion of Handler.crf
+                if getattr(args, "track_motion", 0) or getattr(args, "track_reid", None):   # the frames as bytes, the conversion of Handler.crf
                     st.host["frames"] = frames if frames.dtype == np.uint8 else (255 * frames).astype(np.uint8)
                 self.tracks = report(evaluate.tracks_report, "eval_tracks.json")
         if getattr(args, "boundary_tol", ""):   # (this build's flag) the outlines against the truth's outline

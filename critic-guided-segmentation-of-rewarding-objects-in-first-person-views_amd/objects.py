@@ -18,7 +18,10 @@ are carried along ``temporal.flow``'s backward block vectors before they are int
 is the block the reports gain.  ``fill`` (csrc/objects_fill.hip, ``--track-fill``) gives the frames that a bridged link jumps over
 the mask of the link's tail object, carried there along the same vectors; ``fill_report`` is the block the reports gain.
 ``FillStream`` gives ``fill``'s result to a label stack that arrives in chunks, G frames behind it (``--overlay-fill``), through
-``fill(frames=)``, the frame range of a window (cgs_objects_track_fill_window)."""
+``fill(frames=)``, the frame range of a window (cgs_objects_track_fill_window).  ``appearance`` and ``reid`` (csrc/objects_reid.hip,
+``--track-reid``) put an identity layer on top of the tracks: a 64-bin colour histogram per track, and tracks that do not overlap in
+time, lie at most ``window`` frames apart and have the same histogram are chained into one identity; ``identities`` gives every object
+its identity, and ``parse_track_reid`` / ``parse_track_reid_window`` / ``reid_report`` are the host helpers."""
 import re
 from collections import namedtuple
 
@@ -40,6 +43,10 @@ TRACK_MAX_GAP = _lib.OBJ_TRACK_MAX_GAP
 MOTION_SIDE, MOTION_BLOCKS, MOTION_MAX_SEARCH = 64, 64 // _lib.TEMPORAL_BLOCK, _lib.TEMPORAL_MAX_SEARCH      # cgs_objects_track_mc
 Tracks = namedtuple("Tracks", ["prev", "track", "n_tracks", "n_links", "n_objects", "longest", "table", "track_labels", "rgb",
                                "gap", "gap_links", "extra"], defaults=(None, None, None))
+REID_BINS, REID_MAX_WINDOW, REID_MAX_FRAMES = _lib.OBJ_REID_BINS, _lib.OBJ_REID_MAX_WINDOW, _lib.OBJ_REID_MAX_FRAMES
+REID_SIM, REID_WINDOW, REID_MIN_AREA = 0.8, 64, 64          # --track-reid's defaults: judgements, not tuned values
+Appearance = namedtuple("Appearance", ["track_hist", "object_hist"])
+Reid = namedtuple("Reid", ["prev", "next", "sim", "identity", "signature", "n_identities", "n_links", "n_eligible", "longest"])
 Filled = namedtuple("Filled", ["labels", "track", "age", "table", "n_objects", "n_cells", "n_dropped", "n_vanished", "rgb"])
 
 
@@ -396,6 +403,145 @@ def fill(labels, tracks, motion=None, max_objects=64, want_table=True, want_rgb=
     return Filled(out, out_track, age, table, totals[0], totals[1], totals[2], totals[3], rgb)
 
 
+def appearance(frames, labels, tracks=None, max_objects=64, want_objects=False):
+    """The colour histograms of cgs_objects_appearance (its header comment in include/cgs_hip.h is the rule).  frames: uint8 device
+    tensor [n,h,w,3], the frames the labels were made from; labels: int32 [n,h,w] on the same device, 1 <= h, w <= 64, n <= 2^14;
+    tracks: ``track``'s result for these labels with the same max_objects, or None.  A pixel's bin is ((R >> 6) << 4) | ((G >> 6) << 2)
+    | (B >> 6), 64 bins.  Returns Appearance(track_hist int32 [max_tracks,64] (max_tracks: the rows of tracks.table): per track the
+    pixels of its objects by bin, None without tracks; object_hist int32 [n,K,64]: the same per object, None unless want_objects or
+    tracks is None).  Nothing here synchronises.  No CPU path: raises CgsError without a GPU."""
+    for name, t, dtype in (("frames", frames, torch.uint8), ("labels", labels, torch.int32)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if labels.dim() != 3 or frames.dim() != 4 or tuple(frames.shape) != tuple(labels.shape) + (3,):
+        raise ValueError(f"labels must be [n,h,w] and frames [n,h,w,3], got {tuple(labels.shape)} and {tuple(frames.shape)}")
+    n, h, w = (int(s) for s in labels.shape)
+    if not 1 <= n <= REID_MAX_FRAMES or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError(f"labels {tuple(labels.shape)}: 1..{REID_MAX_FRAMES} frames of 1..{MAX_SIDE} x 1..{MAX_SIDE} pixels")
+    max_objects = _as_int(max_objects, "max_objects")
+    if not 1 <= max_objects <= MATCH_MAX_OBJECTS:
+        raise ValueError(f"max_objects must be 1..{MATCH_MAX_OBJECTS}, got {max_objects}")
+    if frames.device != labels.device:
+        raise ValueError(f"frames are on {frames.device}, the labels on {labels.device}")
+    if tracks is not None:
+        if not isinstance(tracks, Tracks):
+            raise ValueError(f"tracks must be the result of objects.track or None, got {type(tracks).__name__}")
+        t = tracks.track
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (n, max_objects):
+            raise ValueError(f"tracks.track must be int32 [{n},{max_objects}] (the labels' frames, max_objects), got "
+                             + (f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__))
+        if t.device != labels.device:
+            raise ValueError(f"tracks.track is on {t.device}, the labels on {labels.device}")
+    if not torch.cuda.is_available() or not labels.is_cuda:
+        raise _lib.CgsError("objects.appearance runs on the GPU (cgs_objects_appearance); " + ("no GPU is visible" if not
+                            torch.cuda.is_available() else f"the tensors are on {labels.device}") + " and there is no CPU fallback")
+    frames, labels = frames.contiguous(), labels.contiguous()
+    dev, K = labels.device, max_objects
+    want_objects = bool(want_objects) or tracks is None
+    with torch.cuda.device(dev):
+        rows = int(tracks.table.shape[0]) if tracks is not None else 0
+        trk = tracks.track.contiguous() if tracks is not None else None
+        S = torch.empty((rows, REID_BINS), dtype=torch.int32, device=dev) if tracks is not None else None
+        H = torch.empty((n, K, REID_BINS), dtype=torch.int32, device=dev) if want_objects else None
+        _lib.call("cgs_objects_appearance", frames.data_ptr(), labels.data_ptr(), trk.data_ptr() if trk is not None else None, n, h, w, K,
+                  rows, S.data_ptr() if S is not None else None, H.data_ptr() if H is not None else None,
+                  torch.cuda.current_stream().cuda_stream)
+    return Appearance(S, H)
+
+
+def _reid_milli(sim):
+    """``reid``'s similarity threshold in (0, 1] as whole thousandths; ValueError in the style of ``_track_milli``."""
+    try:
+        return _track_milli(sim)
+    except ValueError as e:
+        raise ValueError(str(e).replace("track IoU", "re-identification similarity")) from None
+
+
+def _reid_window(window):
+    window = _as_int(window, "window")
+    if not 1 <= window <= REID_MAX_WINDOW:
+        raise ValueError(f"window must be 1..{REID_MAX_WINDOW}, got {window}")
+    return window
+
+
+def reid(tracks, appearance, n_frames, sim=REID_SIM, window=REID_WINDOW, min_area=REID_MIN_AREA):
+    """Tracks chained into identities by colour (cgs_objects_reid, whose header comment in include/cgs_hip.h is the rule).  tracks:
+    ``track``'s result for a stack of n_frames frames, with the full table (max_tracks >= n_frames * max_objects: a truncated table
+    cannot be re-identified); appearance: ``appearance``'s result for the same tracks.  A track is eligible with at least min_area
+    pixels over its life; its signature is its histogram scaled to 4096.  Eligible tracks t, u with last(t) < first(u) <= last(t) +
+    window are linked when each is the other's best partner by histogram intersection and the intersection reaches sim (whole
+    thousandths in (0, 1]) of the smaller signature sum, in integers.  An identity is a maximal chain of links.
+    Returns Reid(prev, next int32 [max_tracks]: the track linked before / behind track t at t - 1, 0 for none; sim int32 [max_tracks]:
+    the intersection of the link to prev; identity int32 [max_tracks]: numbered from 1 by their first track, zero from n_tracks on;
+    signature int16 [max_tracks,64]; n_identities, n_links, n_eligible, longest: int32 scalars ON THE DEVICE (no synchronisation here;
+    longest is the most tracks in one identity)).  The defaults 0.8 / 64 / 64 are judgements, not tuned values.  No CPU path."""
+    if not isinstance(tracks, Tracks):
+        raise ValueError(f"tracks must be the result of objects.track, got {type(tracks).__name__}")
+    if not isinstance(appearance, Appearance) or not isinstance(appearance.track_hist, torch.Tensor):
+        raise ValueError("appearance must be the result of objects.appearance with tracks (its track_hist is needed)")
+    n = _as_int(n_frames, "n_frames")
+    if not 1 <= n <= REID_MAX_FRAMES:
+        raise ValueError(f"n_frames must be 1..{REID_MAX_FRAMES}, got {n}")
+    table, trk, S = tracks.table, tracks.track, appearance.track_hist
+    if not isinstance(trk, torch.Tensor) or trk.dim() != 2 or int(trk.shape[0]) != n:
+        raise ValueError(f"tracks.track must be [{n},K] (n_frames rows), got "
+                         + (f"{tuple(trk.shape)}" if isinstance(trk, torch.Tensor) else type(trk).__name__))
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != len(TRACK_FIELDS):
+        raise ValueError(f"tracks.table must be int32 [max_tracks,{len(TRACK_FIELDS)}]")
+    rows, K = int(table.shape[0]), int(trk.shape[1])
+    if rows < n * K:
+        raise ValueError(f"tracks.table has {rows} rows, {n} frames of {K} objects need {n * K}: a truncated table cannot be re-identified "
+                         "(track with max_tracks=None)")
+    if S.dtype != torch.int32 or tuple(S.shape) != (rows, REID_BINS):
+        raise ValueError(f"appearance.track_hist must be int32 [{rows},{REID_BINS}] (the table's rows), got {S.dtype} {tuple(S.shape)}")
+    extra = tracks.extra
+    if extra is not None and (not isinstance(extra, torch.Tensor) or extra.dtype != torch.int32 or tuple(extra.shape) != (rows, 2)):
+        raise ValueError(f"tracks.extra must be int32 [{rows},2] or None")
+    milli, window = _reid_milli(sim), _reid_window(window)
+    min_area = _as_int(min_area, "min_area")
+    if not 1 <= min_area <= 0x7FFFFFFF:
+        raise ValueError(f"min_area must be at least 1 (and fit 32 bits), got {min_area}")
+    if not torch.cuda.is_available() or not table.is_cuda:
+        raise _lib.CgsError("objects.reid runs on the GPU (cgs_objects_reid); " + ("no GPU is visible" if not torch.cuda.is_available()
+                            else f"the table is on {table.device}") + " and there is no CPU fallback")
+    dev = table.device
+    for name, t in (("appearance.track_hist", S), ("tracks.n_tracks", tracks.n_tracks), ("tracks.extra", extra)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, the table on {dev}")
+    table, S = table.contiguous(), S.contiguous()
+    extra = extra.contiguous() if extra is not None else None
+    with torch.cuda.device(dev):
+        n_tracks = tracks.n_tracks.reshape(1).to(torch.int32).contiguous()
+        need = int(_lib.load().cgs_objects_reid_scratch_bytes(n, rows))
+        scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        out = torch.empty((4, rows), dtype=torch.int32, device=dev)
+        totals = torch.empty(4, dtype=torch.int32, device=dev)
+        Q = torch.empty((rows, REID_BINS), dtype=torch.int16, device=dev)
+        _lib.call("cgs_objects_reid", S.data_ptr(), table.data_ptr(), extra.data_ptr() if extra is not None else None, n_tracks.data_ptr(),
+                  n, rows, milli, window, min_area, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(),
+                  totals.data_ptr(), Q.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, torch.cuda.current_stream().cuda_stream)
+    return Reid(out[0], out[1], out[2], out[3], Q, totals[0], totals[1], totals[2], totals[3])
+
+
+def identities(track, identity):
+    """The identity of every object: track int [n,K] (``Tracks.track`` or ``Filled.track``, so a carried object gets its track's
+    identity), identity int [max_tracks] (``Reid.identity``), on one device.  int32 [n,K], 0 where there is no object or the track
+    number lies beyond the table.  A gather in torch, no synchronisation."""
+    if not isinstance(track, torch.Tensor) or track.dim() != 2 or not isinstance(identity, torch.Tensor) or identity.dim() != 1:
+        raise ValueError("track must be a tensor [n,K] and identity a tensor [max_tracks]")
+    if track.device != identity.device:
+        raise ValueError(f"track is on {track.device}, identity on {identity.device}")
+    t = track.to(torch.int64)
+    rows = int(identity.shape[0])
+    inside = (t >= 1) & (t <= rows)
+    if rows == 0:
+        return torch.zeros_like(track, dtype=torch.int32)
+    got = identity.to(torch.int32)[(t - 1).clamp(0, rows - 1)]
+    return torch.where(inside, got, torch.zeros_like(got))
+
+
 def stream_remap(local, carried_local, carried_global, c0, n_tracks):
     """The track numbers of a chunk tracked behind one carried frame, as numbers of the whole stream.  local: int [m,K], rows 1.. of
     ``track(cat(carry, chunk)).track``; carried_local: int [K], its row 0 (every object of the carried frame heads a track there, so
@@ -667,6 +813,74 @@ def fill_report(filled):
     "dropped", "vanished"}.  One transfer of the four scalars."""
     counts = torch.stack([filled.n_objects, filled.n_cells, filled.n_dropped, filled.n_vanished]).tolist()
     return dict(zip(("objects", "cells", "dropped", "vanished"), (int(v) for v in counts)))
+
+
+def parse_track_reid(s, flag="--track-reid"):
+    """``--track-reid``: the similarity threshold, one number in (0, 1], a whole number of thousandths.  Returns it as a float;
+    ValueError otherwise."""
+    s = str(s).strip()
+    try:
+        v = float(s)
+    except ValueError:
+        raise ValueError(f"{flag} {s!r}: expected one number in (0, 1]") from None
+    try:
+        return _reid_milli(v) / 1000
+    except ValueError as e:
+        raise ValueError(f"{flag} {s!r}: {e}") from None
+
+
+def parse_track_reid_window(s, flag="--track-reid-window"):
+    """``--track-reid-window``: a whole number 1..1024 (objects.REID_MAX_WINDOW), the most frames between the last frame of a track and
+    the first of the track that continues it.  Returns the int; ValueError otherwise."""
+    try:
+        v = int(str(s).strip())
+    except ValueError:
+        raise ValueError(f"{flag} {s!r}: expected a whole number 1..{REID_MAX_WINDOW}") from None
+    if not 1 <= v <= REID_MAX_WINDOW:
+        raise ValueError(f"{flag} {v}: expected a whole number 1..{REID_MAX_WINDOW}")
+    return v
+
+
+def parse_track_reid_area(s, flag="--track-reid-area"):
+    """``--track-reid-area``: a whole number >= 1, the pixels a track needs over its life to be re-identified.  Returns the int."""
+    try:
+        v = int(str(s).strip())
+    except ValueError:
+        raise ValueError(f"{flag} {s!r}: expected a whole number of at least 1") from None
+    if not 1 <= v <= 0x7FFFFFFF:
+        raise ValueError(f"{flag} {v}: expected a whole number of at least 1 (that fits 32 bits)")
+    return v
+
+
+def reid_report(reid, table, extra=None, sim=REID_SIM, window=REID_WINDOW, min_area=REID_MIN_AREA):
+    """The "track_reid" block of tracks.json from ``reid``'s result and the tracks' table (and extra): {"sim", "window", "min_area",
+    "bins": 64, "eligible", "links", "identities", "longest", "link_gaps": the links by first(u) - last(t) in LENGTH_BINS}.
+    eval_tracks.json's "reid" is its four counts.  Tensors or arrays; the gaps are binned where they are."""
+    counts = [int(v) for v in _host(torch.stack([reid.n_identities, reid.n_links, reid.n_eligible, reid.longest])
+                                    if isinstance(reid.n_identities, torch.Tensor) else
+                                    [reid.n_identities, reid.n_links, reid.n_eligible, reid.longest]).reshape(-1)]
+    prev, table = _host(reid.prev).reshape(-1).astype(np.int64), _host(table).astype(np.int64)
+    last = table[:, 0] + table[:, 2] - 1 + (_host(extra).astype(np.int64)[:, 1] if extra is not None else 0)
+    u = np.flatnonzero(prev[:table.shape[0]] > 0)
+    gaps = table[u, 0] - last[prev[u] - 1]
+    if len(u) != counts[1] or (len(u) and gaps.min() < 1):
+        raise ValueError(f"{len(u)} links in prev, the totals say {counts[1]} (or a link that does not run forward in time)")
+    return {"sim": float(sim), "window": int(window), "min_area": int(min_area), "bins": REID_BINS, "eligible": counts[2],
+            "links": counts[1], "identities": counts[0], "longest": counts[3],
+            "link_gaps": dict(zip(LENGTH_BINS, (int(v) for v in length_hist(gaps))))}
+
+
+def identity_rows(identity, reid_prev, n_tracks, first, last, lengths):
+    """The "identities" list of tracks.json: identity, reid_prev [max_tracks] (tensors or arrays), and per track (index t - 1) the names
+    of its first and last frame and its length in objects.  [{"identity", "tracks": [...], "first", "last", "objects"}] in order."""
+    identity = _host(identity).reshape(-1)
+    rows = {}
+    for t in range(int(n_tracks)):
+        row = rows.setdefault(int(identity[t]), {"identity": int(identity[t]), "tracks": [], "first": first[t], "last": last[t], "objects": 0})
+        row["tracks"].append(t + 1)
+        row["last"] = last[t]
+        row["objects"] += int(lengths[t])
+    return [rows[k] for k in sorted(rows)]
 
 
 def parse_track_iou(s):

@@ -106,7 +106,7 @@ def write_clean_pngs(out_dir, stems, masks):
 def objects_and_tracks(args, M, crf_mask, stems, device, rank, low=None, cleaned=None):
     """-process -objects [--track-iou]: the stack of binary_source labelled on the GPU once (objects.py; labels, mask and counts do not
     depend on the table's rows), then reported as objects and, if asked for, as tracks.  low: with --track-motion the uint8 frames
-    [n,64,64,3] the masks were made from (tensor or array, in the order of stems).  cleaned: with --clean the cleaned bool stack on the
+    [n,64,64,3] the masks were made from (tensor or array, in the order of stems); --track-reid needs them too.  cleaned: with --clean the cleaned bool stack on the
     device, which is then the one described; the reports' header gains "clean"."""
     want_tracks = bool(getattr(args, "track_iou", ""))
     source, thresh, stack, kw = binary_source(args, M, crf_mask, device, cleaned)
@@ -116,10 +116,12 @@ def objects_and_tracks(args, M, crf_mask, stems, device, rank, low=None, cleaned
     _objects(args, res, head, stems, M.shape[-1], rank)
     if want_tracks:
         search = int(getattr(args, "track_motion", 0) or 0)
-        if search and low is None:
-            raise ValueError("--track-motion needs the 64 x 64 frames of the masks")
-        _tracks(args, res, head, stems, rank, low=torch.as_tensor(low).to(device) if search else None, search=search,
-                fill=bool(getattr(args, "track_fill", False)))
+        reid = getattr(args, "track_reid", None)
+        if (search or reid) and low is None:
+            raise ValueError("--track-motion and --track-reid need the 64 x 64 frames of the masks")
+        _tracks(args, res, head, stems, rank, low=torch.as_tensor(low).to(device) if search or reid else None, search=search,
+                fill=bool(getattr(args, "track_fill", False)),
+                reid=(reid, args.track_reid_window, args.track_reid_area) if reid else None)
 
 
 def video_reports(args, M, stem, device, rank, bwd=None):
@@ -161,7 +163,8 @@ def _objects(args, res, head, stems, width, rank, png=True, name="objects.json")
         Image.fromarray(np.repeat((mask[i] * np.uint8(255))[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-objects-mask.png")
 
 
-def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None, gap=None, low=None, bwd=None, search=0, fill=False):
+def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None, gap=None, low=None, bwd=None, search=0, fill=False,
+            reid=None):
     """The objects objects.json describes followed through the frames in natural order of their names on the GPU (objects.track);
     labels above 64 are untracked.  Rank 0 writes {R}/tracks.json and per frame {R}/{stem}-tracks-mask.png, a colour per track
     (png=False: the report alone, as {R}/{name}; iou, gap: the link threshold and the gap when they are not --track-iou's and
@@ -173,7 +176,10 @@ def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None
     object's carried mask (objects.fill).  {stem}-tracks-mask.png is then painted from the filled labels, {stem}-filled-mask.png holds
     the filled labels > 0 as 0 / 255 grey RGB, and the report gains "track_fill" (objects.fill_report), per frame an entry {"label",
     "track", "filled": the frames the mask was carried over, "area"} for every new object, and per track "filled", the number of its
-    new objects, counted on the device."""
+    new objects, counted on the device.  reid (--track-reid: similarity, window, area): the tracks are chained into identities by the
+    colour histograms of low (objects.appearance, objects.reid); the report gains "track_reid" (objects.reid_report), per track
+    "identity", "reid_prev" and "reid_sim", and the list "identities", and {stem}-identities-mask.png is painted with
+    objects.track_colours of every pixel's identity, from the filled labels with fill.  Nothing else changes."""
     from PIL import Image
     K, iou = MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou) if iou is None else iou
     gap = int(getattr(args, "track_gap", 0) or 0) if gap is None else gap
@@ -189,6 +195,12 @@ def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None
         fl = objects.fill(stack, tr, motion=bwd if search else None, max_objects=K, want_rgb=png)
         new = fl.age > 0
         per_track = torch.bincount(fl.track[new].to(torch.int64).clamp(min=0), minlength=stack.shape[0] * K + 1)
+    if reid:
+        rd = objects.reid(tr, objects.appearance(low[pick].contiguous(), stack, tr, max_objects=K), stack.shape[0], *reid)
+        painted = fl.labels if fill else stack
+        per_object = objects.identities(fl.track if fill else tr.track, rd.identity)
+        number = torch.gather(per_object, 1, (painted.reshape(painted.shape[0], -1).to(torch.int64) - 1).clamp(0, K - 1)).reshape(painted.shape)
+        identity_rgb = objects.track_colours(torch.where((painted >= 1) & (painted <= K), number, torch.zeros_like(number))) if png else None
     if rank != 0:
         return
     totals = torch.stack([tr.n_tracks, tr.n_links, tr.n_objects, tr.longest])
@@ -216,6 +228,14 @@ def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None
                                        for l in np.flatnonzero(age[j])]
         for row in report["tracks"]:
             row["filled"] = int(per_track[row["track"]])
+    if reid:
+        identity, r_prev, r_sim = rd.identity.cpu().numpy(), rd.prev.cpu().numpy(), rd.sim.cpu().numpy()
+        report["track_reid"] = objects.reid_report(rd, tr.table, tr.extra, *reid)
+        for row in report["tracks"]:
+            t = row["track"] - 1
+            row.update(identity=int(identity[t]), reid_prev=int(r_prev[t]), reid_sim=int(r_sim[t]))
+        report["identities"] = objects.identity_rows(identity, r_prev, len(rows), [r["first"] for r in report["tracks"]],
+                                                     [r["last"] for r in report["tracks"]], [r["length"] for r in rows])
     out_dir = args.mask_output_imgs
     write_json(f"{out_dir}/{name}", report)
     if not png:
@@ -223,6 +243,10 @@ def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None
     rgb = (fl.rgb if fill else tr.rgb).cpu().numpy()
     for j, stem in enumerate(names):
         Image.fromarray(rgb[j]).save(f"{out_dir}/{stem}-tracks-mask.png")
+    if reid:
+        identity_rgb = identity_rgb.cpu().numpy()
+        for j, stem in enumerate(names):
+            Image.fromarray(identity_rgb[j]).save(f"{out_dir}/{stem}-identities-mask.png")
     if fill:
         on = (fl.labels > 0).cpu().numpy()
         for j, stem in enumerate(names):

@@ -1058,6 +1058,65 @@ int cgs_objects_track_fill_window(const int32_t* labels, const int8_t* bwd, int3
                                   int32_t* out_labels, int32_t* out_track, int32_t* age, int32_t* table, int32_t* totals,
                                   cgs_stream_t stream);
 
+/* cgs_objects_appearance, cgs_objects_reid (csrc/objects_reid.hip): an identity layer on top of the tracks.  Tracks that do not overlap
+ * in time, lie at most W frames apart and have the same colour histogram are chained into one identity; the tracks themselves, their
+ * links and their numbers are not touched.  This comment is the specification.
+ *   frames     uint8 [n][h][w][3], the frames the labels were made from; labels int32 [n][h][w]; track int32 [n][K] as cgs_objects_track*
+ *              wrote it; tracks int32 [max_tracks][8] and tracks_extra int32 [max_tracks][2] (NULL for a tracker result without gaps);
+ *              n_tracks: the tracker's totals[0], read ON THE DEVICE, used as min(max(n_tracks, 0), max_tracks) = N.
+ *              1 <= h, w <= 64, K = max_objects <= 64.
+ *   bin        a pixel's bin is ((R >> 6) << 4) | ((G >> 6) << 2) | (B >> 6): 64 bins, four levels a channel.  (64 is one lane per bin
+ *              of a wave: a judgement, not a tuned value.)
+ *   H          object histogram: H[f][l-1][b] = the pixels of frame f with label l in 1..K and bin b.  Labels outside 1..K count nowhere.
+ *   S          track histogram: S[t-1][b] = the sum of H[f][l-1][b] over all (f, l) with track[f][l-1] == t, int32; a track number
+ *              outside 1..max_tracks counts nowhere.  The track's pixel count is A_t = sum_b S[t-1][b] -- defined from S, not taken from
+ *              the table's area_sum, so it does not depend on which tracker entry made the table.
+ *   signature  track t is eligible when A_t >= min_area.  Then Q[t-1][b] = floor(S[t-1][b] * 4096 / A_t), computed in 64 bits, stored as
+ *              int16, and D_t = sum_b Q[t-1][b], which lies in 4033..4096.  For an ineligible t, Q is all zero and D_t = 0.
+ *   time       F_t = the table's first_frame; L_t = F_t + length + missed - 1 with missed from tracks_extra, 0 without it.  (t -> u) is
+ *              a candidate pair when both are eligible and L_t < F_u <= L_t + W.  Tracks are numbered by first frame, then label, so the
+ *              u of one t are a contiguous range of track numbers, all above t.
+ *   similarity s(t, u) = sum_b min(Q_t[b], Q_u[b]).  A candidate pair is admissible when 1000 s >= sim_milli min(D_t, D_u), in
+ *              integers: identical histograms score 1.0.
+ *   links      succ[t] = the admissible u of largest s, ties to the smallest u; pred[u] = the admissible t of largest s, ties to the
+ *              smallest t.  t -> u is a link when succ[t] == u and pred[u] == t.  Links are one to one and run forward in time, so
+ *              chains are acyclic and their members do not overlap in time.
+ *   identity   a maximal chain of links; identities are numbered from 1 in the order of their first track's number.  A track without a
+ *              link is an identity of its own, ineligible tracks included.
+ * cgs_objects_appearance: one launch, one workgroup per frame.
+ *   track_hist   int32 [max_tracks][64] = S, zeroed by the entry on the stream, or NULL together with track: only H is made then
+ *   object_hist  int32 [n][K][64] = H, or NULL: not written
+ * frames, labels not NULL, track and track_hist both NULL or both not, at least one output, n, h, w, max_objects >= 1, max_tracks >= 1
+ * with track, int32 pointers 4-byte aligned, else CGS_ERR_BADARG (nothing is launched); then h, w <= 64, max_objects <= 64 and n <=
+ * CGS_OBJ_REID_MAX_FRAMES (S and Q have n K rows for a full table: the tracker's 2^17 frames would need gigabytes), else
+ * CGS_ERR_UNSUPPORTED.  Integer sums in LDS and int32 global atomic adds: bit-reproducible.
+ * cgs_objects_reid: n is the number of frames of the stack (first_frame < n), W = window, every output indexed by t - 1.
+ *   reid_prev, reid_next  int32 [max_tracks]: the track linked before / behind t, 0 for none
+ *   reid_sim   int32 [max_tracks]: the s of the link to reid_prev, else 0
+ *   identity   int32 [max_tracks]
+ *   signature  int16 [max_tracks][64] = Q, 16-byte aligned
+ *   totals     int32 [4]: identities, links, eligible tracks, the most tracks in one identity (0 for N = 0)
+ *   The five arrays are zero from row N on.
+ *   scratch    caller-owned, 8-byte aligned, at least cgs_objects_reid_scratch_bytes(n, max_tracks) bytes (0 for n or max_tracks < 1);
+ *              holds nothing between calls
+ * Runs on `stream` without synchronising, allocates nothing; 7 + R launches and memsets, R = ceil(log2(min(n, max_tracks) - 1)) rounds
+ * of pointer doubling (a chain has at most n members), a function of n and max_tracks alone.  All integer; global atomics are int32 add
+ * / max and one unsigned 64-bit max: bit-reproducible.  No read or write is out of range for any int32 content of track_hist, tracks,
+ * tracks_extra or n_tracks (the candidate range comes from a search that is bounded whatever the first column holds, every pair is
+ * checked against the rule itself, and a link is only taken towards a larger number); the outputs are the rule's when the first column
+ * is non-decreasing over the first N rows, as every tracker entry writes it.  max_tracks >= n K is not required: a truncated
+ * table re-identifies the tracks it holds.  Pointers other than tracks_extra not NULL and aligned, n, max_tracks >= 1, sim_milli in
+ * 1..1000, window in 1..CGS_OBJ_REID_MAX_WINDOW, min_area >= 1, scratch_bytes large enough, else CGS_ERR_BADARG (nothing is launched);
+ * then n <= CGS_OBJ_REID_MAX_FRAMES, else CGS_ERR_UNSUPPORTED.                                                                          */
+enum { CGS_OBJ_REID_BINS = 64, CGS_OBJ_REID_MAX_WINDOW = 1024, CGS_OBJ_REID_MAX_FRAMES = 1 << 14 };
+int cgs_objects_appearance(const uint8_t* frames, const int32_t* labels, const int32_t* track, int32_t n, int32_t h, int32_t w,
+                           int32_t max_objects, int32_t max_tracks, int32_t* track_hist, int32_t* object_hist, cgs_stream_t stream);
+int64_t cgs_objects_reid_scratch_bytes(int32_t n, int32_t max_tracks);
+int cgs_objects_reid(const int32_t* track_hist, const int32_t* tracks, const int32_t* tracks_extra, const int32_t* n_tracks, int32_t n,
+                     int32_t max_tracks, int32_t sim_milli, int32_t window, int32_t min_area, int32_t* reid_prev, int32_t* reid_next,
+                     int32_t* reid_sim, int32_t* identity, int32_t* totals, int16_t* signature, void* scratch, int64_t scratch_bytes,
+                     cgs_stream_t stream);
+
 /* ---- the saliency baseline over a threshold grid (csrc/saliency.hip; Handler._saliency_post, main.py:976-1003; this build's own
  * -eval -salience --salience-grid) -----------------------------------------------------------------------------------------------------
  * The baseline's whole post-processing for T thresholds at once, each threshold with its own normaliser as the host form has it.  A
