@@ -67,7 +67,8 @@ OBJ_MATCH_MAX_OBJECTS, OBJ_MATCH_MAX_IOU = 64, 16                               
 OBJ_TRACK_FIELDS, OBJ_TRACK_MAX_FRAMES = 8, 1 << 17                             # cgs_objects_track (include/cgs_hip.h)
 OBJ_TRACK_MAX_GAP = 8                                                           # cgs_objects_track_gap: a judgement, not a measured value
 OBJ_REID_BINS, OBJ_REID_MAX_WINDOW, OBJ_REID_MAX_FRAMES = 64, 1024, 1 << 14        # cgs_objects_appearance / cgs_objects_reid (include/cgs_hip.h)
-SALIENCY_SIDE, SALIENCY_MAX_T = 64, 1024                                        # cgs_saliency_sweep (include/cgs_hip.h)
+OBJ_VALUE_MAX_OBJECTS, OBJ_VALUE_MAX_GROW, OBJ_VALUE_SIDE = 64, 4, 64              # cgs_objects_ablate / cgs_objects_select (include/cgs_hip.h)
+SALIENCY_SIDE, SALIENCY_MAX_T = 64, 1024                                       # cgs_saliency_sweep (include/cgs_hip.h)
 BOUNDARY_MAX_TOL, BOUNDARY_MAX_TOL_PX = 16, 128                                 # cgs_boundary_score (include/cgs_hip.h)
 FIT_SIDE, FIT_MAX_SIDE, FIT_RADIUS, FIT_MAP_F32, FIT_MAP_U8 = 64, 4096, 2, 0, 1 # cgs_fit_down_u8 / cgs_fit_up_joint (include/cgs_hip.h)
 TEMPORAL_SIDE, TEMPORAL_MAX_RADIUS = 64, 8                                      # cgs_temporal_smooth (include/cgs_hip.h)
@@ -232,6 +233,8 @@ SIGNATURES = {
     "cgs_objects_appearance": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "cgs_objects_reid_scratch_bytes": (i64, [i32, i32]),
     "cgs_objects_reid": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "cgs_objects_ablate": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_uint32, vp, i64, i64, vp, vp, vp, vp]),
+    "cgs_objects_select": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "cgs_saliency_sweep": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "cgs_boundary_score": (i32, [vp, i32, f32, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
     "cgs_fit_down_u8": (i32, [vp, i32, i32, i32, vp, vp]),

@@ -60,6 +60,17 @@ def build_parser():
     p.add_argument("--track-reid", type=str, default=None)
     p.add_argument("--track-reid-window", type=str, default=None)
     p.add_argument("--track-reid-area", type=str, default=None)
+    # (this build's own flags) -objects --object-value: the critic is asked about every object (objects.value): the frame is rebuilt on
+    # the GPU once per object with that object replaced -- by the frame of smallest value (--object-value-fill low, the training rule's
+    # B, the default), by the frame's mean background colour (mean) or by a colour R,G,B -- together with the cells within
+    # --object-value-grow cells of it (0..4, default 0), and the object's value is how far the critic's value of the frame falls.
+    # --min-value-drop V keeps the objects whose drop is at least V and renumbers them (objects.select): the mask PNGs, --track-iou,
+    # --match-iou and everything on top then describe those.  -process adds to objects.json / tracks.json and leaves
+    # {stem}-valued-mask.png, -eval adds to eval_objects.json / eval_match.json.  Not for --source-video, not with -noevalmode
+    p.add_argument("--object-value", action="store_true")
+    p.add_argument("--object-value-fill", type=str, default=None)
+    p.add_argument("--object-value-grow", type=str, default=None)
+    p.add_argument("--min-value-drop", type=str, default=None)
     # (this build's own flag) -eval --boundary-tol "0-1-2-3" or "lo:hi:n": every evaluated stack's outline against the truth's outline at
     # these tolerances in pixels -- boundary F, boundary IoU and the Hausdorff distance -- on the GPU (boundary.score); leaves
     # {model}/eval_boundary.json
@@ -198,7 +209,9 @@ def check_objects_flags(args):
     here, before any GPU work; the defaults (--min-area 1, --connectivity 8, --track-gap 0 and --track-motion 0 as ints) are filled in.
     --boundary-tol needs -eval, not -objects; --track-fill needs --track-iou and a --track-gap of at least 1, and no --source-video.
     --track-reid S needs --track-iou and no --source-video; it becomes a float, and --track-reid-window / --track-reid-area (which need
-    it) become ints, 64 and 64 by default."""
+    it) become ints, 64 and 64 by default.  --object-value needs -objects, no --source-video and no -noevalmode; --object-value-fill
+    (low | mean | R,G,B, default low), --object-value-grow (0..4, default 0) and --min-value-drop (a finite number, default none) need
+    it and are parsed here.  The two defaults are judgements, not tuned values."""
     given = [f for f, v in (("--min-area", args.min_area), ("--connectivity", args.connectivity)) if v is not None]
     if args.match_iou:
         from .objects import parse_match_iou
@@ -253,6 +266,22 @@ def check_objects_flags(args):
         args.track_reid_window = (_objects.REID_WINDOW if args.track_reid_window is None
                                   else _objects.parse_track_reid_window(args.track_reid_window))
         args.track_reid_area = _objects.REID_MIN_AREA if args.track_reid_area is None else _objects.parse_track_reid_area(args.track_reid_area)
+    value_more = [f for f, v in (("--object-value-fill", args.object_value_fill), ("--object-value-grow", args.object_value_grow),
+                                 ("--min-value-drop", args.min_value_drop)) if v is not None]
+    if not args.object_value:
+        if value_more:
+            raise ValueError(f"{' / '.join(value_more)} belong to --object-value: give --object-value")
+    else:
+        from . import objects as _objects
+        given.append("--object-value")
+        if args.source_video:
+            raise ValueError("--object-value with --source-video: outside this build (the stream path does not score its objects)")
+        if args.noevalmode:
+            raise ValueError("--object-value with -noevalmode: Dropout would make the values noise; the critic is asked in eval mode")
+        args.object_value_fill = (_objects.VALUE_FILL if args.object_value_fill is None
+                                  else _objects.parse_object_value_fill(args.object_value_fill))
+        args.object_value_grow = _objects.VALUE_GROW if args.object_value_grow is None else _objects.parse_object_value_grow(args.object_value_grow)
+        args.min_value_drop = None if args.min_value_drop is None else _objects.parse_min_value_drop(args.min_value_drop)
     if not args.objects:
         if given:
             raise ValueError(f"{' / '.join(given)} belong to -objects: give -objects")

@@ -39,10 +39,12 @@ def fmt(v):
 class Stacks:
     """The stacks of one -eval run by name, host arrays in `host`: "truth" (bool), "mask" (the probabilities, float32, read with the
     strict compare of --eval-thresh, main.py:964), the hard stacks "crf", "saliency", "saliency_crf" where the run has them, and the
-    saliency sweep's inputs "sal" and "preds" (float32), and with --track-motion "frames" (uint8 [n,64,64,3]).  dev uploads a stack when it is first read; labelled and matched likewise."""
+    saliency sweep's inputs "sal" and "preds" (float32), and with --track-motion "frames" (uint8 [n,64,64,3]).  dev uploads a stack when it is first read; labelled and matched likewise.
+    With --object-value the run also sets "frames" and `infer`, the critic as objects.value asks it (uint8 [b,64,64,3] -> [b])."""
 
     def __init__(self, args, device, **host):
         self.args, self.device, self.host, self._made = args, device, host, {}
+        self.infer = None
 
     def _once(self, key, make):
         if key not in self._made:
@@ -71,7 +73,7 @@ class Stacks:
             return self.cleaned(name).mask, None
         return self.dev(name), self.thresh(name)
 
-    def labelled(self, name):
+    def labelled_all(self, name):
         """objects.label's result for a stack, labels and kept-pixel mask: a prediction with --connectivity and --min-area (the
         objects eval_objects.json counts), the truth unfiltered.  One call serves every report: labels, mask, found and kept do not
         depend on max_objects, and no report reads the table.  With --clean a prediction is labelled after the clean-up."""
@@ -81,10 +83,37 @@ class Stacks:
             src, thresh=thresh, connectivity=a.connectivity, min_area=1 if name == "truth" else a.min_area,
             max_objects=MATCH_MAX_OBJECTS, want_labels=True, want_mask=name != "truth"))
 
-    def matched(self, name, iou):
-        """objects.match of a labelled prediction against the labelled truth at the thresholds `iou`."""
-        return self._once(("match", name, tuple(iou)), lambda: objects.match(
-            self.labelled(name).labels, self.labelled("truth").labels, iou=iou, max_objects=MATCH_MAX_OBJECTS))
+    def labelled(self, name):
+        """The objects the reports describe: labelled_all's, and with --object-value --min-value-drop, for a prediction, the ones
+        that pass (selected)."""
+        a = self.args
+        if getattr(a, "object_value", False) and getattr(a, "min_value_drop", None) is not None and name != "truth":
+            return self.selected(name)[0]
+        return self.labelled_all(name)
+
+    def valued(self, name):
+        """--object-value: objects.value of a labelled prediction on the evaluation frames (the stack "frames", uint8), asked of
+        self.infer, the critic in eval mode; made once."""
+        a = self.args
+        res = self.labelled_all(name)
+        return self._once(("value", name), lambda: objects.value(
+            self.infer, self.dev("frames").contiguous(), res.labels, res.kept, fill=a.object_value_fill, grow=a.object_value_grow,
+            max_objects=MATCH_MAX_OBJECTS))
+
+    def selected(self, name):
+        """--min-value-drop: (the Objects that pass, objects.select's unscored, the keep table) of a prediction; made once."""
+        def make():
+            res = self.labelled_all(name)
+            keep = objects.value_keep(self.valued(name).drop, res.kept, self.args.min_value_drop)
+            return (*objects.select(res, keep), keep)
+        return self._once(("select", name), make)
+
+    def matched(self, name, iou, every=False):
+        """objects.match of a labelled prediction against the labelled truth at the thresholds `iou`; every: of all its labelled
+        objects, also when --min-value-drop selects among them."""
+        pred = self.labelled_all(name) if every else self.labelled(name)
+        return self._once(("match", name, tuple(iou), pred is self.labelled_all(name)), lambda: objects.match(
+            pred.labels, self.labelled("truth").labels, iou=iou, max_objects=MATCH_MAX_OBJECTS))
 
 
 def _head(args, **more):
@@ -133,7 +162,7 @@ def crf_grid(args, st, tables):
 def _objects_block(st, name):
     """One block of eval_objects.json: the kept pixels of a labelled stack and the unfiltered stack scored against the truth with
     metrics.iou_counts / iou_curve (with --clean both are the cleaned stack's).  Only the counts come back."""
-    res, (src, thresh), truth = st.labelled(name), st.object_source(name), st.dev("truth")
+    res, (src, thresh), truth = st.labelled_all(name), st.object_source(name), st.dev("truth")
     inter, union = metrics.iou_counts(res.mask, truth).tolist()
     if thresh is None:
         inter0, union0 = metrics.iou_counts(src, truth).tolist()
@@ -142,29 +171,74 @@ def _objects_block(st, name):
     kept, found = res.kept.cpu().numpy(), res.found.cpu().numpy()
     return {"inter": inter, "union": union, "iou": metrics.ratio(inter, union),
             "unfiltered": {"inter": inter0, "union": union0, "iou": metrics.ratio(inter0, union0)},
-            "found": int(found.sum()), "kept": int(kept.sum()), "frames_without_objects": int(np.count_nonzero(kept == 0))}
+            "found": int(found.sum()), "kept": int(kept.sum()), "frames_without_objects": int(np.count_nonzero(kept == 0)),
+            **_value_blocks(st, name)}
+
+
+def _value_blocks(st, name):
+    """--object-value: a source block's "value" (objects.value_report without the threshold) and, with --min-value-drop, "selected":
+    the selected objects' count and their mask scored on the device with metrics.iou_counts."""
+    a = st.args
+    if not getattr(a, "object_value", False):
+        return {}
+    res, val, V = st.labelled_all(name), st.valued(name), a.min_value_drop
+    if V is None:
+        rep = objects.value_report(val, res.kept, a.object_value_fill, a.object_value_grow)
+        rep.pop("min_value_drop")
+        return {"value": rep}
+    sel, unscored, keep = st.selected(name)
+    rep = objects.value_report(val, res.kept, a.object_value_fill, a.object_value_grow, V, unscored=unscored)
+    rep.pop("min_value_drop")
+    inter, union = metrics.iou_counts(sel.mask, st.dev("truth")).tolist()
+    return {"value": rep, "selected": {"kept": int(sel.kept.sum()), "inter": inter, "union": union, "iou": metrics.ratio(inter, union)}}
 
 
 def objects_report(args, st):
-    """-objects: the masks as objects, labelled, filtered and scored on the GPU."""
+    """-objects: the masks as objects, labelled, filtered and scored on the GPU.  With --object-value every block gains "value" (and
+    with --min-value-drop "selected"), and the summary line the mean drop and the selected count."""
     report = _head(args)
     for name in st.names(("mask", "crf")):
         report[name] = _objects_block(st, name)
     report = _json_safe(report)
+
+    def valued(b):
+        if "value" not in b:
+            return ""
+        return f"; value drop mean {fmt(b['value']['drop']['mean'])}, selected {b['selected']['kept'] if 'selected' in b else b['value']['rows']}/{b['value']['rows']}"
     return report, f"\nOBJECTS conn={args.connectivity} min_area={args.min_area}: " + "; ".join(
-        f"{pre}iou {fmt(b['iou'])} (unfiltered {fmt(b['unfiltered']['iou'])}), kept {b['kept']}/found {b['found']} objects"
+        f"{pre}iou {fmt(b['iou'])} (unfiltered {fmt(b['unfiltered']['iou'])}), kept {b['kept']}/found {b['found']} objects{valued(b)}"
         for pre, b in _blocks(st, report))
+
+
+def _match_values(st, name, iou):
+    """--object-value with --match-iou: per threshold {"matched": {"n", "mean", "median"}, "spurious": {...}}, the value drops of the
+    scored predicted objects (all of them, before any selection) whose best truth object reaches / does not reach that IoU -- Matches.best
+    side 0, the compare the kernel makes, in integers; the statistics are host float64 (None for an empty side)."""
+    res = st.labelled_all(name)
+    best = st.matched(name, iou, every=True).best[:, 0].cpu().numpy().astype(np.int64)        # [n,K,4]: t, inter, area_p, area_t
+    drop, kept = st.valued(name).drop.cpu().numpy().astype(np.float64), res.kept.cpu().numpy()
+    scored = np.arange(drop.shape[1])[None] < np.clip(kept, 0, drop.shape[1])[:, None]
+    inter, union = best[..., 1], best[..., 2] + best[..., 3] - best[..., 1]
+    side = lambda d: {"n": int(d.size), "mean": float(d.mean()) if d.size else None, "median": float(np.median(d)) if d.size else None}
+    out = []
+    for m in objects.iou_milli(iou):
+        reach = (inter > 0) & (1000 * inter >= m * union)
+        out.append({"matched": side(drop[scored & reach]), "spurious": side(drop[scored & ~reach])})
+    return out
 
 
 def match_report(args, st):
     """--match-iou: those objects matched on the GPU to the truth's objects (objects.match).  Only the counts and the T sums of IoU
-    come back."""
+    come back.  With --object-value every threshold's entry gains "value" (_match_values)."""
     iou = objects.parse_match_iou(args.match_iou)
     report = _head(args, max_objects=MATCH_MAX_OBJECTS, iou=iou)
     for name in st.names(("mask", "crf")):
         m = st.matched(name, iou)
         report[name] = objects.match_report(m.pred_max, m.truth_max, m.matched_pred, m.matched_truth, objects.sum_iou(m.best, iou), iou,
                                             max_objects=MATCH_MAX_OBJECTS)
+        if getattr(args, "object_value", False):
+            for entry, v in zip(report[name]["per_iou"], _match_values(st, name, iou)):
+                entry["value"] = v
     report = _json_safe(report)
     first = lambda b: b["per_iou"][0]
     return report, f"\nMATCH conn={args.connectivity} min_area={args.min_area} iou>={iou[0]:g} ({len(iou)} thresholds): " + "; ".join(

@@ -482,8 +482,9 @@ class Handler:
         if getattr(args, "objects", False):     # (this build's flag) not a column: the by-position naming and the strip stay as they are
             process.objects_and_tracks(args, M, cols[-1] if args.crf else None, stems[:len(frames)], self.device, self.rank,
                                        low=np.ascontiguousarray(file_bytes, dtype=np.uint8)
-                                       if getattr(args, "track_motion", 0) or getattr(args, "track_reid", None) else None,
-                                       cleaned=cleaned)
+                                       if getattr(args, "track_motion", 0) or getattr(args, "track_reid", None)
+                                       or getattr(args, "object_value", False) else None,
+                                       cleaned=cleaned, infer=self._value_infer())
         if args.process_salience:       # main.py:1176-1197
             sal_maps, sal_hard = self._saliency_post(sal, preds, args.salience_thresh, args.salglobal)
             cols += [sal_maps, sal_hard]
@@ -535,7 +536,8 @@ class Handler:
         masks, crf_masks = [], []
         spec = getattr(args, "clean", None)              # --clean: per chunk the cleaned 64 x 64 masks and their counts, on the device
         cleaned, clean_counts, clean_head = [], [], None
-        lows = [] if getattr(args, "objects", False) and (getattr(args, "track_motion", 0) or getattr(args, "track_reid", None)) else None     # --track-motion / --track-reid: the shrunk frames
+        lows = [] if getattr(args, "objects", False) and (getattr(args, "track_motion", 0) or getattr(args, "track_reid", None)
+                                                          or getattr(args, "object_value", False)) else None     # --track-motion / --track-reid / --object-value: the shrunk frames
         unit = process.unit_table(self.device)
         for lo in range(0, len(files), step):
             print("segmentation in progress", round(lo / len(files), 2), end="%\r")
@@ -572,7 +574,8 @@ class Handler:
             process.write_clean(args, *clean_head, torch.cat(clean_counts), stems[:len(files)], self.rank)
         if getattr(args, "objects", False):
             process.objects_and_tracks(args, M, crf_mask, stems[:len(files)], self.device, self.rank,
-                                       low=torch.cat(lows) if lows is not None else None, cleaned=torch.cat(cleaned) if spec else None)
+                                       low=torch.cat(lows) if lows is not None else None, cleaned=torch.cat(cleaned) if spec else None,
+                                       infer=self._value_infer())
         write_json(f"{out_dir}/fit.json", {"frame_size": [H, W], "net_size": [fit.SIDE, fit.SIDE], "sigma_spatial": args.fit_spatial,
                                            "sigma_range": args.fit_range, "radius": fit.RADIUS, "frames": len(files)}, self.rank)
         return M
@@ -785,6 +788,14 @@ class Handler:
             **({"clean": {**clean.clean_report(clean_counts, spec), "frames": len(M)}} if spec else {})}, self.rank)
         return M
 
+    def _value_infer(self):
+        """--object-value: the critic as objects.value asks it, uint8 frames [b,64,64,3] -> values [b], always fp32 and eval mode (None
+        without the flag)."""
+        if not getattr(self.args, "object_value", False):
+            return None
+        eng = self._engine(2 * 32)
+        return lambda X: eng.infer(X, want_mask=False)[0]
+
     def _sweep_masks(self, X, to_device, progress, want_saliency=False, fp16=False, batchsize=128, train_mode=None):
         """The inference loop shared by -process and -eval (main.py:1130-1151, 900-953): eval-mode critic + masker over X in batches
         of 128, optionally the saliency baseline |d mean(pred) / d batch| summed over the colour channels.
@@ -940,6 +951,9 @@ class Handler:
         if getattr(args, "clean", None):        # (this build's flag) the masks cleaned on the GPU; the reports below then read those
             self.clean = report(evaluate.clean_report, "eval_clean.json")
         if getattr(args, "objects", False):     # (this build's flags) the masks as objects, matched to the truth's, followed through the frames
+            if getattr(args, "object_value", False):    # the critic is asked about every object, on the frames as bytes
+                st.host["frames"] = frames if frames.dtype == np.uint8 else (255 * frames).astype(np.uint8)
+                st.infer = self._value_infer()
             self.objects = report(evaluate.objects_report, "eval_objects.json")
             if getattr(args, "match_iou", ""):
                 self.matches = report(evaluate.match_report, "eval_match.json")

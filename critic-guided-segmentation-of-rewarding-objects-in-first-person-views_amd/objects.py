@@ -21,7 +21,11 @@ the mask of the link's tail object, carried there along the same vectors; ``fill
 ``fill(frames=)``, the frame range of a window (cgs_objects_track_fill_window).  ``appearance`` and ``reid`` (csrc/objects_reid.hip,
 ``--track-reid``) put an identity layer on top of the tracks: a 64-bin colour histogram per track, and tracks that do not overlap in
 time, lie at most ``window`` frames apart and have the same histogram are chained into one identity; ``identities`` gives every object
-its identity, and ``parse_track_reid`` / ``parse_track_reid_window`` / ``reid_report`` are the host helpers."""
+its identity, and ``parse_track_reid`` / ``parse_track_reid_window`` / ``reid_report`` are the host helpers.  ``ablate``, ``value`` and
+``select`` (csrc/objects_value.hip, ``--object-value``) ask the critic about every object: the frame is rebuilt on the device once per
+object with that object replaced, the critic's value of each rebuilt frame is taken from the frame's own, and the objects whose drop
+fails ``--min-value-drop`` are removed and the rest renumbered; ``value_chunks`` / ``value_keep`` / ``value_report`` and the three
+``parse_*`` of its flags are the host helpers."""
 import re
 from collections import namedtuple
 
@@ -47,6 +51,10 @@ REID_BINS, REID_MAX_WINDOW, REID_MAX_FRAMES = _lib.OBJ_REID_BINS, _lib.OBJ_REID_
 REID_SIM, REID_WINDOW, REID_MIN_AREA = 0.8, 64, 64          # --track-reid's defaults: judgements, not tuned values
 Appearance = namedtuple("Appearance", ["track_hist", "object_hist"])
 Reid = namedtuple("Reid", ["prev", "next", "sim", "identity", "signature", "n_identities", "n_links", "n_eligible", "longest"])
+VALUE_SIDE, VALUE_MAX_OBJECTS, VALUE_MAX_GROW = _lib.OBJ_VALUE_SIDE, _lib.OBJ_VALUE_MAX_OBJECTS, _lib.OBJ_VALUE_MAX_GROW
+VALUE_FILL, VALUE_GROW = "low", 0                         # --object-value's defaults: judgements, not tuned values
+Ablated = namedtuple("Ablated", ["images", "row_frame", "row_label", "offsets"])
+Values = namedtuple("Values", ["base", "drop", "fill_frame", "rows", "chunks"])
 Filled = namedtuple("Filled", ["labels", "track", "age", "table", "n_objects", "n_cells", "n_dropped", "n_vanished", "rgb"])
 
 
@@ -772,7 +780,270 @@ def fragments(truth_track, pred_track, best, iou):
     return torch.tensor(out, dtype=torch.int64, device=best.device)
 
 
+# ---------------------------------------------------------------------------------------------------------------- the value of an object
+def _value_stack(frames, labels, kept, max_objects, who, frames_range=None):
+    """The checks ``ablate`` and ``value`` share; returns (frames, labels, kept, n, K, (f0, f1)) ready for the kernel."""
+    for name, t, dtype in (("frames", frames, torch.uint8), ("labels", labels, torch.int32), ("kept", kept, torch.int32)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if labels.dim() != 3 or tuple(labels.shape[1:]) != (VALUE_SIDE, VALUE_SIDE) or tuple(frames.shape) != tuple(labels.shape) + (3,):
+        raise ValueError(f"labels must be [n,{VALUE_SIDE},{VALUE_SIDE}] and frames [n,{VALUE_SIDE},{VALUE_SIDE},3] (the critic takes only "
+                         f"that size), got {tuple(labels.shape)} and {tuple(frames.shape)}")
+    n = int(labels.shape[0])
+    if n < 1 or tuple(kept.shape) != (n,):
+        raise ValueError(f"at least one frame and kept [n], got {n} frames and kept {tuple(kept.shape)}")
+    max_objects = _as_int(max_objects, "max_objects")
+    if not 1 <= max_objects <= VALUE_MAX_OBJECTS:
+        raise ValueError(f"max_objects must be 1..{VALUE_MAX_OBJECTS}, got {max_objects}")
+    if not (frames.device == labels.device == kept.device):
+        raise ValueError(f"frames, labels and kept are on {frames.device}, {labels.device} and {kept.device}")
+    span = (0, n) if frames_range is None else _frame_range(frames_range, n)
+    if not torch.cuda.is_available() or not labels.is_cuda:
+        raise _lib.CgsError(f"objects.{who} runs on the GPU (cgs_objects_ablate); " + ("no GPU is visible" if not torch.cuda.is_available()
+                            else f"the tensors are on {labels.device}") + " and there is no CPU fallback")
+    return _aligned16(frames.contiguous()), labels.contiguous(), kept.contiguous(), n, max_objects, span
+
+
+def _aligned16(t):
+    return t if t.data_ptr() % 16 == 0 else t.clone()          # (a view at an odd byte offset: the kernel moves 16 bytes at a time)
+
+
+def _value_fill(fill, allow_low=False):
+    """``ablate``'s fill as (mode, R | G << 8 | B << 16, tensor or None, the JSON form); ValueError otherwise."""
+    if isinstance(fill, str):
+        if fill == "mean":
+            return 2, 0, None, "mean"
+        if fill == "low" and allow_low:
+            return None, 0, None, "low"
+        raise ValueError(f"fill {fill!r}: expected " + ('"low", ' if allow_low else "") + '"mean", (r, g, b) or a uint8 tensor [64,64,3]')
+    if isinstance(fill, torch.Tensor):
+        if fill.dtype != torch.uint8 or tuple(fill.shape) != (VALUE_SIDE, VALUE_SIDE, 3):
+            raise ValueError(f"a fill frame must be a uint8 tensor [{VALUE_SIDE},{VALUE_SIDE},3], got {fill.dtype} {tuple(fill.shape)}")
+        return 1, 0, fill, "frame"
+    try:
+        rgb = [_as_int(v, "fill colour") for v in fill]
+    except TypeError:
+        raise ValueError(f"fill {fill!r}: expected \"mean\", (r, g, b) or a uint8 tensor [64,64,3]") from None
+    if len(rgb) != 3 or not all(0 <= v <= 255 for v in rgb):
+        raise ValueError(f"fill colour {fill!r}: three whole numbers 0..255")
+    return 0, rgb[0] | rgb[1] << 8 | rgb[2] << 16, None, rgb
+
+
+def _value_grow(grow):
+    grow = _as_int(grow, "grow")
+    if not 0 <= grow <= VALUE_MAX_GROW:
+        raise ValueError(f"grow must be 0..{VALUE_MAX_GROW}, got {grow}")
+    return grow
+
+
+def ablate(frames, labels, kept, fill="mean", grow=0, max_objects=64, frames_range=None):
+    """The "this frame without object k" images of cgs_objects_ablate (its header comment in include/cgs_hip.h is the rule).  frames:
+    uint8 device tensor [n,64,64,3]; labels: int32 [n,64,64] as ``label`` gives them; kept: int32 [n] (``Objects.kept``), on one device.
+    The rows of frame f are its objects k = 1 .. min(kept[f], max_objects) in that order, frame by frame; row (f, k) is frame f with
+    the fill written over every cell within `grow` cells (0..4, a clipped square) of a cell labelled k, other objects' cells included,
+    and the frame's own bytes elsewhere.  fill: "mean" (per frame the rounded mean colour of its label-0 cells, of all cells when it has
+    none, computed by the kernel), a colour (r, g, b), or one uint8 tensor [64,64,3] on the same device for all rows.  A label above
+    max_objects gets no row and matches no k.  frames_range: None or (f0, f1), 0 <= f0 <= f1 <= n: only the rows of those frames;
+    the concatenation over any split of 0..n is the whole-stack result bit for bit.
+    Returns Ablated(images uint8 [rows,64,64,3], row_frame int32 [rows], row_label int32 [rows], offsets int32 [n + 1]: the exclusive
+    prefix sum of the row counts over the WHOLE stack, so a range's rows are offsets[f0] .. offsets[f1] - 1).  The row count comes to
+    the host (one synchronisation); without rows nothing is launched.  No CPU path: raises CgsError without a GPU."""
+    mode, rgb, frame, _ = _value_fill(fill)
+    grow = _value_grow(grow)
+    frames, labels, kept, n, K, (f0, f1) = _value_stack(frames, labels, kept, max_objects, "ablate", frames_range)
+    dev = labels.device
+    if frame is not None:
+        if frame.device != dev:
+            raise ValueError(f"the fill frame is on {frame.device}, the frames on {dev}")
+        frame = _aligned16(frame.contiguous())
+    with torch.cuda.device(dev):
+        offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        offsets[1:] = torch.cumsum(kept.clamp(0, K), 0)
+        lo, hi = (int(v) for v in offsets[[f0, f1]].tolist())
+        rows = hi - lo
+        images = torch.empty((rows, VALUE_SIDE, VALUE_SIDE, 3), dtype=torch.uint8, device=dev)
+        row_frame = torch.empty(rows, dtype=torch.int32, device=dev)
+        row_label = torch.empty(rows, dtype=torch.int32, device=dev)
+        if rows:
+            _lib.call("cgs_objects_ablate", frames.data_ptr(), labels.data_ptr(), offsets.data_ptr(), n, f0, f1, K, grow, mode, rgb,
+                      frame.data_ptr() if frame is not None else None, 0, rows, images.data_ptr(), row_frame.data_ptr(),
+                      row_label.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return Ablated(images, row_frame, row_label, offsets)
+
+
+def value_chunks(rows, chunk_rows):
+    """``value``'s ranges: the frames cut greedily into consecutive ranges whose row total is at most chunk_rows (a frame joins the
+    range while the total still fits, so a frame without rows always does); a range without rows is left out.  rows: the row count of
+    every frame, each at most chunk_rows.  Returns [(f0, f1, rows)]."""
+    out, f0, total = [], 0, 0
+    for f, r in enumerate(int(v) for v in rows):
+        if r > chunk_rows:
+            raise ValueError(f"frame {f} has {r} rows, chunk_rows is {chunk_rows}")
+        if total + r > chunk_rows:
+            out.append((f0, f, total))
+            f0, total = f, 0
+        total += r
+    out.append((f0, len(rows), total))
+    return [c for c in out if c[2]]
+
+
+def value(infer, frames, labels, kept, fill="low", grow=0, max_objects=64, chunk_rows=2048):
+    """How far the critic's value of a frame falls when one object alone is taken out of it: the training rule replaced = A (1 - Z) +
+    Z B asked once per object with a hard Z.  infer: a callable X_u8 [b,64,64,3] -> pred [b] float32 on the frames' device (the
+    handler passes ``lambda X: eng.infer(X, want_mask=False)[0]``: fp32, eval mode); frames, labels, kept, grow, max_objects as
+    ``ablate`` takes them; fill as there, or "low": the frame of smallest base value, the rule's B, one for the whole stack.
+    1. base = infer over the frames in consecutive chunks of at most chunk_rows frames.
+    2. "low" is the frame at int(np.argmin(base.cpu().numpy())): the first index on ties, taken on the host.
+    3. The frames are cut into ranges of at most chunk_rows rows (``value_chunks``; chunk_rows >= 64, so a frame always fits); every
+       range is one ``ablate`` and one infer over its rows.
+    4. drop[f, k - 1] = base[f] - pred(row (f, k)), one float32 subtraction; entries without a row are 0.
+    Returns Values(base float32 [n], drop float32 [n,max_objects], fill_frame: the index "low" chose, else None, rows: the row total,
+    chunks: [(f0, f1, rows)] -- the chunk composition is part of the contract, a caller can repeat it).  A frame that is its own fill
+    frame is rebuilt unchanged, so its objects have drop 0 exactly, by construction and not by measurement.
+    Limits: one replacement at a time (no Shapley value: two objects that are each redundant with the other both score low); "mean"
+    and a colour lie outside what the critic was trained on; one critic forward per object.  No CPU path."""
+    if not callable(infer):
+        raise ValueError(f"infer must be callable, got {type(infer).__name__}")
+    mode, _, frame, _ = _value_fill(fill, allow_low=True)
+    grow = _value_grow(grow)
+    chunk_rows = _as_int(chunk_rows, "chunk_rows")
+    if chunk_rows < VALUE_MAX_OBJECTS:
+        raise ValueError(f"chunk_rows must be at least {VALUE_MAX_OBJECTS} (one frame's rows always fit), got {chunk_rows}")
+    frames, labels, kept, n, K, _ = _value_stack(frames, labels, kept, max_objects, "value")
+    if frame is not None and frame.device != labels.device:
+        raise ValueError(f"the fill frame is on {frame.device}, the frames on {labels.device}")
+    dev = labels.device
+    with torch.cuda.device(dev):
+        base = torch.cat([infer(frames[lo:lo + chunk_rows]).reshape(-1).to(torch.float32) for lo in range(0, n, chunk_rows)])
+        fill_frame = None
+        if mode is None:
+            fill_frame = int(np.argmin(base.cpu().numpy()))
+            fill = frames[fill_frame]
+        counts = kept.clamp(0, K).cpu().numpy()
+        chunks = value_chunks(counts, chunk_rows)
+        drop = torch.zeros((n, K), dtype=torch.float32, device=dev)
+        for f0, f1, rows in chunks:
+            ab = ablate(frames, labels, kept, fill=fill, grow=grow, max_objects=K, frames_range=(f0, f1))
+            pred = infer(ab.images).reshape(-1).to(torch.float32)
+            if int(pred.shape[0]) != rows:
+                raise ValueError(f"infer returned {int(pred.shape[0])} values for {rows} images")
+            f, k = ab.row_frame.to(torch.int64), ab.row_label.to(torch.int64) - 1
+            drop[f, k] = base[f] - pred
+    return Values(base, drop, fill_frame, int(counts.sum()), chunks)
+
+
+def select(res, keep):
+    """The objects that pass: res: ``label``'s Objects with labels and a table of at least K rows; keep: bool or uint8 device tensor
+    [n,K], K <= 64.  Old label k of frame f becomes 1 + the number of kept labels below it when k <= min(kept[f], K) and keep[f, k - 1],
+    else 0 -- every label above K too: an object that was never scored is dropped (cgs_objects_select).  The order is kept, so the new
+    numbers are still the raster order of the first pixel.  Returns (Objects(labels, mask bool, kept, found: passed through, table
+    [n,K,8]: the kept rows in order, zero rows behind them), unscored int32 [n]: the objects above K that were dropped).  The reports
+    and ``track`` take the result as they take ``label``'s.  No CPU path: raises CgsError without a GPU."""
+    if not isinstance(res, Objects) or not isinstance(res.labels, torch.Tensor) or not isinstance(res.table, torch.Tensor):
+        raise ValueError("res must be the result of objects.label with labels (want_labels=True) and its table")
+    if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8) or keep.dim() != 2:
+        raise ValueError("keep must be a bool or uint8 tensor [n,K], got "
+                         + (f"{keep.dtype} {tuple(keep.shape)}" if isinstance(keep, torch.Tensor) else type(keep).__name__))
+    labels, table, kept = res.labels, res.table, res.kept
+    if labels.dtype != torch.int32 or labels.dim() != 3 or table.dtype != torch.int32 or kept.dtype != torch.int32:
+        raise ValueError("res.labels must be int32 [n,h,w], res.table and res.kept int32")
+    n, h, w = (int(s) for s in labels.shape)
+    K = int(keep.shape[1])
+    if n < 1 or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE) or not 1 <= K <= VALUE_MAX_OBJECTS or int(keep.shape[0]) != n:
+        raise ValueError(f"labels {tuple(labels.shape)} and keep {tuple(keep.shape)}: n frames of 1..{MAX_SIDE} x 1..{MAX_SIDE} pixels and "
+                         f"keep [n,K] with K in 1..{VALUE_MAX_OBJECTS}")
+    if table.dim() != 3 or int(table.shape[0]) != n or int(table.shape[1]) < K or int(table.shape[2]) != len(FIELDS) or tuple(kept.shape) != (n,):
+        raise ValueError(f"res.table {tuple(table.shape)} must be [{n},>={K},{len(FIELDS)}] and res.kept [{n}]")
+    if not torch.cuda.is_available() or not labels.is_cuda:
+        raise _lib.CgsError("objects.select runs on the GPU (cgs_objects_select); " + ("no GPU is visible" if not torch.cuda.is_available()
+                            else f"the tensors are on {labels.device}") + " and there is no CPU fallback")
+    dev = labels.device
+    if not (table.device == kept.device == keep.device == dev):
+        raise ValueError("res.labels, res.table, res.kept and keep are on different devices")
+    labels, table, kept = labels.contiguous(), table[:, :K].contiguous(), kept.contiguous()
+    keep = keep.contiguous()
+    keep = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+    with torch.cuda.device(dev):
+        out = torch.empty_like(labels)
+        out_table = torch.empty_like(table)
+        out_kept = torch.empty_like(kept)
+        mask = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+        unscored = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.call("cgs_objects_select", labels.data_ptr(), table.data_ptr(), kept.data_ptr(), keep.data_ptr(), n, h, w, K, out.data_ptr(),
+                  out_table.data_ptr(), out_kept.data_ptr(), mask.data_ptr(), unscored.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return Objects(out, mask.view(torch.bool), out_kept, res.found, out_table), unscored
+
+
 # ---------------------------------------------------------------------------------------------------------------- host helpers
+def parse_object_value_fill(s, flag="--object-value-fill"):
+    """``--object-value-fill``: "low", "mean" or a colour "R,G,B" of whole numbers 0..255.  Returns "low", "mean" or (r, g, b)."""
+    s = str(s).strip()
+    if s in ("low", "mean"):
+        return s
+    try:
+        rgb = tuple(int(p.strip()) for p in s.split(","))
+    except ValueError:
+        raise ValueError(f"{flag} {s!r}: expected low, mean or R,G,B") from None
+    if len(rgb) != 3 or not all(0 <= v <= 255 for v in rgb):
+        raise ValueError(f"{flag} {s!r}: expected low, mean or R,G,B with three whole numbers 0..255")
+    return rgb
+
+
+def parse_object_value_grow(s, flag="--object-value-grow"):
+    """``--object-value-grow``: a whole number 0..4, the cells around an object that are replaced with it.  Returns the int."""
+    try:
+        v = int(str(s).strip())
+    except ValueError:
+        raise ValueError(f"{flag} {s!r}: expected a whole number 0..{VALUE_MAX_GROW}") from None
+    if not 0 <= v <= VALUE_MAX_GROW:
+        raise ValueError(f"{flag} {v}: expected a whole number 0..{VALUE_MAX_GROW}")
+    return v
+
+
+def parse_min_value_drop(s, flag="--min-value-drop"):
+    """``--min-value-drop``: one finite number (it may be negative: a drop is a difference).  Returns the float."""
+    try:
+        v = float(str(s).strip())
+    except ValueError:
+        raise ValueError(f"{flag} {s!r}: expected one finite number") from None
+    if v != v or abs(v) == float("inf"):
+        raise ValueError(f"{flag} {s!r}: expected one finite number")
+    return v
+
+
+def value_keep(drop, kept, min_drop):
+    """The keep table of ``select`` for a threshold: drop >= min_drop compared in float32 (a NaN is not kept), for the objects that
+    have a row (k <= min(kept, K)).  drop float32 [n,K] and kept int32 [n] on one device; bool [n,K] there."""
+    K = int(drop.shape[1])
+    has_row = torch.arange(K, device=drop.device)[None] < kept.clamp(0, K)[:, None]
+    return (drop >= torch.tensor(min_drop, dtype=torch.float32, device=drop.device)) & has_row
+
+
+def value_report(values, kept, fill, grow, min_drop=None, keep=None, unscored=None, stems=None):
+    """The "object_value" header of objects.json / the "value" block of eval_objects.json from ``value``'s result.  kept: the frames'
+    object counts (tensor or array); fill: the flag's value ("low", "mean" or (r, g, b)); keep: ``value_keep``'s table with a
+    threshold; unscored: the objects numbered above K, ``select``'s per-frame count or, without a selection, max(kept - K, 0); stems:
+    the frames' names, then "fill_frame" is a name.  {"fill", "fill_frame", "grow", "min_value_drop", "rows", "unscored", "base_mean",
+    "drop": {"mean", "min", "max", "negative"} over the scored objects in float64 (None without any), and with keep "selected_objects"}."""
+    base, drop, kept = _host(values.base).astype(np.float64), _host(values.drop).astype(np.float64), _host(kept).reshape(-1).astype(np.int64)
+    K = drop.shape[1]
+    scored = np.arange(K)[None] < np.clip(kept, 0, K)[:, None]
+    d = drop[scored]
+    ff = values.fill_frame
+    rep = {"fill": list(fill) if isinstance(fill, (tuple, list)) else fill,
+           "fill_frame": None if ff is None else (stems[ff] if stems is not None else int(ff)), "grow": int(grow),
+           "min_value_drop": None if min_drop is None else float(min_drop), "rows": int(values.rows),
+           "unscored": int(np.maximum(kept - K, 0).sum()) if unscored is None else int(_host(unscored).sum()),
+           "base_mean": float(base.mean()) if base.size else None,
+           "drop": {"mean": float(d.mean()) if d.size else None, "min": float(d.min()) if d.size else None,
+                    "max": float(d.max()) if d.size else None, "negative": int(np.count_nonzero(d < 0))}}
+    if keep is not None:
+        rep["selected_objects"] = int(np.count_nonzero(_host(keep) & scored))
+    return rep
+
+
 def parse_track_gap(s, flag="--track-gap"):
     """``--track-gap`` / ``--overlay-gap``: a whole number 0..8 (objects.TRACK_MAX_GAP).  Returns the int; ValueError otherwise."""
     try:

@@ -1,7 +1,8 @@
 """What the three ``-process`` paths of handler.Handler share (segment, _segment_fit, _segment_video): the folder listing, the chunk
 size, how a shrunk uint8 frame is fed to the network, the PNG columns with their by-position names, and ``-objects`` /
 ``--track-iou`` on the 64 x 64 masks (objects.json, tracks.json and their PNGs; ``video_reports`` writes the two reports of
-``--source-video --overlay-tracks`` without PNGs), and ``--clean`` (``clean_source``, ``write_clean``: clean.json and the
+``--source-video --overlay-tracks`` without PNGs; with ``--object-value`` the objects are scored by the critic and, with
+``--min-value-drop``, selected before they are reported and tracked: {stem}-valued-mask.png), and ``--clean`` (``clean_source``, ``write_clean``: clean.json and the
 {stem}-clean-mask.png files).  Under data parallelism every rank makes the GPU
 calls and rank 0 writes."""
 import os
@@ -103,17 +104,28 @@ def write_clean_pngs(out_dir, stems, masks):
         Image.fromarray(np.repeat(grey[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-clean-mask.png")
 
 
-def objects_and_tracks(args, M, crf_mask, stems, device, rank, low=None, cleaned=None):
+def objects_and_tracks(args, M, crf_mask, stems, device, rank, low=None, cleaned=None, infer=None):
     """-process -objects [--track-iou]: the stack of binary_source labelled on the GPU once (objects.py; labels, mask and counts do not
     depend on the table's rows), then reported as objects and, if asked for, as tracks.  low: with --track-motion the uint8 frames
     [n,64,64,3] the masks were made from (tensor or array, in the order of stems); --track-reid needs them too.  cleaned: with --clean the cleaned bool stack on the
-    device, which is then the one described; the reports' header gains "clean"."""
+    device, which is then the one described; the reports' header gains "clean".  infer: with --object-value the critic, uint8 frames
+    [b,64,64,3] -> values [b] in eval mode; low is then needed too.  The objects 1..64 of every frame are scored (objects.value), and
+    with --min-value-drop the ones that pass are what the mask PNGs and the tracks describe (objects.select)."""
     want_tracks = bool(getattr(args, "track_iou", ""))
+    want_value = bool(getattr(args, "object_value", False))
     source, thresh, stack, kw = binary_source(args, M, crf_mask, device, cleaned)
-    res = objects.label(stack, max_objects=PROCESS_MAX_OBJECTS, want_labels=want_tracks, want_mask=True, **kw)
+    res = objects.label(stack, max_objects=PROCESS_MAX_OBJECTS, want_labels=want_tracks or want_value, want_mask=True, **kw)
     head = {"source": source, "threshold": thresh, "connectivity": args.connectivity, "min_area": args.min_area,
             **({"clean": dict(args.clean)} if cleaned is not None else {})}
-    _objects(args, res, head, stems, M.shape[-1], rank)
+    valued = drops = None
+    if want_value:
+        if low is None or infer is None:
+            raise ValueError("--object-value needs the 64 x 64 frames of the masks and the critic")
+        valued = _valued(args, res, torch.as_tensor(low).to(device), infer, stems)
+        res_all, res, drops = res, valued["objects"], valued["drops"]
+        _objects(args, res_all, head, stems, M.shape[-1], rank, valued=valued)
+    else:
+        _objects(args, res, head, stems, M.shape[-1], rank)
     if want_tracks:
         search = int(getattr(args, "track_motion", 0) or 0)
         reid = getattr(args, "track_reid", None)
@@ -121,7 +133,34 @@ def objects_and_tracks(args, M, crf_mask, stems, device, rank, low=None, cleaned
             raise ValueError("--track-motion and --track-reid need the 64 x 64 frames of the masks")
         _tracks(args, res, head, stems, rank, low=torch.as_tensor(low).to(device) if search or reid else None, search=search,
                 fill=bool(getattr(args, "track_fill", False)),
-                reid=(reid, args.track_reid_window, args.track_reid_area) if reid else None)
+                reid=(reid, args.track_reid_window, args.track_reid_area) if reid else None, drops=drops)
+
+
+def _valued(args, res, frames, infer, stems):
+    """--object-value: objects.value of the labelled stack and, with --min-value-drop, objects.select.  Returns {"head": the
+    "object_value" header, "base" [n] and "drop" [n,64] (host), "keep" bool [n,64] and "label_selected" int [n,64] (host, None without
+    a threshold), "mask": the selected kept-pixel mask (host, None likewise), "objects": the Objects everything downstream describes
+    (the selected ones with a threshold, else res), "drops": float64 [n,64], the drop of every object of "objects" by ITS number}."""
+    K = MATCH_MAX_OBJECTS
+    fill, grow, V = args.object_value_fill, args.object_value_grow, args.min_value_drop
+    val = objects.value(infer, frames, res.labels, res.kept, fill=fill, grow=grow, max_objects=K)
+    drop = val.drop.cpu().numpy()
+    out = {"base": val.base.cpu().numpy(), "drop": drop, "keep": None, "label_selected": None, "mask": None, "objects": res,
+           "drops": drop.astype(np.float64)}
+    keep = unscored = None
+    if V is not None:
+        keep = objects.value_keep(val.drop, res.kept, V)
+        sel, unscored = objects.select(res, keep)
+        keep = keep.cpu().numpy()
+        number = np.where(keep, np.cumsum(keep, axis=1), 0)
+        drops = np.zeros((len(drop), K), dtype=np.float64)
+        for f, k in zip(*np.nonzero(keep)):
+            drops[f, number[f, k] - 1] = drop[f, k]
+        out.update(keep=keep, label_selected=number, mask=sel.mask.cpu().numpy(), objects=sel, drops=drops)
+    out["head"] = objects.value_report(val, res.kept, fill, grow, V, unscored=unscored, stems=stems)
+    for key in ("base_mean", "drop"):                                  # (the summary figures are -eval's)
+        out["head"].pop(key)
+    return out
 
 
 def video_reports(args, M, stem, device, rank, bwd=None):
@@ -145,26 +184,45 @@ def video_reports(args, M, stem, device, rank, bwd=None):
     return list(names)
 
 
-def _objects(args, res, head, stems, width, rank, png=True, name="objects.json"):
+def _objects(args, res, head, stems, width, rank, png=True, name="objects.json", valued=None):
     """Rank 0 writes {R}/objects.json and per frame {R}/{stem}-objects-mask.png, the pixels of the kept objects as 0 / 255 grey RGB
-    (png=False: the report alone, as {R}/{name})."""
+    (png=False: the report alone, as {R}/{name}).  valued (--object-value, _valued's dict): the header gains "object_value", every
+    frame "value" (the critic's value of the frame) and every object "value_drop" (None for an object numbered above 64, which is never
+    scored); with --min-value-drop every object also "selected" and "label_selected" (its new number, 0 when dropped), the mask PNG
+    shows the selected objects and {stem}-valued-mask.png is written from the same mask."""
     from PIL import Image
     if rank != 0:
         return
     kept, found = res.kept.cpu().numpy(), res.found.cpu().numpy()
     rows = objects.table_rows(res.table, kept, width=width)
+    frame_more = lambda i: {}
+    if valued is not None:
+        drop, keep, number = valued["drop"], valued["keep"], valued["label_selected"]
+        head = {**head, "object_value": valued["head"]}
+        frame_more = lambda i: {"value": float(valued["base"][i])}
+        for i, frame in enumerate(rows):
+            for row in frame:
+                k = row["label"] - 1
+                scored = k < drop.shape[1]
+                row["value_drop"] = float(drop[i, k]) if scored else None
+                if keep is not None:
+                    row.update(selected=bool(scored and keep[i, k]), label_selected=int(number[i, k]) if scored else 0)
     out_dir = args.mask_output_imgs
     write_json(f"{out_dir}/{name}", {**head, "max_objects": PROCESS_MAX_OBJECTS, "frames": {
-        stem: {"found": int(found[i]), "kept": int(kept[i]), "objects": rows[i]} for i, stem in enumerate(stems)}})
+        stem: {"found": int(found[i]), "kept": int(kept[i]), **frame_more(i), "objects": rows[i]} for i, stem in enumerate(stems)}})
     if not png:
         return
-    mask = res.mask.cpu().numpy()
+    selected = valued is not None and valued["mask"] is not None
+    mask = valued["mask"] if selected else res.mask.cpu().numpy()
     for i, stem in enumerate(stems):
-        Image.fromarray(np.repeat((mask[i] * np.uint8(255))[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-objects-mask.png")
+        grey = Image.fromarray(np.repeat((mask[i] * np.uint8(255))[:, :, None], 3, axis=2))
+        grey.save(f"{out_dir}/{stem}-objects-mask.png")
+        if selected:
+            grey.save(f"{out_dir}/{stem}-valued-mask.png")
 
 
 def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None, gap=None, low=None, bwd=None, search=0, fill=False,
-            reid=None):
+            reid=None, drops=None):
     """The objects objects.json describes followed through the frames in natural order of their names on the GPU (objects.track);
     labels above 64 are untracked.  Rank 0 writes {R}/tracks.json and per frame {R}/{stem}-tracks-mask.png, a colour per track
     (png=False: the report alone, as {R}/{name}; iou, gap: the link threshold and the gap when they are not --track-iou's and
@@ -179,7 +237,9 @@ def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None
     new objects, counted on the device.  reid (--track-reid: similarity, window, area): the tracks are chained into identities by the
     colour histograms of low (objects.appearance, objects.reid); the report gains "track_reid" (objects.reid_report), per track
     "identity", "reid_prev" and "reid_sim", and the list "identities", and {stem}-identities-mask.png is painted with
-    objects.track_colours of every pixel's identity, from the filled labels with fill.  Nothing else changes."""
+    objects.track_colours of every pixel's identity, from the filled labels with fill.  Nothing else changes.  drops (--object-value):
+    float64 [n,64] in the order of stems, the value drop of every object of res by its number; every track row then gains
+    "value_drop_mean" and "value_drop_max" over its segmented objects."""
     from PIL import Image
     K, iou = MATCH_MAX_OBJECTS, objects.parse_track_iou(args.track_iou) if iou is None else iou
     gap = int(getattr(args, "track_gap", 0) or 0) if gap is None else gap
@@ -221,6 +281,13 @@ def _tracks(args, res, head, stems, rank, png=True, name="tracks.json", iou=None
               "tracks": [{"track": r["track"], "first": names[r["first_frame"]], "last": names[last(r)],
                           "length": r["length"], "area_sum": r["area_sum"], "area_min": r["area_min"], "area_max": r["area_max"],
                           "link_iou": r["link_iou"], **({"bridges": r["bridges"], "missed": r["missed"]} if gap else {})} for r in rows]}
+    if drops is not None:                                            # host float64, over the segmented objects of every track
+        members = {}
+        for j, l in zip(*np.nonzero(trk)):
+            members.setdefault(int(trk[j, l]), []).append(float(drops[order[j], l]))
+        for row in report["tracks"]:
+            d = np.array(members[row["track"]], dtype=np.float64)
+            row.update(value_drop_mean=float(d.mean()), value_drop_max=float(d.max()))
     if fill:
         age, ftrk, area, per_track = fl.age.cpu().numpy(), fl.track.cpu().numpy(), fl.table[:, :, 0].cpu().numpy(), per_track.cpu().numpy()
         for j, stem in enumerate(names):

@@ -1117,6 +1117,45 @@ int cgs_objects_reid(const int32_t* track_hist, const int32_t* tracks, const int
                      int32_t* reid_sim, int32_t* identity, int32_t* totals, int16_t* signature, void* scratch, int64_t scratch_bytes,
                      cgs_stream_t stream);
 
+/* cgs_objects_ablate, cgs_objects_select (csrc/objects_value.hip): the value of an object, -objects --object-value.  The critic is asked
+ * once per object how far its value of the frame falls when that object alone is replaced -- the training rule's A (1 - Z) + Z B with a
+ * hard Z -- and the objects that fail a threshold are dropped and the rest renumbered.  This comment is the specification.
+ *   frames     uint8 [n][64][64][3]; labels int32 [n][64][64] as cgs_objects_label wrote them; K = max_objects <= 64.
+ *   rows       offsets int32 [n + 1], non-decreasing from 0: frame f owns the rows offsets[f] .. offsets[f + 1] - 1 of the whole stack,
+ *              row offsets[f] + k - 1 is its object k, k = 1 .. min(offsets[f + 1] - offsets[f], K).  (The caller makes it as the
+ *              exclusive prefix sum of min(kept[f], K).)
+ *   ablated    R = grow in 0..4.  A_k is the set of cells (y, x) for which some cell (y', x') inside the frame has |y - y'| <= R,
+ *              |x - x'| <= R and labels[f][y'][x'] == k: cells of other objects within R of object k are replaced too; a label above K
+ *              matches no k.
+ *   row        out[y][x][:] = F_f[y][x][:] on A_k and frames[f][y][x][:] elsewhere.
+ *   fill       fill_mode 0: F_f is the constant colour fill_rgb = R | G << 8 | B << 16.  1: F_f = the uint8 [64][64][3] frame at fill + f
+ *              fill_stride, fill_stride 0 (one frame for all rows) or 12288.  2: F_f is the constant colour c_ch = (2 S_ch + N) / (2 N)
+ *              in integer division, S_ch and N the channel sum and the count over the cells of frame f whose label is 0 (any other
+ *              label, those above K included, is not background), and over all 4096 cells when there are none.
+ * cgs_objects_ablate: the rows of the frames f0 <= f < f1, one launch, one workgroup per frame.
+ *   out        uint8 [rows][64][64][3], row_frame, row_label int32 [rows], rows = offsets[f1] - offsets[f0]: row r of the range is row
+ *              offsets[f0] + r of the stack; row_frame holds f, row_label k.  A row index outside 0 .. rows - 1 (offsets that do not
+ *              fit) is not written, and no read is out of range for any content of labels or offsets.  All offsets are 64-bit.
+ * frames, labels, offsets and the outputs not NULL, frames, fill and out 16-byte aligned, int32 pointers 4-byte aligned, n >= 1, 0 <= f0 <
+ * f1 <= n, rows >= 1 (an empty range or a range without rows is the caller's to skip: nothing is ever launched with an empty grid),
+ * max_objects >= 1, grow >= 0, fill_mode in 0..2, fill given exactly with mode 1, fill_rgb < 2^24, else CGS_ERR_BADARG (nothing is
+ * launched); then max_objects <= 64 and grow <= 4, else CGS_ERR_UNSUPPORTED.  Integer and selection only: bit-reproducible.
+ * cgs_objects_select: table int32 [n][K][8] (cgs_objects_label's rows), kept int32 [n], keep uint8 [n][K]; frames of h x w <= 64 x 64.
+ *   Old label k becomes 1 + #{j < k : keep[f][j - 1] != 0} when k <= min(kept[f], K) and keep[f][k - 1] != 0, and 0 otherwise -- every
+ *   label above K included: an object that was never scored is dropped.  The order is kept, so the new numbers are still the raster
+ *   order of the first pixel.
+ *   out_labels int32 [n][h][w]; out_table int32 [n][K][8]: the kept rows in order, zero rows behind them; out_kept int32 [n];
+ *   mask uint8 [n][h][w] = out_labels != 0; unscored int32 [n] = max(kept[f] - K, 0), the objects numbered above K that were dropped.
+ * One launch, one workgroup per frame.  Pointers not NULL and aligned, n, h, w, max_objects >= 1, else CGS_ERR_BADARG; then h, w <= 64
+ * and max_objects <= 64, else CGS_ERR_UNSUPPORTED.                                                                                       */
+enum { CGS_OBJ_VALUE_MAX_OBJECTS = 64, CGS_OBJ_VALUE_MAX_GROW = 4 };
+int cgs_objects_ablate(const uint8_t* frames, const int32_t* labels, const int32_t* offsets, int32_t n, int32_t f0, int32_t f1,
+                       int32_t max_objects, int32_t grow, int32_t fill_mode, uint32_t fill_rgb, const uint8_t* fill, int64_t fill_stride,
+                       int64_t rows, uint8_t* out, int32_t* row_frame, int32_t* row_label, cgs_stream_t stream);
+int cgs_objects_select(const int32_t* labels, const int32_t* table, const int32_t* kept, const uint8_t* keep, int32_t n, int32_t h,
+                       int32_t w, int32_t max_objects, int32_t* out_labels, int32_t* out_table, int32_t* out_kept, uint8_t* mask,
+                       int32_t* unscored, cgs_stream_t stream);
+
 /* ---- the saliency baseline over a threshold grid (csrc/saliency.hip; Handler._saliency_post, main.py:976-1003; this build's own
  * -eval -salience --salience-grid) -----------------------------------------------------------------------------------------------------
  * The baseline's whole post-processing for T thresholds at once, each threshold with its own normaliser as the host form has it.  A
