@@ -74,6 +74,9 @@ FIT_SIDE, FIT_MAX_SIDE, FIT_RADIUS, FIT_MAP_F32, FIT_MAP_U8 = 64, 4096, 2, 0, 1 
 TEMPORAL_SIDE, TEMPORAL_MAX_RADIUS = 64, 8                                      # cgs_temporal_smooth (include/cgs_hip.h)
 TEMPORAL_BLOCK, TEMPORAL_MAX_SEARCH = 8, 4                                      # cgs_temporal_flow / cgs_temporal_smooth_mc (include/cgs_hip.h)
 OVERLAY_ONLY, OVERLAY_SIDE, OVERLAY_TRIPLE, OVERLAY_MAX_OUTLINE, OVERLAY_NONTEMPORAL = 1, 2, 3, 4, 1       # cgs_overlay_compose (include/cgs_hip.h)
+CUT_MAX_SIDE, CUT_FIELDS, CUT_TABLE, CUT_LOG_TABLE, CUT_MAX_ITERS = 64, 8, 1024, 4096 + 512 + 1, 8                              # cgs_graph_cut (include/cgs_hip.h)
+CUT_SCALE, CUT_MAX_LAMBDA, CUT_SWEEPS, CUT_MAX_ROUNDS = 16, 100, 16, 1 << 16
+CUT_EMPTY, CUT_EARLY, CUT_NOT_CONVERGED = 1, 2, 4
 OVERLAY_MAX_TRACK_OBJECTS, OVERLAY_MAX_BOXES, OVERLAY_FONT_GLYPHS, OVERLAY_FONT_ROWS = 64, 4, 10, 7                    # cgs_overlay_compose_tracks (include/cgs_hip.h)
 
 
@@ -245,6 +248,8 @@ SIGNATURES = {
     "cgs_overlay_compose_tracks_carried": (i32, [vp] * 8 + [i32] * 12 + [vp, vp]),
     "cgs_temporal_flow": (i32, [vp, i32, i32, vp, vp, vp]),
     "cgs_temporal_smooth_mc": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
+    "cgs_graph_cut": (i32, [vp, vp, i32, f32, f32, f32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "cgs_graph_cut_sweeps": (i32, [vp, vp, i32, f32, f32, f32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "cgs_build_arch": (C.c_char_p, []),
     "cgs_abi_version": (i32, []),
 }

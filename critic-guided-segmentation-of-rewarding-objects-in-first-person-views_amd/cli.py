@@ -10,7 +10,8 @@
 
 Every flag of the reference parses (same names, defaults and the ``type=bool`` quirk: ``-cload False`` is
 still True, as in the reference); flags whose code path is outside this build raise NotImplementedError
-when reached instead of being silently ignored."""
+when reached instead of being silently ignored.  ``-grabcut`` is the one flag the reference itself declares and never reads (main.py:1485):
+it is parsed and does nothing here too; the refinement it names is this build's ``--graph-cut SPEC`` (graphcut.py)."""
 import argparse
 
 
@@ -116,6 +117,14 @@ def build_parser():
     # --boundary-tol then describe the cleaned masks, and the overlay video draws them.  check_clean_flags parses both into dicts
     p.add_argument("--clean", type=str, default=None)
     p.add_argument("--overlay-clean", type=str, default=None)
+    # (this build's own flag) --graph-cut SPEC with -process or -eval: the mask refined by an exact min cut on the GPU (graphcut.py), GrabCut
+    # without the mixtures: "lo=0.1;hi=0.9;lambda=50;it=3;bins=8;conn=8", every key optional ("" is the defaults) -- cells below lo are
+    # hard background, cells above hi hard foreground (defaults: half way from the threshold to 0 and to 1), the rest is decided by up
+    # to `it` cuts with colour histograms of `bins` bins a channel as the models and `lambda` times a contrast weight between `conn`
+    # neighbours.  The cut mask takes the place the CRF mask takes (so not with -crf): -process leaves {stem}-cut-mask.png and cut.json,
+    # -eval eval_cut.json; --clean, -objects, --match-iou, --track-iou and --boundary-tol then describe the cut masks.  The
+    # reference's -grabcut stays what it is there, parsed and never read.  check_cut_flags parses the spec into a dict
+    p.add_argument("--graph-cut", type=str, default=None)
     for flag in ("-masker", "-critic", "-cload", "-mload", "-staticnorm", "-visbesteval", "-salglobal"):
         p.add_argument(flag, type=bool, default=True)
     p.add_argument("--salience-thresh", type=float, default="1.5")
@@ -174,6 +183,7 @@ def parse_args(argv=None):
     check_video_flags(args)
     check_fit_flags(args)
     check_clean_flags(args)
+    check_cut_flags(args)
     return args
 
 
@@ -426,6 +436,32 @@ def check_clean_flags(args):
     for on, flag, thr in ((args.process, "--binarymaskthreshold", args.binarymaskthreshold), (args.eval, "--eval-thresh", args.eval_thresh)):
         if on and spec["hyst"] < thr:
             raise ValueError(f"--clean hyst={spec['hyst']!r} lies below {flag} {thr!r}: the strong threshold is the higher of the two")
+
+
+def check_cut_flags(args):
+    """--graph-cut: a malformed or out-of-range spec and combinations that could not run are refused here, before any GPU work; the
+    flag becomes graphcut.parse_spec's dict (None without the flag).  The cut is seeded at the threshold its path compares with --
+    --binarymaskthreshold for -process, --eval-thresh for -eval -- and lo <= threshold <= hi must hold for each (lo and hi default to
+    graphcut.default_band of that threshold).  Not with --source-video (the stream path has no refinement slot) and not with -crf: two
+    refinements, one slot for the refined mask."""
+    if args.graph_cut is None:
+        return
+    from .graphcut import parse_spec, spec_band
+    if args.source_video:
+        raise ValueError("--graph-cut with --source-video: outside this build (a video source gives the masks and the overlay video only)")
+    if not (args.process or args.eval):
+        raise ValueError("--graph-cut refines the masks of -process or -eval (or -test): give one of them")
+    if args.crf:
+        raise ValueError("--graph-cut with -crf: two refinements and one slot for the refined mask; give one of them")
+    args.graph_cut = spec = parse_spec(args.graph_cut, "--graph-cut")
+    if isinstance(getattr(args, "clean", None), dict) and args.clean["hyst"] is not None:
+        raise ValueError("--clean hyst=... with --graph-cut: the cut mask is hard, it has no strong pixels (hysteresis needs the soft mask)")
+    for on, flag, thr in ((args.process, "--binarymaskthreshold", args.binarymaskthreshold), (args.eval, "--eval-thresh", args.eval_thresh)):
+        if on:
+            try:
+                spec_band(spec, thr)
+            except ValueError as e:
+                raise ValueError(f"{e} ({flag} {thr!r})") from None
 
 
 def check_video_size(w, h, panels):

@@ -1,5 +1,5 @@
 """The reports of ``-eval`` (handler.Handler.eval): the threshold, saliency and CRF-grid sweeps of eval_sweep.json, and
-eval_objects.json, eval_match.json, eval_tracks.json, eval_boundary.json, eval_clean.json.  ``Stacks`` holds the stacks of one run on the device: each
+eval_objects.json, eval_match.json, eval_tracks.json, eval_boundary.json, eval_clean.json, eval_cut.json.  ``Stacks`` holds the stacks of one run on the device: each
 is uploaded when a report first reads it, labelled (objects.label) once per source and matched (objects.match) once per source and
 threshold list.  A report function takes (args, stacks) and returns (the dict of its file, its summary line); everything is scored on
 the GPU and only counts come back.  ``write_json`` is the one writer of every report, here and in process.py."""
@@ -10,9 +10,10 @@ import os
 import numpy as np
 import torch
 
-from . import boundary, clean, metrics, objects, saliency, temporal
+from . import boundary, clean, graphcut, metrics, objects, saliency, temporal
 
 MATCH_MAX_OBJECTS = 64          # objects per frame and side that --match-iou matches and --track-iou follows
+PREDICTIONS = ("mask", "crf", "cut")    # the stacks of the masker's own prediction: the soft mask, and its CRF / graph-cut refinement where the run has one
 
 
 def _json_safe(obj):
@@ -38,7 +39,7 @@ def fmt(v):
 
 class Stacks:
     """The stacks of one -eval run by name, host arrays in `host`: "truth" (bool), "mask" (the probabilities, float32, read with the
-    strict compare of --eval-thresh, main.py:964), the hard stacks "crf", "saliency", "saliency_crf" where the run has them, and the
+    strict compare of --eval-thresh, main.py:964), the hard stacks "crf", "cut" (--graph-cut), "saliency", "saliency_crf" where the run has them, and the
     saliency sweep's inputs "sal" and "preds" (float32), and with --track-motion "frames" (uint8 [n,64,64,3]).  dev uploads a stack when it is first read; labelled and matched likewise.
     With --object-value the run also sets "frames" and `infer`, the critic as objects.value asks it (uint8 [b,64,64,3] -> [b])."""
 
@@ -51,8 +52,8 @@ class Stacks:
             self._made[key] = make()
         return self._made[key]
 
-    def names(self, among=("mask", "crf", "saliency", "saliency_crf")):
-        """The hard stacks this run has, in the reports' order; among=("mask", "crf"): the ones the object reports describe."""
+    def names(self, among=("mask", "crf", "cut", "saliency", "saliency_crf")):
+        """The hard stacks this run has, in the reports' order; among=PREDICTIONS: the ones the object reports describe."""
         return [name for name in among if name in self.host]
 
     def dev(self, name):
@@ -67,9 +68,15 @@ class Stacks:
         stack "mask_clean" / "crf_clean"."""
         return self._once(("clean", name), lambda: clean.clean(self.dev(name), thresh=self.thresh(name), **clean.spec_kwargs(self.args.clean)))
 
+    def cut(self):
+        """--graph-cut: graphcut.cut of the stack "mask" on the evaluation frames (the stack "frames", uint8), seeded with the strict
+        compare of --eval-thresh; made once.  The run puts its mask into `host` as the hard stack "cut"."""
+        return self._once(("cut",), lambda: graphcut.cut(self.dev("frames").contiguous(), self.dev("mask"), float(self.args.eval_thresh),
+                                                         inclusive=False, **graphcut.spec_kwargs(self.args.graph_cut)))
+
     def object_source(self, name):
         """(stack, threshold) the object reports label for a source: with --clean the cleaned stack of a prediction (hard: None)."""
-        if getattr(self.args, "clean", None) and name in ("mask", "crf"):
+        if getattr(self.args, "clean", None) and name in PREDICTIONS:
             return self.cleaned(name).mask, None
         return self.dev(name), self.thresh(name)
 
@@ -123,7 +130,7 @@ def _head(args, **more):
 
 def _blocks(st, report):
     """(prefix of the summary line, block) of every object source."""
-    return [("" if name == "mask" else name + " ", report[name]) for name in st.names(("mask", "crf"))]
+    return [("" if name == "mask" else name + " ", report[name]) for name in st.names(PREDICTIONS)]
 
 
 # ---------------------------------------------------------------------------------------------------------------- eval_sweep.json
@@ -197,7 +204,7 @@ def objects_report(args, st):
     """-objects: the masks as objects, labelled, filtered and scored on the GPU.  With --object-value every block gains "value" (and
     with --min-value-drop "selected"), and the summary line the mean drop and the selected count."""
     report = _head(args)
-    for name in st.names(("mask", "crf")):
+    for name in st.names(PREDICTIONS):
         report[name] = _objects_block(st, name)
     report = _json_safe(report)
 
@@ -232,7 +239,7 @@ def match_report(args, st):
     come back.  With --object-value every threshold's entry gains "value" (_match_values)."""
     iou = objects.parse_match_iou(args.match_iou)
     report = _head(args, max_objects=MATCH_MAX_OBJECTS, iou=iou)
-    for name in st.names(("mask", "crf")):
+    for name in st.names(PREDICTIONS):
         m = st.matched(name, iou)
         report[name] = objects.match_report(m.pred_max, m.truth_max, m.matched_pred, m.matched_truth, objects.sum_iou(m.best, iou), iou,
                                             max_objects=MATCH_MAX_OBJECTS)
@@ -297,7 +304,7 @@ def tracks_report(args, st):
     truth_tr, truth_side, truth_rd = _tracked(st.labelled("truth"), t_iou, gap, motion, reid)
     report = _head(args, max_objects=MATCH_MAX_OBJECTS, track_iou=t_iou, truth=truth_side)
     truth_prev = torch.where(truth_tr.gap == 1, truth_tr.prev, 0) if gap else truth_tr.prev     # (without gaps every link has gap 1)
-    for name in st.names(("mask", "crf")):
+    for name in st.names(PREDICTIONS):
         pred_tr, side, pred_rd = _tracked(st.labelled(name), t_iou, gap, motion, reid)
         report[name] = {"pred": side}
         if fill:
@@ -342,7 +349,7 @@ def clean_report(args, st):
     truth = st.dev("truth")
     truth_on = int(np.count_nonzero(st.host["truth"]))
     report = {"clean": dict(args.clean), "threshold": float(args.eval_thresh)}
-    for name in st.names(("mask", "crf")):
+    for name in st.names(PREDICTIONS):
         res, src, thresh = st.cleaned(name), st.dev(name), st.thresh(name)
         sums = clean.clean_report(res.counts, args.clean)
         inter, union = metrics.iou_counts(res.mask, truth).tolist()
@@ -357,7 +364,28 @@ def clean_report(args, st):
     return report, f"\nCLEAN {clean.spec_text(args.clean)}: " + "; ".join(
         f"{pre}iou {fmt(b['iou'])} (uncleaned {fmt(b['uncleaned']['iou'])}), {b['counts']['holes_filled']} holes filled, "
         f"{b['counts']['components_dropped']} components dropped"
-        for pre, b in (("" if name == "mask" else name + " ", report[name + "_clean"]) for name in st.names(("mask", "crf"))))
+        for pre, b in (("" if name == "mask" else name + " ", report[name + "_clean"]) for name in st.names(PREDICTIONS)))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the graph cut
+def cut_report(args, st):
+    """--graph-cut: the mask refined by graphcut.cut and scored against the truth on the device (metrics.iou_counts), beside the same
+    counts of the plain threshold (metrics.iou_curve at --eval-thresh, the strict compare); the cut's own stats are summed.  Only
+    counts come back."""
+    res, truth = st.cut(), st.dev("truth")
+    thresh = float(args.eval_thresh)
+    sums = graphcut.cut_report(res.stats, args.graph_cut)
+    lo, hi = graphcut.spec_band(args.graph_cut, thresh)
+    inter, union = metrics.iou_counts(res.mask, truth).tolist()
+    inter0, union0 = (int(c[0]) for c in metrics.iou_curve(st.dev("mask"), truth, [thresh]))
+    truth_on = int(np.count_nonzero(st.host["truth"]))
+    counts = lambda i, u, on: {"tp": i, "fp": on - i, "fn": truth_on - i, "inter": i, "union": u, "iou": metrics.ratio(i, u)}
+    report = _json_safe({"graph_cut": dict(args.graph_cut), "threshold": thresh, "lo": lo, "hi": hi,
+                         "before": counts(inter0, union0, sums["seed_on"]), "after": counts(inter, union, sums["on"]),
+                         "stats": {k: v for k, v in sums.items() if k != "spec"}})
+    return report, (f"\nCUT {graphcut.spec_text(args.graph_cut) or 'defaults'}: iou {fmt(report['after']['iou'])} (threshold alone "
+                    f"{fmt(report['before']['iou'])}), {sums['changed']} cells changed, {sums['iterations']} cuts over {sums['frames']} frames, "
+                    f"at most {sums['rounds']} rounds, {sums['not_converged']} not converged")
 
 
 # ---------------------------------------------------------------------------------------------------------------- the outlines
@@ -367,7 +395,7 @@ def boundary_report(args, st):
     tol = boundary.parse_boundary_tol(args.boundary_tol)
     stacks = [(name, st.dev(name), st.thresh(name)) for name in st.names()]
     if getattr(args, "clean", None):
-        stacks += [(name + "_clean", st.cleaned(name).mask, None) for name in st.names(("mask", "crf"))]
+        stacks += [(name + "_clean", st.cleaned(name).mask, None) for name in st.names(PREDICTIONS)]
     if getattr(args, "objects", False):
         stacks.append(("mask_objects", st.labelled("mask").mask, None))
     report = {"tol": tol, "tol2": boundary.tol_squared(tol), "threshold": float(args.eval_thresh)}

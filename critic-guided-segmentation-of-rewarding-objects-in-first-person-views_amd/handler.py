@@ -78,6 +78,7 @@ class Handler:
         self.tracks = None          # -eval -objects --track-iou: the dict of eval_tracks.json
         self.boundary = None        # -eval --boundary-tol: the dict of eval_boundary.json
         self.clean = None           # -eval --clean: the dict of eval_clean.json
+        self.cut = None             # -eval --graph-cut: the dict of eval_cut.json
         self._trace = None          # tests set a dict of lists (Handler.start_trace): per-step indices / losses of the two training loops
 
     def start_trace(self):
@@ -473,14 +474,20 @@ class Handler:
             cols.append(M >= args.binarymaskthreshold)
         if args.crf:                    # main.py:1169-1172 (with --binarymaskthreshold 0 this column lands in position 2)
             cols.append(self.crf(frames, M, None))
+        refined, hard = cols[-1] if args.crf else None, "crf-mask"      # the refined hard mask --clean and -objects read, and its name
+        if getattr(args, "graph_cut", None):    # (this build's flag) not a column: {stem}-cut-mask.png and cut.json; it takes the CRF mask's place
+            os.makedirs(args.mask_output_imgs, exist_ok=True)
+            thresh, res = process.cut_source(args, np.ascontiguousarray(file_bytes, dtype=np.uint8), M[:, 0], self.device)
+            refined, hard = res.mask.cpu().numpy()[:, None], "cut-mask"
+            process.write_cut(args, thresh, res.stats, stems[:len(frames)], self.rank, pngs=refined[:, 0])
         cleaned = None
         if getattr(args, "clean", None):        # (this build's flag) not a column either: {stem}-clean-mask.png and clean.json
             os.makedirs(args.mask_output_imgs, exist_ok=True)
-            source, thresh, res = process.clean_source(args, M[:, 0], cols[-1][:, 0] if args.crf else None, self.device)
+            source, thresh, res = process.clean_source(args, M[:, 0], refined[:, 0] if refined is not None else None, self.device, hard)
             cleaned = res.mask
             process.write_clean(args, source, thresh, res.counts, stems[:len(frames)], self.rank, pngs=cleaned.cpu().numpy())
         if getattr(args, "objects", False):     # (this build's flag) not a column: the by-position naming and the strip stay as they are
-            process.objects_and_tracks(args, M, cols[-1] if args.crf else None, stems[:len(frames)], self.device, self.rank,
+            process.objects_and_tracks(args, M, refined, stems[:len(frames)], self.device, self.rank, hard=hard,
                                        low=np.ascontiguousarray(file_bytes, dtype=np.uint8)
                                        if getattr(args, "track_motion", 0) or getattr(args, "track_reid", None)
                                        or getattr(args, "object_value", False) else None,
@@ -536,6 +543,8 @@ class Handler:
         masks, crf_masks = [], []
         spec = getattr(args, "clean", None)              # --clean: per chunk the cleaned 64 x 64 masks and their counts, on the device
         cleaned, clean_counts, clean_head = [], [], None
+        cut_spec = getattr(args, "graph_cut", None)      # --graph-cut: per chunk the cut 64 x 64 masks and their stats, on the device
+        cut_masks, cut_stats, cut_thr = [], [], None
         lows = [] if getattr(args, "objects", False) and (getattr(args, "track_motion", 0) or getattr(args, "track_reid", None)
                                                           or getattr(args, "object_value", False)) else None     # --track-motion / --track-reid / --object-value: the shrunk frames
         unit = process.unit_table(self.device)
@@ -558,8 +567,16 @@ class Handler:
                 crf_masks.append(labels)
                 dev_labels = torch.from_numpy(np.ascontiguousarray(labels[:, 0]).view(np.uint8)).to(self.device)
                 cols.append(fit.up(dev_labels, guide, low, thresh=0.5, want=("hard",), **sig).hard.cpu().numpy() * np.uint8(255))
+            if cut_spec:                                 # on the shrunk frames; brought to H x W as the CRF labels are; not a column
+                cut_thr, cres = process.cut_source(args, low, Z.contiguous(), self.device)
+                cut_masks.append(cres.mask)
+                cut_stats.append(cres.stats)
+                big = fit.up(cres.mask.view(torch.uint8), guide, low, thresh=0.5, want=("hard",), **sig).hard
+                if self.rank == 0:
+                    process.write_cut_pngs(out_dir, stems[lo:lo + len(host)], big.cpu().numpy())
             if spec:                                     # brought to H x W as the CRF labels are; not a column
-                source, thresh, res = process.clean_source(args, Z, labels[:, 0] if args.crf else None, self.device)
+                source, thresh, res = process.clean_source(args, Z, labels[:, 0] if args.crf else (cres.mask if cut_spec else None),
+                                                           self.device, "cut-mask" if cut_spec else "crf-mask")
                 clean_head = (source, thresh)
                 cleaned.append(res.mask)
                 clean_counts.append(res.counts)
@@ -570,12 +587,15 @@ class Handler:
         print()
         M = np.concatenate(masks, axis=0)
         crf_mask = np.concatenate(crf_masks, axis=0) if args.crf else None
+        if cut_spec:
+            crf_mask = torch.cat(cut_masks).cpu().numpy()[:, None]
+            process.write_cut(args, cut_thr, torch.cat(cut_stats), stems[:len(files)], self.rank)
         if spec:
             process.write_clean(args, *clean_head, torch.cat(clean_counts), stems[:len(files)], self.rank)
         if getattr(args, "objects", False):
             process.objects_and_tracks(args, M, crf_mask, stems[:len(files)], self.device, self.rank,
                                        low=torch.cat(lows) if lows is not None else None, cleaned=torch.cat(cleaned) if spec else None,
-                                       infer=self._value_infer())
+                                       infer=self._value_infer(), hard="cut-mask" if cut_spec else "crf-mask")
         write_json(f"{out_dir}/fit.json", {"frame_size": [H, W], "net_size": [fit.SIDE, fit.SIDE], "sigma_spatial": args.fit_spatial,
                                            "sigma_range": args.fit_range, "radius": fit.RADIUS, "frames": len(files)}, self.rank)
         return M
@@ -948,6 +968,10 @@ class Handler:
         if sweep:
             self.sweep = sweep
             write_json(self.path + "eval_sweep.json", sweep, self.rank)
+        if getattr(args, "graph_cut", None):    # (this build's flag) the mask refined by a min cut on the GPU; it stands where the CRF mask stands
+            st.host["frames"] = frames if frames.dtype == np.uint8 else (255 * frames).astype(np.uint8)
+            self.cut = report(evaluate.cut_report, "eval_cut.json")
+            st.host["cut"] = st.cut().mask.cpu().numpy()
         if getattr(args, "clean", None):        # (this build's flag) the masks cleaned on the GPU; the reports below then read those
             self.clean = report(evaluate.clean_report, "eval_clean.json")
         if getattr(args, "objects", False):     # (this build's flags) the masks as objects, matched to the truth's, followed through the frames

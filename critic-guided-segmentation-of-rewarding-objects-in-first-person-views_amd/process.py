@@ -3,14 +3,15 @@ size, how a shrunk uint8 frame is fed to the network, the PNG columns with their
 ``--track-iou`` on the 64 x 64 masks (objects.json, tracks.json and their PNGs; ``video_reports`` writes the two reports of
 ``--source-video --overlay-tracks`` without PNGs; with ``--object-value`` the objects are scored by the critic and, with
 ``--min-value-drop``, selected before they are reported and tracked: {stem}-valued-mask.png), and ``--clean`` (``clean_source``, ``write_clean``: clean.json and the
-{stem}-clean-mask.png files).  Under data parallelism every rank makes the GPU
+{stem}-clean-mask.png files), and ``--graph-cut`` (``cut_source``, ``write_cut``: cut.json and the {stem}-cut-mask.png files; the cut
+mask then stands where the CRF mask stands, under the name "cut-mask").  Under data parallelism every rank makes the GPU
 calls and rank 0 writes."""
 import os
 
 import numpy as np
 import torch
 
-from . import clean, objects
+from . import clean, graphcut, objects
 from .evaluate import MATCH_MAX_OBJECTS, write_json
 
 PROCESS_MAX_OBJECTS = 256       # rows of the object table of -process -objects
@@ -56,28 +57,29 @@ def write_columns(out_dir, stems, frames, cols, concatenated):
                 Image.fromarray(rgb(c[i])).save(f"{out_dir}/{stem}-{kind}.png")
 
 
-def binary_source(args, M, crf_mask, device, cleaned=None):
+def binary_source(args, M, crf_mask, device, cleaned=None, hard="crf-mask"):
     """The stack -objects and --track-iou describe: (source name, threshold, device stack, objects.label's keywords) -- with -crf the
     CRF masks, else M >= --binarymaskthreshold (the comparison of the thresholded column).  cleaned: with --clean the bool stack
-    clean_source made of that one; it is handed on under the name "clean-mask" / "clean-crf-mask"."""
+    clean_source made of that one; it is handed on under the name "clean-mask" / "clean-crf-mask".  hard: the name of the refined
+    stack in crf_mask's place, "cut-mask" with --graph-cut (then "clean-cut-mask")."""
     kw = dict(connectivity=args.connectivity, min_area=args.min_area)
     if cleaned is not None:
-        return ("clean-crf-mask", None, cleaned, kw) if crf_mask is not None else ("clean-mask", float(args.binarymaskthreshold), cleaned, kw)
+        return ("clean-" + hard, None, cleaned, kw) if crf_mask is not None else ("clean-mask", float(args.binarymaskthreshold), cleaned, kw)
     if crf_mask is not None:
-        return "crf-mask", None, torch.from_numpy(np.ascontiguousarray(crf_mask[:, 0])).to(device), kw
+        return hard, None, torch.from_numpy(np.ascontiguousarray(crf_mask[:, 0])).to(device), kw
     thresh = float(args.binarymaskthreshold)
     return ("thresholded-mask", thresh, torch.from_numpy(np.ascontiguousarray(M[:, 0], dtype=np.float32)).to(device),
             dict(kw, thresh=thresh, inclusive=True))
 
 
-def clean_source(args, soft, hard, device):
+def clean_source(args, soft, hard, device, hard_name="crf-mask"):
     """--clean: the stack binary_source names, cleaned on the GPU (clean.clean).  soft: the masks [n,64,64] float32 (array or tensor),
-    read as soft >= --binarymaskthreshold; hard: with -crf the CRF labels [n,64,64] bool, which then are the source.  Returns (source
-    name, threshold, clean.Cleaned on the device)."""
+    read as soft >= --binarymaskthreshold; hard: with -crf the CRF labels [n,64,64] bool, which then are the source (with --graph-cut
+    the cut masks, hard_name="cut-mask").  Returns (source name, threshold, clean.Cleaned on the device)."""
     to_dev = lambda a, dtype: a.to(device) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(device)
     kw = clean.spec_kwargs(args.clean)
     if hard is not None:
-        return "crf-mask", None, clean.clean(to_dev(hard, bool), **kw)
+        return hard_name, None, clean.clean(to_dev(hard, bool), **kw)
     thresh = float(args.binarymaskthreshold)
     return "thresholded-mask", thresh, clean.clean(to_dev(soft, np.float32), thresh=thresh, inclusive=True, **kw)
 
@@ -104,19 +106,52 @@ def write_clean_pngs(out_dir, stems, masks):
         Image.fromarray(np.repeat(grey[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-clean-mask.png")
 
 
-def objects_and_tracks(args, M, crf_mask, stems, device, rank, low=None, cleaned=None, infer=None):
+def cut_source(args, frames, soft, device):
+    """--graph-cut: the masks refined by graphcut.cut, seeded as the thresholded column compares (soft >= --binarymaskthreshold).
+    frames: uint8 [n,64,64,3], soft: float32 [n,64,64] (arrays or tensors).  Returns (threshold, graphcut.Cut on the device)."""
+    to_dev = lambda a, dtype: a.to(device) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(device)
+    thresh = float(args.binarymaskthreshold)
+    return thresh, graphcut.cut(to_dev(frames, np.uint8), to_dev(soft, np.float32), thresh, inclusive=True, **graphcut.spec_kwargs(args.graph_cut))
+
+
+def write_cut(args, thresh, stats, stems, rank, pngs=None):
+    """Rank 0 writes {R}/cut.json -- the spec, the source threshold and the band it gives, the summed stats and the stats per stem --
+    and, when pngs (uint8 or bool [n,H,W]) is given, per frame {R}/{stem}-cut-mask.png as 0 / 255 grey RGB (not a column: the
+    by-position naming and the concatenated strip stay as they are).  stats: int32 [n,8] of graphcut.cut, tensor or array."""
+    if rank != 0:
+        return
+    out_dir = args.mask_output_imgs
+    c = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+    lo, hi = graphcut.spec_band(args.graph_cut, thresh)
+    write_json(f"{out_dir}/cut.json", {"source": "thresholded-mask", "threshold": thresh, "lo": lo, "hi": hi,
+                                       **graphcut.cut_report(c, args.graph_cut),
+                                       "per_frame": {stem: {k: int(v) for k, v in zip(graphcut.STATS, c[i])} for i, stem in enumerate(stems)}})
+    if pngs is not None:
+        write_cut_pngs(out_dir, stems, pngs)
+
+
+def write_cut_pngs(out_dir, stems, masks):
+    """{R}/{stem}-cut-mask.png of a run of frames: masks uint8 or bool [n,H,W], non-zero = on, written as 0 / 255 grey RGB."""
+    from PIL import Image
+    for i, stem in enumerate(stems):
+        grey = (np.asarray(masks[i]) != 0) * np.uint8(255)
+        Image.fromarray(np.repeat(grey[:, :, None], 3, axis=2)).save(f"{out_dir}/{stem}-cut-mask.png")
+
+
+def objects_and_tracks(args, M, crf_mask, stems, device, rank, low=None, cleaned=None, infer=None, hard="crf-mask"):
     """-process -objects [--track-iou]: the stack of binary_source labelled on the GPU once (objects.py; labels, mask and counts do not
     depend on the table's rows), then reported as objects and, if asked for, as tracks.  low: with --track-motion the uint8 frames
     [n,64,64,3] the masks were made from (tensor or array, in the order of stems); --track-reid needs them too.  cleaned: with --clean the cleaned bool stack on the
     device, which is then the one described; the reports' header gains "clean".  infer: with --object-value the critic, uint8 frames
     [b,64,64,3] -> values [b] in eval mode; low is then needed too.  The objects 1..64 of every frame are scored (objects.value), and
-    with --min-value-drop the ones that pass are what the mask PNGs and the tracks describe (objects.select)."""
+    with --min-value-drop the ones that pass are what the mask PNGs and the tracks describe (objects.select).  hard: binary_source's."""
     want_tracks = bool(getattr(args, "track_iou", ""))
     want_value = bool(getattr(args, "object_value", False))
-    source, thresh, stack, kw = binary_source(args, M, crf_mask, device, cleaned)
+    source, thresh, stack, kw = binary_source(args, M, crf_mask, device, cleaned, hard)
     res = objects.label(stack, max_objects=PROCESS_MAX_OBJECTS, want_labels=want_tracks or want_value, want_mask=True, **kw)
     head = {"source": source, "threshold": thresh, "connectivity": args.connectivity, "min_area": args.min_area,
-            **({"clean": dict(args.clean)} if cleaned is not None else {})}
+            **({"clean": dict(args.clean)} if cleaned is not None else {}),
+            **({"graph_cut": dict(args.graph_cut)} if hard == "cut-mask" else {})}
     valued = drops = None
     if want_value:
         if low is None or infer is None:

@@ -1398,6 +1398,58 @@ int cgs_temporal_flow(const uint8_t* low, int32_t n, int32_t search, int8_t* fwd
 int cgs_temporal_smooth_mc(const float* z, const uint8_t* low, const int8_t* fwd, const int8_t* bwd, int32_t n, int32_t f0, int32_t f1,
                            int32_t radius, float sigma_r, float* out, cgs_stream_t stream);
 
+/* ---- GrabCut-style mask refinement by an exact min cut (csrc/graph_cut.hip) --------------------------------------------------------------
+ * cgs_graph_cut: for each of n frames of h x w cells (1 <= h, w <= CGS_CUT_MAX_SIDE), frames uint8 [n][h][w][3] (RGB), z fp32 [n][h][w],
+ * the labelling of a binary graph cut that is seeded by the mask and uses colour models of the frame's own foreground and background.
+ * Everything is an integer or an fp32 compare; costs are in S = 16 units per nat and come from three int32 tables the caller builds in
+ * float64: wa, wd [CGS_CUT_TABLE] and l [CGS_CUT_LOG_TABLE] (below).  This comment is the rule.
+ *   1. seed    the seed label of a cell is z > thresh (CGS_OBJ_F32_GT) or z >= thresh (CGS_OBJ_F32_GE), compared in fp32, a NaN is off.
+ *              A cell is hard background where z < lo or z is a NaN, hard foreground where z > hi, and unknown otherwise.
+ *              lo <= thresh <= hi, so a hard cell agrees with its seed label.  The first labelling is the seed labelling.
+ *   2. n-links connectivity 4: the pairs of horizontal and vertical neighbours (axial); 8: also the two diagonals.  d2 of a pair is the
+ *              squared distance of its two RGB triples (an integer), P the number of unordered pairs of the frame, and
+ *              m = max(1, sum(d2) / P) in integer division (m = 1 when P = 0); idx = min(CGS_CUT_TABLE - 1, 64 d2 / m), again an integer
+ *              division.  The capacity of the pair, in both directions, is wa[idx] when it is axial and wd[idx] when it is diagonal.
+ *              wa[i] = rint(S lambda exp(-i / 128)), wd[i] = rint(S lambda exp(-i / 128) / sqrt(2)), lambda a whole number 0..100:
+ *              GrabCut's beta = 1 / (2 <d2>) in integers.
+ *   3. models  histograms, not mixtures: b = `bins` (4 or 8) bins a channel, B = b^3, bin = (R >> s) b^2 + (G >> s) b + (B >> s) with
+ *              s = 8 - log2 b.  H1 / H0 count the cells the current labelling has on / off (hard cells included), N1 / N0 are their
+ *              sizes.  N1 = 0 or N0 = 0: the labelling stays, status gains CGS_CUT_EMPTY and the frame is finished.  Else an unknown
+ *              cell has cost_fg = l[N1 + B] - l[H1[bin] + 1] and cost_bg = l[N0 + B] - l[H0[bin] + 1], l[k] = rint(S ln k) for
+ *              k = 1 .. 4096 + 512 (l[0] is not read), and the t-links source -> cell = cost_bg, cell -> sink = cost_fg.  A hard
+ *              foreground cell has source -> cell = BIG, cell -> sink = 0, a hard background cell the mirror; BIG = 8 wa[0] + 1 is more
+ *              than a cell's n-links together, and 4096 BIG < 2^31.
+ *   4. cut     the new labelling is on exactly in the cells that cannot reach the sink in the residual graph of a maximum flow: the
+ *              largest source side of a minimum cut, which is unique and depends neither on the algorithm nor on any order.  `energy`
+ *              is the value of that flow in the whole graph (the part min(source -> cell, cell -> sink) that passes straight through
+ *              a cell included).
+ *   5. iterate steps 3 and 4 up to `iters` times (1..CGS_CUT_MAX_ITERS).  A cut that returns the labelling it started from ends the
+ *              iteration; status gains CGS_CUT_EARLY when fewer than `iters` cuts had been run by then.
+ *   6. out     uint8 [n][h][w], 1 = on.  stats int32 [n][CGS_CUT_FIELDS]: status bits, cuts completed, the most rounds a cut of the
+ *              frame took (below), energy of the last completed cut (0: none), cells on in the seed labelling, cells on in out, unknown
+ *              cells, cells of out that differ from the seed labelling.
+ * How it is computed (no part of the rule but for `rounds`): one workgroup per frame, the whole graph in LDS; push-relabel with the
+ * source folded into an initial excess, in rounds.  A round is an exact backward breadth-first search from the sink over residual arcs (at
+ * most h w steps); the cut is finished when no cell with excess has a finite distance -- the label is then "distance infinite" -- else
+ * a constant number of sweeps follows, each a push phase and a relabel phase with a barrier between them.  The rounds of a cut are the
+ * searches it ran, at least 1.  A cut that is not finished by its max_rounds-th search leaves the labelling it started from, sets
+ * CGS_CUT_NOT_CONVERGED, counts max_rounds as its rounds and ends the frame: every loop is bounded, whatever the input.
+ * frames, z, wa, wd, l, out, stats not NULL, z / wa / wd / l / stats 4-byte aligned, n >= 1, src_kind CGS_OBJ_F32_GT or CGS_OBJ_F32_GE,
+ * lo <= thresh <= hi (none a NaN), connectivity 4 or 8, bins 4 or 8, 1 <= iters <= CGS_CUT_MAX_ITERS, 1 <= max_rounds <= CGS_CUT_MAX_ROUNDS,
+ * else CGS_ERR_BADARG (nothing is launched); then 1 <= h, w <= CGS_CUT_MAX_SIDE, else CGS_ERR_UNSUPPORTED.  Tables other than the rule's
+ * (wa[0] above 1600, which would not fit the 16-bit residuals) are the caller's error; no read or write is out of range for any content.
+ * cgs_graph_cut_sweeps is the same with the number of sweeps a round (16, 32 or 64, else CGS_ERR_UNSUPPORTED) chosen by the caller: the
+ * result is the rule's at every value but for `rounds`; tools/time_graph_cut.py times the three.  cgs_graph_cut runs CGS_CUT_SWEEPS.   */
+enum { CGS_CUT_MAX_SIDE = 64, CGS_CUT_FIELDS = 8, CGS_CUT_TABLE = 1024, CGS_CUT_LOG_TABLE = 4096 + 512 + 1, CGS_CUT_MAX_ITERS = 8 };
+enum { CGS_CUT_SCALE = 16, CGS_CUT_MAX_LAMBDA = 100, CGS_CUT_SWEEPS = 16, CGS_CUT_MAX_ROUNDS = 1 << 16 };
+enum { CGS_CUT_EMPTY = 1, CGS_CUT_EARLY = 2, CGS_CUT_NOT_CONVERGED = 4 };
+int cgs_graph_cut(const uint8_t* frames, const float* z, int32_t src_kind, float thresh, float lo, float hi, int32_t n, int32_t h, int32_t w,
+                  int32_t connectivity, int32_t bins, int32_t iters, int32_t max_rounds, const int32_t* wa, const int32_t* wd,
+                  const int32_t* l, uint8_t* out, int32_t* stats, cgs_stream_t stream);
+int cgs_graph_cut_sweeps(const uint8_t* frames, const float* z, int32_t src_kind, float thresh, float lo, float hi, int32_t n, int32_t h,
+                         int32_t w, int32_t connectivity, int32_t bins, int32_t iters, int32_t max_rounds, int32_t sweeps, const int32_t* wa,
+                         const int32_t* wd, const int32_t* l, uint8_t* out, int32_t* stats, cgs_stream_t stream);
+
 const char* cgs_build_arch(void);
 int cgs_abi_version(void);
 
